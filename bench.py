@@ -1,6 +1,7 @@
 """Benchmark: stories15M batched prefill on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline] [--global-batch G]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--global-batch G]
+    python bench.py --full [--no-cpu-baseline] [--no-kernel-breakdown] [--no-x6] ...
     N > 1: either under python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N,
     or plain `python bench.py --gpus N`, which starts the N rank processes itself (spawn_ranks)
     --global-batch G: strong scaling instead (G rows split over the N GPUs; C4 is G = 2048)
@@ -13,10 +14,25 @@ llama3.py:163-211) and the step ends with the single RCCL gather of every rank's
 logits to rank 0 over xGMI (on the context stream, after the forward that wrote the rows).
 Rank 0 prints one JSON line.
 
+A plain run does only what `value` needs: it sets up, runs the W warm-up steps, times the K
+steps, writes the outputs if --dump-outputs is given, and prints the line (metric, value, unit,
+ms_per_step, higher_is_better, dtype, the configuration and the library hash).  Everything else
+described below — ms_per_step_median, the all-rows / serialized / roofline passes, whole_step,
+gemm_x6, the host path, ms_gather_alone, the finite-logits probe, cpu_baseline, kernel_ms — runs
+only with --full, after the same timed steps, and adds its fields to the same line (the
+--no-cpu-baseline / --no-kernel-breakdown / --no-x6 switches take parts of --full out again).
+With a communicator (N > 1 or --rccl) the device proof and the gather self-check belong to the
+line itself and run either way.
+--dump-outputs DIR: after the timed steps rank 0 writes DIR/logits.npy, the float32 logits the
+last timed step left in HBM (what a caller of the timed path receives: [B, vocab] at N = 1, the
+gathered [N*B, vocab] rows with a communicator).  Weights and ids are seeded, so the same
+arguments give the same inputs on every run and two builds can be compared output for output.
+Above 64 MB a fixed, seeded sample of the rows is written instead (default_rng(0), sorted).
+
 value: the product forward (layers as two batch-row ranges on two HIP streams,
 l3_set_batch_split; the last block's attention / O-proj / FFN on each sequence's last
 position, the only rows that reach the logits, l3_set_last_layer_rows — its QKV GEMM still
-appends every position to the KV cache), no events in the timed region; beside it
+appends every position to the KV cache), no events in the timed region; beside it (--full)
 ms_per_step_all_rows_last_layer, the same steps with every position through the last block.
 The roofline, per-kernel and C5 passes run every position of every layer.
 roofline: the dominant kernel is the fused gate|up GEMM (N = 2*FD = 1536, K = 288,
@@ -628,11 +644,33 @@ def check_gathered_group(ctx, N, bpg, VS, gathered_dev, ids_blk):
     return N
 
 
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(ctx, dirname, src_dev, rows, cols):
+    """--dump-outputs: the [rows, cols] float32 logits at ``src_dev`` to ``dirname``/logits.npy
+    (the d2h joins the streams that wrote them).  Above DUMP_LIMIT_BYTES a fixed sample of the
+    rows: default_rng(0).choice without replacement, sorted, the same on every run."""
+    out = np.empty((rows, cols), np.float32)
+    ctx.d2h(out, src_dev)
+    keep = DUMP_LIMIT_BYTES // (cols * 4)
+    if rows > keep:
+        out = out[np.sort(np.random.default_rng(0).choice(rows, keep, replace=False))]
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "logits.npy"), np.ascontiguousarray(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other measurement and check of the "
+                         "line (median, all-rows / serialized / roofline passes, x6 path, host path, "
+                         "CPU baseline, per-kernel breakdown); off: the timed steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the logits of the last timed step to DIR/logits.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-breakdown", action="store_true",
                     help="skip the untimed all-kernel event pass (profiling runs)")
@@ -664,6 +702,8 @@ def main():
                     help="start the rank processes here even at N=1 (rehearses the launcher-free "
                          "N>1 path; N>1 without WORLD_SIZE spawns anyway)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
     if "WORLD_SIZE" not in os.environ and (a.gpus > 1 or a.spawn) and not a.single_process:
         # no launcher: this process only starts the ranks (nothing here has touched the GPU)
         argv = [x for x in sys.argv[1:] if x != "--spawn"]
@@ -769,16 +809,26 @@ def main():
     # value: the product forward (batch split into row ranges on concurrent streams), no events
     elapsed, elapsed_min = timed_steps(a.steps)
 
+    # what the last timed step left for its caller: the gathered rows on rank 0 with a gather in
+    # the step, else this rank's own logits
+    if a.dump_outputs and dist.rank == 0:
+        if gathered_dev is not None and (a.single_process or step_gather):
+            dump_outputs(ctx, a.dump_outputs, gathered_dev, bpg * N, VS)
+        else:
+            dump_outputs(ctx, a.dump_outputs, logits_dev, bpg, VS)
+
     # beside `value` (BASELINE.md's plan: the median step): the same steps one at a time, each
     # bracketed by a device sync — the median of those, whose gaps the back-to-back mean hides
-    per_step = []
-    for _ in range(a.steps):
-        sync()
-        t0 = time.perf_counter()
-        step()
-        sync()
-        per_step.append(time.perf_counter() - t0)
-    median_ms = dist.max(float(np.median(per_step))) * 1e3
+    median_ms = None
+    if a.full:
+        per_step = []
+        for _ in range(a.steps):
+            sync()
+            t0 = time.perf_counter()
+            step()
+            sync()
+            per_step.append(time.perf_counter() - t0)
+        median_ms = dist.max(float(np.median(per_step))) * 1e3
 
     # N > 1: the gathered rows against rank 0's own recomputation (untimed)
     if a.single_process:
@@ -786,6 +836,42 @@ def main():
     else:
         checked = check_gathered(ctx, dist, bpg, VS, gathered_dev) if step_gather else None
     dist.barrier()
+
+    tokens = bpg * SEQ * dist.world * a.steps
+    # the line of a plain run; --full adds its fields to these below
+    head = {
+        "metric": METRIC,
+        "value": round(tokens / elapsed, 1),
+        "unit": "tokens/s",
+        "n_gpus": dist.world,
+        "steps": a.steps,
+        "warmup": a.warmup,
+        "ms_per_step": round(elapsed / a.steps * 1e3, 4),
+        "timing": (f"value and ms_per_step: wall clock of {a.steps} back-to-back steps after {a.warmup} "
+                   "warm-up steps, bracketed by a barrier and a device sync, max over ranks, mean per step"),
+        "full": bool(a.full),
+        "batch_split": a.split if a.split is not None else 2,
+        "ms_per_step_rank_min": round(elapsed_min / a.steps * 1e3, 4),
+        "ms_per_step_rank_max": round(elapsed / a.steps * 1e3, 4),
+        "launcher": "single-process" if a.single_process else (
+            "spawned" if os.environ.get("L3_LAUNCH_KEY", "").startswith("spawn_") else
+            "torch.distributed.run" if "TORCHELASTIC_RUN_ID" in os.environ else "none"),
+        "gather_self_check_ranks": checked,
+        "higher_is_better": True,
+        "scaling": "strong" if a.global_batch else "weak",
+        "vs_baseline": None,
+        "dtype": "fp32",
+        "data": "synthetic: stories15M-shaped N(0,0.02^2) weights (seed 0), uniform random ids",
+        "config": {"workload": f"stories15M prefill, B={bpg} per GPU x L={SEQ}, start_pos 0",
+                   "global_batch": bpg * dist.world, "seq_len": SEQ,
+                   "parallelism": f"dp{dist.world} (batch rows) + RCCL logits gather"},
+        "lib": {"version": l3hip.version(), "source_hash": l3hip.source_hash()},
+        **(dist.info or {}),
+    }
+    if not a.full:
+        if dist.rank == 0:
+            print(json.dumps(head))
+        return
 
     # beside `value`: the same K steps with the last block run on every position (the product
     # runs its attention / O-proj / FFN on each sequence's last position only: the rows that
@@ -871,7 +957,6 @@ def main():
 
     if dist.rank != 0:
         return
-    tokens = bpg * SEQ * dist.world * a.steps
     T = bpg * SEQ
     gu_ms, gu_n = stats["gateup"]
     dn_ms, dn_n = stats["down"]
@@ -896,39 +981,15 @@ def main():
                   "note": "per GPU; executed = the timed step's own work (last block on each sequence's "
                           "last position, step_flops in bench.py), wall clock of the same steps as value"}
     out = {
-        "metric": METRIC,
-        "value": round(tokens / elapsed, 1),
-        "unit": "tokens/s",
-        "n_gpus": dist.world,
-        "steps": a.steps,
-        "warmup": a.warmup,
-        "ms_per_step": round(elapsed / a.steps * 1e3, 4),
-        "timing": (f"value and ms_per_step: wall clock of {a.steps} back-to-back steps after {a.warmup} "
-                   "warm-up steps, bracketed by a barrier and a device sync, max over ranks, mean per step; "
-                   "ms_per_step_median: the median of the same steps run one at a time, each between syncs"),
+        **head,
+        "timing": head["timing"] + ("; ms_per_step_median: the median of the same steps run one at a "
+                                    "time, each between syncs"),
         "ms_per_step_median": round(median_ms, 4),
         "ms_per_step_serialized": round(elapsed_serial / a.steps * 1e3, 4),
         "ms_per_step_all_rows_last_layer": round(elapsed_all_rows / a.steps * 1e3, 4),
-        "batch_split": a.split if a.split is not None else 2,
         "ms_per_step_with_logits_d2h": round(host_ms, 4),
         "host_path_tokens_per_s": round(T * dist.world * d2h_steps / elapsed_d2h, 1),
-        "ms_per_step_rank_min": round(elapsed_min / a.steps * 1e3, 4),
-        "ms_per_step_rank_max": round(elapsed / a.steps * 1e3, 4),
-        "launcher": "single-process" if a.single_process else (
-            "spawned" if os.environ.get("L3_LAUNCH_KEY", "").startswith("spawn_") else
-            "torch.distributed.run" if "TORCHELASTIC_RUN_ID" in os.environ else "none"),
         "ms_gather_alone": None if gather_ms is None else round(gather_ms, 4),
-        "gather_self_check_ranks": checked,
-        "higher_is_better": True,
-        "scaling": "strong" if a.global_batch else "weak",
-        "vs_baseline": None,
-        "dtype": "fp32",
-        "data": "synthetic: stories15M-shaped N(0,0.02^2) weights (seed 0), uniform random ids",
-        "config": {"workload": f"stories15M prefill, B={bpg} per GPU x L={SEQ}, start_pos 0",
-                   "global_batch": bpg * dist.world, "seq_len": SEQ,
-                   "parallelism": f"dp{dist.world} (batch rows) + RCCL logits gather"},
-        "lib": {"version": l3hip.version(), "source_hash": l3hip.source_hash()},
-        **(dist.info or {}),
         "whole_step": whole_step,
         "roofline": {"kernel": f"gemm gate|up (fused SwiGLU epilogue), M={T} K=288 N=1536",
                      "pass": "same workload and step count, batch split off (HIP events need "

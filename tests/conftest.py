@@ -7,6 +7,7 @@
   the oracle on ``sys.path``.
 """
 
+import glob
 import os
 import sys
 
@@ -28,7 +29,19 @@ def pytest_configure(config):
 
 
 def load_golden(name):
-    return np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False)
+    """``name``.npz, or — a fixture stored in parts to keep every committed file under 1 MiB
+    (c5_slice: three float64 logit rows of 128256) — the arrays of ``name``.part*.npz merged."""
+    path = os.path.join(GOLDEN, name + ".npz")
+    if os.path.exists(path):
+        return np.load(path, allow_pickle=False)
+    parts = sorted(glob.glob(os.path.join(GOLDEN, name + ".part*.npz")))
+    if not parts:
+        raise FileNotFoundError(path)
+    out = {}
+    for p in parts:
+        with np.load(p, allow_pickle=False) as z:
+            out.update({k: z[k] for k in z.files})
+    return out
 
 
 @pytest.fixture(scope="session")

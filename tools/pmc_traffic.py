@@ -75,7 +75,7 @@ def main():
     algo = 4 * (ROWS * D + 2 * FD * D + ROWS * FD)
     res = {"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE, separate passes, " +
                      ("python bench.py --workload c5 --layers 2 --steps 1 --warmup 1" if c5 else
-                      "python bench.py --steps 2 --warmup 1 --split 1 (every launch full size)"),
+                      "python bench.py --full --steps 2 --warmup 1 --split 1 (every launch full size)"),
            "correction": "bytes = (2*FETCH_SIZE + WRITE_SIZE) * 1024 (gfx950 FETCH_SIZE half-count) for "
                          "the 16-B/lane coalesced streaming kernels only; others uncalibrated (range)",
            "workload_rows": ROWS,
