@@ -136,21 +136,50 @@ int l3_set_gemm_x6(l3_ctx* ctx, int32_t on);
 /* Same with device-resident ids (int32 [B, L]) and logits ([B, VS]); async. */
 int l3_forward_dev(l3_ctx* ctx, const int32_t* ids_dev, int32_t B, int32_t L,
                    int32_t start_pos, float* logits_dev);
+/* Sampling (extension; the reference decodes greedily).  With temperature > 0 every l3_greedy_*
+ * entry point below picks its tokens by temperature / top-k / top-p sampling on the device
+ * instead of argmax; temperature 0 (the default) restores greedy decoding, unchanged.
+ * The rule for one fp32 logits row z[0..n) and a uniform u in [0, 1) (DESIGN.md "Sampling"):
+ *   - a NaN in the row or a maximum that is not finite: the argmax rule's answer;
+ *   - w_i = exp((z_i - max z) / temperature); rank order is z descending, ties by lower index;
+ *   - K = the first top_k ranks if 0 < top_k < n, else all;
+ *   - S = the shortest rank-order prefix of K whose mass reaches top_p * mass(K) (top_p < 1),
+ *     at least one token; else K;
+ *   - the token is the first i of S, in ascending index order, whose running mass exceeds
+ *     u * mass(S).
+ * u is a pure function of (seed, batch row, position of the step's last token) — Philox4x32-10
+ * with key = the seed's 32-bit halves and counter = (row, pos, 0, 0), u = (x0 >> 8) * 2^-24 —
+ * so one seed gives one token sequence whether a step ran eagerly, as a graph replay, ahead of
+ * the caller and undone, or inside l3_greedy_generate_host.  The kernel is deterministic: the
+ * same logits, parameters and u give the same token on every launch.
+ * Errors: temperature not finite or < 0, top_k < 0, top_p outside (0, 1]; a context that is a
+ * member of a multi-device l3_group is refused.  While sampling is on the captured decode step is
+ * the graph of kernels (l3_decode_persistent reports 0); the sample launch is counted under
+ * L3_K_ARGMAX. */
+int l3_set_sampling(l3_ctx* ctx, float temperature, int32_t top_k, float top_p, uint64_t seed);
+/* The parameters in force (any pointer may be NULL). */
+int l3_get_sampling(l3_ctx* ctx, float* temperature, int32_t* top_k, float* top_p, uint64_t* seed);
+/* The uniform a sampling step draws for (seed, row, pos); host only, no device needed. */
+int l3_sample_uniform(uint64_t seed, int32_t row, int32_t pos, float* u);
+
 /* One greedy step (Llama.generate body, llama3.py:313-320): forward + argmax
- * (lowest index on ties, as np.argmax).  next_ids_host [B] int64;
+ * (lowest index on ties, as np.argmax), or with sampling on (l3_set_sampling) one sampled
+ * token per row, drawn at pos = start_pos + L - 1.  next_ids_host [B] int64;
  * logits_host may be NULL. */
 int l3_greedy_step_host(l3_ctx* ctx, const int64_t* ids_host, int32_t B, int32_t L,
                         int32_t start_pos, int64_t* next_ids_host, float* logits_host);
 
 /* The whole greedy loop on the device (same schedule and ids as Llama.generate,
  * llama3.py:310-321, but not lazy: all max_new_tokens - L steps run, each one
- * hipGraph replay, one copy-back at the end).  out_ids_host [B, max_new_tokens - L]. */
+ * hipGraph replay, one copy-back at the end).  out_ids_host [B, max_new_tokens - L].
+ * With sampling on (l3_set_sampling) the ids are the sampled ones, the same as step by step. */
 int l3_greedy_generate_host(l3_ctx* ctx, const int64_t* ids_host, int32_t B, int32_t L,
                             int32_t max_new_tokens, int64_t* out_ids_host);
 /* The same loop, also returning each step's winning logit (the value np.argmax picked at
  * llama3.py:320, i.e. logits[b, -1, id]) in out_vals [B, max_new_tokens - L] fp32: the replayed
  * steps record it beside the id on the device, the eager steps read it from their logits rows.
- * Pins a decode path's values, not only its ids, against the reference (extension). */
+ * Pins a decode path's values, not only its ids, against the reference (extension).  With
+ * sampling on, the value is the logit of the token picked. */
 int l3_greedy_generate_values_host(l3_ctx* ctx, const int64_t* ids_host, int32_t B, int32_t L,
                                    int32_t max_new_tokens, int64_t* out_ids_host, float* out_vals);
 
@@ -173,6 +202,12 @@ int l3_op_softmax_host(l3_ctx* ctx, const float* x, int64_t rows, int64_t n, flo
 /* argmax over the last axis with np.argmax's tie-break: first index of the maximum, the first
  * NaN if any (llama3.py:320); rows x n -> rows int32. */
 int l3_op_argmax_host(l3_ctx* ctx, const float* x, int64_t rows, int64_t n, int32_t* out);
+/* One sampled token per row by the rule of l3_set_sampling (temperature 0: the argmax);
+ * logits rows x n -> rows int32.  u [rows] holds each row's uniform in [0, 1), or is NULL: row r
+ * then draws l3_sample_uniform(seed, row0 + r, pos). */
+int l3_op_sample_host(l3_ctx* ctx, const float* logits, int64_t rows, int64_t n, float temperature,
+                      int32_t top_k, float top_p, const float* u, uint64_t seed, int32_t row0,
+                      int32_t pos, int32_t* out);
 /* silu (llama3.py:27-28); n elements. */
 int l3_op_silu_host(l3_ctx* ctx, const float* x, int64_t n, float* y);
 /* RMSNorm (llama3.py:111-114); rows x dim. */

@@ -78,6 +78,41 @@ struct DecState {
     float* hist_val;   // null, or beside hist: each step's winning logit (the value argmax picked)
 };
 
+// Sampling (sample.hip): temperature / top-k / top-p parameters of a context, as the kernel
+// reads them from device memory (l3_set_sampling keeps the copy current)
+struct SampleParams {
+    float temperature;       // > 0 (0 = greedy: the runtime launches the argmax instead)
+    int32_t top_k;           // 0: off
+    float top_p;             // (0, 1]; 1: off
+    uint32_t seed_lo, seed_hi;
+};
+
+// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11): a
+// counter-based generator, so a draw is a pure function of (seed, row, position) and does not
+// depend on how often or in which order steps were launched (graph replay, run-ahead + undo)
+__host__ __device__ inline void philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {
+    uint32_t c0 = ctr[0], c1 = ctr[1], c2 = ctr[2], c3 = ctr[3], k0 = key[0], k1 = key[1];
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (uint32_t)p1;
+        c3 = (uint32_t)p0;
+        c0 = n0;
+        c2 = n2;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+// the 24 random bits of a sampling step: u = sample_bits24 * 2^-24 in [0, 1); key = the seed's
+// halves, counter = (row, pos, 0, 0)
+__host__ __device__ inline uint32_t sample_bits24(uint32_t seed_lo, uint32_t seed_hi, int32_t row, int32_t pos) {
+    const uint32_t ctr[4] = {(uint32_t)row, (uint32_t)pos, 0u, 0u}, key[2] = {seed_lo, seed_hi};
+    uint32_t x[4];
+    philox4x32_10(ctr, key, x);
+    return x[0] >> 8;
+}
+
 struct GemmArgs {
     const float* A; int64_t lda;   // A rows, row stride (floats)
     const float* W;                // [N, K] row-major
@@ -266,6 +301,40 @@ __device__ __forceinline__ void group_argmax(float& best, int& bi, int lane) {
     argmax_xor16_32<LANES >= 32, LANES >= 64>(best, bi, lane);
 }
 
+// End of a row's token choice (argmax_kernel, argmax_parts_kernel, sample_kernel), run by the one
+// thread that holds the row's id bi and its logit best: the id to out[blockIdx.x]; in a captured
+// decode step also the generate history and the position advance (last-arriving row)
+// hist_off 1: the step's lm_head has already moved the position on (GemmArgs::pos_adv), so the
+// id belongs at pos - 1 and the position stays
+__device__ __forceinline__ void decode_row_finish(float best, int bi, int32_t* __restrict__ out,
+                                                  DecState* __restrict__ st, int hist_off, int n_ids) {
+    if (n_ids > 0) L3_DCHECK(bi >= 0 && bi < n_ids, CHK_TOKEN_ID);
+    out[blockIdx.x] = bi;
+    if (st) {
+        // captured decode step: record the id in the generate history, and the last row
+        // to arrive moves the loop one position on (llama3.py:312-318).  Every block
+        // reads pos before its arrival (the fence orders the read and the history store
+        // before the atomic), so none sees the advanced value.
+        const int pos = st->pos - hist_off, q = pos - st->hist_base;
+        if (st->hist && q >= 0 && q < st->hist_cap) st->hist[(int64_t)q * gridDim.x + blockIdx.x] = bi;
+        if (st->hist_val && q >= 0 && q < st->hist_cap) st->hist_val[(int64_t)q * gridDim.x + blockIdx.x] = best;
+        if (hist_off) {
+            // the lm_head of this step already moved the position on
+        } else if (gridDim.x == 1) {
+            // one row (batch-1 decode): this thread is the only reader of pos in this
+            // launch, so it advances it directly — no agent-scope fence (≈1-3 µs of the
+            // step) and no arrival count
+            st->pos = pos + 1;
+        } else {
+            __threadfence();
+            if (atomicAdd(&st->arrive, 1u) == gridDim.x - 1) {
+                st->arrive = 0u;
+                st->pos = pos + 1;
+            }
+        }
+    }
+}
+
 // row r of A (identity, or the gathered embedding row)
 __device__ __forceinline__ const float* a_row(const GemmArgs& p, int64_t r) {
     return p.A + (p.a_rows ? (int64_t)p.a_rows[r] : r) * p.lda;
@@ -355,6 +424,11 @@ hipError_t launch_argmax(const float* logits, int64_t rows, int n, int32_t* out,
 // GemmArgs::amax_rows, a batch)
 hipError_t launch_argmax_parts(const ArgmaxPart* parts, int nparts, int32_t* out, hipStream_t s,
                                DecState* st = nullptr, int hist_off = 0, int rows = 1);
+// one token per row by temperature / top-k / top-p sampling (sample.hip; the rule: DESIGN.md
+// "Sampling"): prm in device memory; u_dev [rows] uniforms in [0, 1), or null: row r draws
+// Philox(seed, row0 + r, pos) with pos = st->pos in a captured decode step (st set)
+hipError_t launch_sample(const float* logits, int64_t rows, int n, int32_t* out, const SampleParams* prm,
+                         const float* u_dev, int row0, int pos, hipStream_t s, DecState* st = nullptr);
 // blocks of the one-row lm_head GEMV (= its partial count when amax_part is set), 0 otherwise
 int gemv_store_blocks(const GemmArgs& a);
 // true when launch_gemm runs this shape on the row-blocked GEMV (short M)
@@ -386,6 +460,7 @@ hipError_t launch_kv_restore(float* cache, const float* bak, int B, int KVH, int
 hipError_t dcheck_collect_gemm(unsigned* out);
 hipError_t dcheck_collect_attention(unsigned* out);
 hipError_t dcheck_collect_misc(unsigned* out);
+hipError_t dcheck_collect_sample(unsigned* out);
 hipError_t dcheck_collect_persist(unsigned* out);
 hipError_t launch_dcheck_selftest(hipStream_t s);
 hipError_t launch_rope(const float* x, float* y, const float* cos_t, const float* sin_t, int B,

@@ -23,11 +23,8 @@ __device__ __forceinline__ float wave_max(float v) {
 // its float4 loads in flight at once (8 per thread at the 32000-wide vocab), then a wavefront
 // butterfly and a 16-way LDS step — a decode step waits on one memory round trip, not on a
 // serial walk of the row.
-// block-wide finish of a row argmax (1024 threads, every thread's candidate in best / bi): the
-// id to out[blockIdx.x]; in a captured decode step also the generate history and the position
-// advance (last-arriving row)
-// hist_off 1: the step's lm_head has already moved the position on (GemmArgs::pos_adv), so the
-// id belongs at pos - 1 and the position stays
+// block-wide finish of a row argmax (1024 threads, every thread's candidate in best / bi), then
+// the row's end shared with the sampler (kernels.h decode_row_finish)
 __device__ __forceinline__ void argmax_finish(float best, int bi, int32_t* __restrict__ out,
                                               DecState* __restrict__ st, int hist_off = 0, int n_ids = 0) {
     constexpr int NT = 1024;
@@ -41,33 +38,7 @@ __device__ __forceinline__ void argmax_finish(float best, int bi, int32_t* __res
         best = tid < NT / 64 ? sv[tid] : -INFINITY;
         bi = tid < NT / 64 ? si[tid] : 0x7fffffff;
         group_argmax<16>(best, bi, tid);  // the NT / 64 = 16 wave results in lanes 0-15
-        if (tid == 0) {
-            if (n_ids > 0) L3_DCHECK(bi >= 0 && bi < n_ids, CHK_TOKEN_ID);
-            out[blockIdx.x] = bi;
-            if (st) {
-                // captured decode step: record the id in the generate history, and the last row
-                // to arrive moves the loop one position on (llama3.py:312-318).  Every block
-                // reads pos before its arrival (the fence orders the read and the history store
-                // before the atomic), so none sees the advanced value.
-                const int pos = st->pos - hist_off, q = pos - st->hist_base;
-                if (st->hist && q >= 0 && q < st->hist_cap) st->hist[(int64_t)q * gridDim.x + blockIdx.x] = bi;
-                if (st->hist_val && q >= 0 && q < st->hist_cap) st->hist_val[(int64_t)q * gridDim.x + blockIdx.x] = best;
-                if (hist_off) {
-                    // the lm_head of this step already moved the position on
-                } else if (gridDim.x == 1) {
-                    // one row (batch-1 decode): this thread is the only reader of pos in this
-                    // launch, so it advances it directly — no agent-scope fence (≈1-3 µs of the
-                    // step) and no arrival count
-                    st->pos = pos + 1;
-                } else {
-                    __threadfence();
-                    if (atomicAdd(&st->arrive, 1u) == gridDim.x - 1) {
-                        st->arrive = 0u;
-                        st->pos = pos + 1;
-                    }
-                }
-            }
-        }
+        if (tid == 0) decode_row_finish(best, bi, out, st, hist_off, n_ids);
     }
 }
 

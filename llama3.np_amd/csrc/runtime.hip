@@ -234,7 +234,14 @@ struct l3_ctx {
     int host_lag = 2;  // forward_dev: host-path lag of the later batch parts (layers; tools/host_path_probe.py)
     int64_t persist_recoveries = 0;  // steps recovered on the graph path (stats)
     hipEvent_t order_ev = nullptr;   // after this context's last decode graph (launch_decode_graph)
+    // sampling (l3_set_sampling; sample.hip): temperature 0 = greedy, every decode path as it was.
+    // While it is on, the step's argmax launch is the sample kernel, which needs whole logits rows:
+    // no persistent step, no argmax fold, no per-row argmax partials.
+    SampleParams samp{0.f, 0, 1.f, 0u, 0u};
+    SampleParams* samp_dev = nullptr;  // the kernel's copy (allocated by the first l3_set_sampling)
 };
+
+static bool sampling_on(const l3_ctx* c) { return c->samp.temperature > 0.f; }
 
 // ---------------------------------------------------------------------------------------
 // join = the context stream waits for an in-flight logits gather: every entry point except
@@ -492,7 +499,7 @@ extern "C" int l3_destroy(l3_ctx* c) {
     for (void* p : c->scratch) dfree(p);
     for (auto& t : c->timers) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
     drop_decode_graph(c);
-    dfree(c->dec_ids); dfree(c->dec_state); dfree(c->kv_bak);
+    dfree(c->dec_ids); dfree(c->dec_state); dfree(c->kv_bak); dfree(c->samp_dev);
     if (c->dec_host) (void)hipHostFree(c->dec_host);
     for (auto& q : c->spec_q) { (void)hipEventDestroy(q.ev0); (void)hipEventDestroy(q.ev1); (void)hipEventDestroy(q.ev); }
     for (hipEvent_t e : c->spec_free) (void)hipEventDestroy(e);
@@ -893,7 +900,7 @@ static bool lm_amax_on() {
 
 static int run_lm_head(l3_ctx* c, int B, int L, float* logits_dev, int b0, hipStream_t s) {
     GemmArgs lm = lm_head_args(c, B, L, logits_dev, b0);
-    c->amax_n = lm_amax_on() && b0 == 0 ? gemv_store_blocks(lm) : 0;
+    c->amax_n = lm_amax_on() && b0 == 0 && !sampling_on(c) ? gemv_store_blocks(lm) : 0;
     if (c->amax_n) lm.amax_part = c->amax_part;
     if (c->amax_n && c->fold_adv) lm.pos_adv = c->dec_state;
     // a captured batched decode step (ids only): argmax partials per row instead of the logits
@@ -904,8 +911,12 @@ static int run_lm_head(l3_ctx* c, int B, int L, float* logits_dev, int b0, hipSt
 }
 
 // greedy argmax of the rows the last forward left in c->logits (llama3.py:320): from the
-// lm_head's partials when it wrote them; hist_off 1 when that lm_head moved the position on
-static hipError_t launch_greedy_argmax(l3_ctx* c, int B, DecState* st, int hist_off = 0) {
+// lm_head's partials when it wrote them; hist_off 1 when that lm_head moved the position on.
+// With sampling on (l3_set_sampling) the sample kernel takes its place: row b draws with the
+// counter (b, pos), pos the position of the step's last token (st set: DecState.pos)
+static hipError_t launch_greedy_argmax(l3_ctx* c, int B, DecState* st, int hist_off = 0, int pos = 0) {
+    if (sampling_on(c))
+        return launch_sample(c->logits, B, c->d.vocab_size, c->dec_ids, c->samp_dev, nullptr, 0, pos, c->stream, st);
     if (c->amax_n && B == 1) return launch_argmax_parts(c->amax_part, c->amax_n, c->dec_ids, c->stream, st, hist_off);
     if (c->amax_rows_n) return launch_argmax_parts(c->amax_rows, c->amax_rows_n, c->dec_ids, c->stream, st, 0, B);
     return launch_argmax(c->logits, B, c->d.vocab_size, c->dec_ids, c->stream, st);
@@ -917,7 +928,7 @@ static hipError_t launch_greedy_argmax(l3_ctx* c, int B, DecState* st, int hist_
 // L3_DECODE_FOLD_ARGMAX=0: off (A/B)
 static int fold_parts(l3_ctx* c, int B) {
     static const bool on = env_knob("L3_DECODE_FOLD_ARGMAX", 1) != 0;
-    if (!on || B != 1 || !lm_amax_on() || !c->dec_state) return 0;
+    if (!on || B != 1 || !lm_amax_on() || !c->dec_state || sampling_on(c)) return 0;
     const int n = gemv_store_blocks(lm_head_args(c, 1, 1, c->logits, 0));
     GemmArgs qkv{};
     qkv.M = 1;
@@ -1137,7 +1148,7 @@ static DecodePersistArgs persist_shape(const l3_ctx* c) {
 // run on (e.g. a CPX partition's 32 CUs) captures the 25-kernel graph instead of failing
 static bool persist_wanted(l3_ctx* c, int B) {
     const int mode = env_knob("L3_DECODE_PERSIST", 1);
-    if (!mode || c->persist_off || B != 1 || c->layers.empty() || !c->dec_state) return false;
+    if (!mode || c->persist_off || B != 1 || c->layers.empty() || !c->dec_state || sampling_on(c)) return false;
     return decode_persist_grid(persist_shape(c)) > 0;
 }
 
@@ -1325,7 +1336,7 @@ static int capture_steps(l3_ctx* c, int B, int steps, hipGraph_t* graph, hipGrap
             c->fold_in = fold && i > 0;
             c->fold_adv = fold > 0;
             c->fold_n = fold;
-            c->rows_amax = rows_amax && B > 1;
+            c->rows_amax = rows_amax && B > 1 && !sampling_on(c);
             rc = forward_dev(c, c->dec_ids, B, 1, 0, c->logits, c->dec_pos);
             c->fold_in = c->fold_adv = false;
             c->rows_amax = false;
@@ -1525,6 +1536,54 @@ static int spec_resolve(l3_ctx* c) {
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------
+// sampling (sample.hip).  The arguments are checked before anything else, so a bad value is
+// reported whatever the context.
+static int check_sampling(const char* who, float T, int32_t top_k, float top_p) {
+    if (!(T >= 0.f) || std::isinf(T)) return fail("%s: temperature %g must be finite and >= 0", who, (double)T);
+    if (top_k < 0) return fail("%s: top_k %d must be >= 0", who, top_k);
+    if (!(top_p > 0.f && top_p <= 1.f)) return fail("%s: top_p %g must be in (0, 1]", who, (double)top_p);
+    return 0;
+}
+
+static int group_members(const l3_group* g);  // (below)
+
+extern "C" int l3_set_sampling(l3_ctx* c, float temperature, int32_t top_k, float top_p, uint64_t seed) {
+    if (check_sampling("l3_set_sampling", temperature, top_k, top_p)) return 1;
+    CHECK_CTX(c);
+    if (c->group && group_members(c->group) > 1)
+        return fail("l3_set_sampling: this context is a member of a multi-device l3_group (rows would need "
+                    "their global index; not supported)");
+    // the captured steps hold the launch they were captured with (argmax or sample, persistent or
+    // not): with the run-ahead undone and the stream idle they are dropped, and the next decode
+    // step runs eagerly and captures again
+    if (set_dev(c) || spec_resolve(c) || persist_settle(c)) return 1;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    drop_decode_graph(c);
+    c->persist_graph = false;
+    c->dec_pos_mirror = -1;
+    const SampleParams p{temperature, top_k, top_p, (uint32_t)seed, (uint32_t)(seed >> 32)};
+    if (!c->samp_dev) HIP_TRY(hipMalloc(&c->samp_dev, sizeof(SampleParams)));
+    HIP_TRY(hipMemcpy(c->samp_dev, &p, sizeof p, hipMemcpyHostToDevice));
+    c->samp = p;
+    return 0;
+}
+
+extern "C" int l3_get_sampling(l3_ctx* c, float* temperature, int32_t* top_k, float* top_p, uint64_t* seed) {
+    CHECK_CTX(c);
+    if (temperature) *temperature = c->samp.temperature;
+    if (top_k) *top_k = c->samp.top_k;
+    if (top_p) *top_p = c->samp.top_p;
+    if (seed) *seed = (uint64_t)c->samp.seed_hi << 32 | c->samp.seed_lo;
+    return 0;
+}
+
+extern "C" int l3_sample_uniform(uint64_t seed, int32_t row, int32_t pos, float* u) {
+    if (!u) return fail("l3_sample_uniform: null argument");
+    *u = (float)sample_bits24((uint32_t)seed, (uint32_t)(seed >> 32), row, pos) * 0x1p-24f;
+    return 0;
+}
+
 extern "C" int l3_greedy_step_host(l3_ctx* c, const int64_t* ids_host, int32_t B, int32_t L,
                                    int32_t start_pos, int64_t* next_ids_host, float* logits_host) {
     CHECK_CTX(c);
@@ -1599,7 +1658,7 @@ extern "C" int l3_greedy_step_host(l3_ctx* c, const int64_t* ids_host, int32_t B
     const double t_eager = now_us();
     if (upload_ids(c, ids_host, (int64_t)B * L)) return 1;
     if (forward_dev(c, c->ids, B, L, start_pos, c->logits)) return 1;
-    if (timed(c, L3_K_ARGMAX, [&] { return launch_greedy_argmax(c, B, nullptr); }))
+    if (timed(c, L3_K_ARGMAX, [&] { return launch_greedy_argmax(c, B, nullptr, 0, start_pos + L - 1); }))
         return 1;
     HIP_TRY(hipMemcpyAsync(c->dec_host, c->dec_ids, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream));
     if (logits_host)
@@ -1871,6 +1930,36 @@ extern "C" int l3_op_argmax_host(l3_ctx* c, const float* x, int64_t rows, int64_
     return 0;
 }
 
+extern "C" int l3_op_sample_host(l3_ctx* c, const float* logits, int64_t rows, int64_t n, float temperature,
+                                 int32_t top_k, float top_p, const float* u, uint64_t seed, int32_t row0,
+                                 int32_t pos, int32_t* out) {
+    if (check_sampling("l3_op_sample_host", temperature, top_k, top_p)) return 1;
+    if (rows <= 0 || rows > INT32_MAX || n <= 0 || n > INT32_MAX)
+        return fail("l3_op_sample_host: bad shape %lld x %lld", (long long)rows, (long long)n);
+    if (!logits || !out) return fail("l3_op_sample_host: null argument");
+    for (int64_t r = 0; u && r < rows; ++r)
+        if (!(u[r] >= 0.f && u[r] < 1.f)) return fail("l3_op_sample_host: u[%lld] = %g outside [0, 1)", (long long)r, (double)u[r]);
+    CHECK_CTX(c);
+    if (set_dev(c)) return 1;
+    Scratch S{c};
+    SCRATCH(dx, rows * n);
+    SCRATCH(di, rows);
+    SCRATCH(du, rows);
+    SCRATCH(dp, (int64_t)(sizeof(SampleParams) + 3) / 4);
+    const SampleParams p{temperature, top_k, top_p, (uint32_t)seed, (uint32_t)(seed >> 32)};
+    H2D(dx, logits, rows * n);
+    if (u) H2D(du, u, rows);
+    HIP_TRY(hipMemcpyAsync(dp, &p, sizeof p, hipMemcpyHostToDevice, c->stream));
+    if (temperature > 0.f)
+        HIP_TRY(launch_sample(dx, rows, (int)n, reinterpret_cast<int32_t*>(di), reinterpret_cast<SampleParams*>(dp),
+                              u ? du : nullptr, row0, pos, c->stream));
+    else  // temperature 0 is greedy
+        HIP_TRY(launch_argmax(dx, rows, (int)n, reinterpret_cast<int32_t*>(di), c->stream));
+    D2H(out, di, rows);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
 extern "C" int l3_op_silu_host(l3_ctx* c, const float* x, int64_t n, float* y) {
     CHECK_CTX(c);
     if (set_dev(c)) return 1;
@@ -2037,7 +2126,7 @@ extern "C" int l3_set_decode_horizon(l3_ctx* c, int32_t end_pos) {
 
 extern "C" int l3_decode_persistent(l3_ctx* c, int32_t* active) {
     CHECK_CTX(c);
-    if (active) *active = c->dec_exec && c->persist_graph ? 1 : 0;
+    if (active) *active = c->dec_exec && c->persist_graph && !sampling_on(c) ? 1 : 0;
     return 0;
 }
 
@@ -2059,6 +2148,7 @@ extern "C" int l3_device_check_counts(l3_ctx* c, uint32_t* counts, int32_t* enab
     HIP_TRY(dcheck_collect_gemm(n));
     HIP_TRY(dcheck_collect_attention(n));
     HIP_TRY(dcheck_collect_misc(n));
+    HIP_TRY(dcheck_collect_sample(n));
     HIP_TRY(dcheck_collect_persist(n));
     for (int i = 0; i < CHK_N; ++i) counts[i] = n[i];
     return 0;
@@ -2363,6 +2453,7 @@ struct l3_group {
     std::vector<int64_t> tmp;        // host: one member's ids rows
 };
 
+static int group_members(const l3_group* g) { return g->n; }
 static int group_rows(const l3_group* g, int B, int i) { return B > i ? (B - i + g->n - 1) / g->n : 0; }
 
 static int group_busids(l3_group* g, char* busids, int64_t cap) {

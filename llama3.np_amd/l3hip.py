@@ -67,6 +67,10 @@ _SIGNATURES = {
     "l3_attention_forward_host": (ctypes.c_int, [_P, _I32, _P, _I32, _I32, _I32, _P]),
     "l3_op_softmax_host": (ctypes.c_int, [_P, _P, _I64, _I64, _P]),
     "l3_op_argmax_host": (ctypes.c_int, [_P, _P, _I64, _I64, _P]),
+    "l3_op_sample_host": (ctypes.c_int, [_P, _P, _I64, _I64, _F, _I32, _F, _P, ctypes.c_uint64, _I32, _I32, _P]),
+    "l3_set_sampling": (ctypes.c_int, [_P, _F, _I32, _F, ctypes.c_uint64]),
+    "l3_get_sampling": (ctypes.c_int, [_P, _P, _P, _P, _P]),
+    "l3_sample_uniform": (ctypes.c_int, [ctypes.c_uint64, _I32, _I32, _P]),
     "l3_op_silu_host": (ctypes.c_int, [_P, _P, _I64, _P]),
     "l3_op_rmsnorm_host": (ctypes.c_int, [_P, _P, _P, _I64, _I64, _F, _P]),
     "l3_op_rope_host": (ctypes.c_int, [_P, _P, _I32, _I32, _I32, _I32, _P, _P, _P]),
@@ -239,6 +243,14 @@ class PinnedPool:
 pinned = PinnedPool()
 
 
+def sample_uniform(seed: int, row: int, pos: int) -> float:
+    """The uniform in [0, 1) a sampling step draws for (seed, batch row, position): Philox4x32-10,
+    (x0 >> 8) * 2^-24 (l3_sample_uniform; host only, no device)."""
+    u = ctypes.c_float(0.0)
+    check(lib().l3_sample_uniform(int(seed) & (2 ** 64 - 1), int(row), int(pos), ctypes.byref(u)))
+    return float(u.value)
+
+
 def device_count() -> int:
     n = ctypes.c_int32(0)
     check(lib().l3_device_count(ctypes.byref(n)))
@@ -307,9 +319,22 @@ class Context:
                                         ptr(logits) if logits is not None else None))
         return nxt, logits
 
+    def set_sampling(self, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0) -> None:
+        """Temperature / top-k / top-p sampling for ``greedy_step`` / ``greedy_generate``
+        (l3_set_sampling); temperature 0 restores greedy decoding.  Each token's uniform is a
+        function of (seed, batch row, position), so one seed gives one sequence on every path."""
+        check(lib().l3_set_sampling(self._h, float(temperature), int(top_k), float(top_p),
+                                    int(seed) & (2 ** 64 - 1)))
+
+    def get_sampling(self) -> dict:
+        t, k, p, s = ctypes.c_float(0), ctypes.c_int32(0), ctypes.c_float(0), ctypes.c_uint64(0)
+        check(lib().l3_get_sampling(self._h, ctypes.byref(t), ctypes.byref(k), ctypes.byref(p), ctypes.byref(s)))
+        return {"temperature": t.value, "top_k": k.value, "top_p": p.value, "seed": s.value}
+
     def greedy_generate(self, ids: np.ndarray, max_new_tokens: int, values: bool = False):
         """The device-side greedy loop: ids [B, max_new_tokens - L]; with ``values`` also each
-        step's winning logit (fp32, same shape) — the value the step's argmax picked."""
+        step's winning logit (fp32, same shape) — the value the step's argmax picked.  With
+        sampling on (``set_sampling``) the ids are sampled and the value is the picked token's."""
         ids = np.ascontiguousarray(ids, dtype=np.int64)
         B, L = ids.shape
         out = np.empty((B, max(0, max_new_tokens - L)), np.int64)
@@ -489,6 +514,24 @@ class Context:
         n = x.shape[-1]
         out = np.empty(x.shape[:-1], np.int32)
         check(lib().l3_op_argmax_host(self._h, ptr(x), x.size // n, n, ptr(out)))
+        return out
+
+    def op_sample(self, logits: np.ndarray, temperature: float, top_k: int = 0, top_p: float = 1.0,
+                  u: Optional[np.ndarray] = None, seed: int = 0, row0: int = 0, pos: int = 0) -> np.ndarray:
+        """One sampled id per row of ``logits`` (last axis) by the rule of ``set_sampling``; int32
+        of logits.shape[:-1].  ``u``: one uniform in [0, 1) per row; None: row r draws
+        ``sample_uniform(seed, row0 + r, pos)`` on the device."""
+        x = np.ascontiguousarray(logits, dtype=np.float32)
+        n = x.shape[-1]
+        rows = x.size // n
+        out = np.empty(x.shape[:-1], np.int32)
+        if u is not None:
+            u = np.ascontiguousarray(u, dtype=np.float32)
+            if u.size != rows:
+                raise ValueError(f"u has {u.size} entries for {rows} rows")
+        check(lib().l3_op_sample_host(self._h, ptr(x), rows, n, float(temperature), int(top_k), float(top_p),
+                                      ptr(u) if u is not None else None, int(seed) & (2 ** 64 - 1),
+                                      int(row0), int(pos), ptr(out)))
         return out
 
     def op_silu(self, x: np.ndarray) -> np.ndarray:

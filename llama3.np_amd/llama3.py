@@ -352,12 +352,27 @@ class Llama:
         logits = self._target.forward(ids, int(start_pos))
         return logits[:, None, :]
 
+    def set_sampling(self, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0,
+                     seed: int = 0) -> None:
+        """Extension: after this, ``generate`` and ``generate_all`` pick each token by
+        temperature / top-k / top-p sampling on the device instead of argmax (the rule:
+        DESIGN.md "Sampling"); ``temperature=0`` (the default state) is greedy decoding.  A
+        token's random number depends only on (seed, batch row, position), so one seed gives the
+        same tokens from ``generate``, from ``generate_all`` and from a generator that was
+        abandoned and started again.  Not for a model on more than one device."""
+        if self._group is not None and self._group.n > 1:
+            raise NotImplementedError("sampling on a multi-device model: rows would need their global "
+                                      "index on every member")
+        self._ctx.set_sampling(temperature, top_k, top_p, seed)
+
     def generate(self, input_ids, max_new_tokens: int) -> Iterator[np.ndarray]:
         """Greedy decode with the reference's exact position schedule
         (llama3.py:310-321): prefill at 0, then decode step i >= 1 at pos = L + i,
         so KV slot L is never written and stays zero (the "decode hole").  Lazy as the
         reference's: the device may run up to 16 steps ahead of the consumer (never past
-        max_new_tokens), and a schedule left early is undone before any later call."""
+        max_new_tokens), and a schedule left early is undone before any later call.
+        After ``set_sampling`` with a temperature above 0 the tokens are sampled, not the
+        argmax; the schedule, the laziness and the run-ahead are the same."""
         ids = np.asarray(input_ids)
         _, L = ids.shape
         self._target.set_decode_horizon(max_new_tokens)
@@ -377,7 +392,8 @@ class Llama:
         ``[B, max_new_tokens - L]``.  Unlike ``generate`` it is not lazy: every step
         runs, so use it when the caller consumes all tokens.  On a multi-device model a batch of
         more than one row steps through ``Group.greedy_step`` (each device its rows, the ids
-        gathered) instead of the single-device graph loop."""
+        gathered) instead of the single-device graph loop.  After ``set_sampling`` the ids are
+        the sampled ones, identical to ``generate``'s for the same seed."""
         ids = np.asarray(input_ids)
         if self._group is None or self._group.n == 1 or ids.shape[0] == 1:
             return self._ctx.greedy_generate(ids, max_new_tokens)
