@@ -136,6 +136,32 @@ int l3_set_gemm_x6(l3_ctx* ctx, int32_t on);
 /* Same with device-resident ids (int32 [B, L]) and logits ([B, VS]); async. */
 int l3_forward_dev(l3_ctx* ctx, const int32_t* ids_dev, int32_t B, int32_t L,
                    int32_t start_pos, float* logits_dev);
+/* Teacher-forced scoring (extension of Llama.__call__, llama3.py:285-308, which keeps the last
+ * position's logits only; DESIGN.md "Scoring"): one forward over ids [B, L] int64 (host) that
+ * scores every position against targets [B, L] int64 (host) without materialising the logits.
+ * For a row's fp32 logits z[0..VS) — final RMSNorm and lm_head as l3_forward_host computes them —
+ * and its target t:
+ *   lse = m + log sum_i exp(z_i - m), m = max z (a -inf logit adds 0);
+ *   logprobs_host[row] = z_t - lse; t = -1 means "no target" and gives 0.0;
+ *   a row whose maximum is NaN or +inf, or whose logits are all -inf, gives NaN;
+ *   argmax_host[row] (int32 [B, L]; may be NULL) = the greedy id by l3_op_argmax_host's rule (the
+ *   first NaN, else the first maximum), also for such rows.
+ * Any other target outside [0, VS) is an error, reported before anything is launched.  The call
+ * is a forward in every other respect: it writes K / V slots [start_pos, start_pos + L) as
+ * l3_forward_host does (a long text can be scored in pieces; a decode step can follow), every
+ * block runs on every row whatever l3_set_last_layer_rows says (the setting is left as it is),
+ * and l3_set_gemm_x6 applies to the layers.  The lm_head runs in row chunks (whole multiples of
+ * 256 rows) against a bounded workspace of per-tile partials; the results do not depend on the
+ * chunking, bit for bit.  Its launches count under L3_K_LMHEAD, the combine under L3_K_ARGMAX.
+ * A context that is a member of a multi-device l3_group is refused. */
+int l3_score_host(l3_ctx* ctx, const int64_t* ids_host, const int64_t* targets_host, int32_t B, int32_t L,
+                  int32_t start_pos, float* logprobs_host, int32_t* argmax_host);
+/* Size of the scoring workspace (llama3.py:285-308 has no counterpart: the reference materialises
+ * its logits): 16 bytes per row and 64-column tile of the vocabulary, default 64 MiB, allocated
+ * by the first scoring call and freed with the context.  0 restores the default; fewer bytes than
+ * one 256-row chunk of the context's vocabulary is an error (and a scoring call whose own N needs
+ * more per chunk than the workspace holds fails the same way). */
+int l3_set_score_workspace(l3_ctx* ctx, int64_t bytes);
 /* Sampling (extension; the reference decodes greedily).  With temperature > 0 every l3_greedy_*
  * entry point below picks its tokens by temperature / top-k / top-p sampling on the device
  * instead of argmax; temperature 0 (the default) restores greedy decoding, unchanged.
@@ -223,6 +249,14 @@ int l3_op_ffn_host(l3_ctx* ctx, const float* x, int64_t rows, int32_t dim, int32
 /* y [rows, N] = x [rows, K] @ W[N, K]^T (the reference's `x @ W.T`). */
 int l3_op_linear_host(l3_ctx* ctx, const float* x, int64_t rows, int32_t K, int32_t N,
                       const float* w, float* y);
+/* The scoring path of l3_score_host (llama3.py:285-308 with the logits reduced in the lm_head's
+ * epilogue) on a plain product: for z = x [rows, K] @ W[N, K]^T (no norm) and targets int32 [rows]
+ * (-1: no target; else in [0, N)), logprob [rows], and optionally lse [rows] and argmax int32
+ * [rows] (NULL: not wanted).  Same kernels, same row chunks, any shape with K % 32 == 0 and
+ * N % 4 == 0. */
+int l3_op_linear_logprob_host(l3_ctx* ctx, const float* x, int64_t rows, int32_t K, int32_t N,
+                              const float* w, const int32_t* targets, float* logprob, float* lse,
+                              int32_t* argmax);
 
 /* ---- pinned host memory (fast host-buffer path) ------------------------------ */
 /* Page-locked host allocation: l3_forward_host / l3_greedy_step_host / l3_d2h copying into

@@ -220,6 +220,7 @@ bool gemm_is_gemv(const GemmArgs& a) {
 // ids compare rounding: 3 and 4 (128 x 128 vs 256 x 64 tiles) visit K in the same order per
 // element (BK 16, one MFMA chain per accumulator), so they round identically
 int gemm_store_config(const GemmArgs& a) {
+    if (a.force_tiled) return a.force_tiled;
     if (gemm_is_gemv(a)) return 0;
     return a.M <= 32 ? 1 : a.M <= 64 ? 2 : 3;
 }
@@ -244,6 +245,13 @@ hipError_t launch_gemm(int epi, const GemmArgs& a, hipStream_t s) {
     // amax_rows: the tiled EPI_STORE kernels only (16 * TN = 64-column wave tiles, no split-K)
     if (a.amax_rows && (epi != EPI_STORE || gemm_store_config(a) == 0 || a.ws || a.amax_nct != (a.N + 63) / 64))
         return hipErrorInvalidValue;
+    // lse_rows: the same kernels and guards (the GEMV and the skinny kernel have no such epilogue)
+    if (a.lse_rows && (epi != EPI_STORE || gemm_store_config(a) == 0 || a.ws || a.force_skinny || a.amax_rows ||
+                       a.lse_nct != (a.N + 63) / 64 || !a.lse_targets || !a.lse_tgt))
+        return hipErrorInvalidValue;
+    if (a.force_tiled && (epi != EPI_STORE || a.force_tiled < 1 || a.force_tiled > 3 || a.force_skinny || a.parts ||
+                          a.amax_part || a.amax_in))
+        return hipErrorInvalidValue;
     if (a.pos_adv && !a.amax_part) return hipErrorInvalidValue;
     if (a.amax_in) {  // layer-0 QKV of a captured batch-1 decode step with the previous argmax folded in
         if (epi != EPI_QKV || a.M != 1 || !gemv_direct(a) || a.col_base || a.a_rows || a.amax_in_n < 1 ||
@@ -255,7 +263,7 @@ hipError_t launch_gemm(int epi, const GemmArgs& a, hipStream_t s) {
             default: return launch_gemv_lpu<EPI_QKV, 1, 64, false, false, true>(a, s);
         }
     }
-    if (a.force_skinny || (gemm_is_gemv(a) && use_skinny(a))) {
+    if (a.force_skinny || (!a.force_tiled && gemm_is_gemv(a) && use_skinny(a))) {
         switch (epi) {
             case EPI_SWIGLU: return launch_skinny<EPI_SWIGLU, 2>(a, s);
             case EPI_QKV: return a.M > skinny_tn2() ? launch_skinny<EPI_QKV, 2>(a, s) : launch_skinny<EPI_QKV, 1>(a, s);
@@ -264,7 +272,7 @@ hipError_t launch_gemm(int epi, const GemmArgs& a, hipStream_t s) {
             default: return hipErrorInvalidValue;
         }
     }
-    if (gemm_is_gemv(a)) {
+    if (!a.force_tiled && gemm_is_gemv(a)) {
         // GemmArgs::col_base (a K / V-only QKV) is honoured by the skinny and tiled epilogues
         // only: the GEMV would write the K / V columns as q
         if (a.col_base) return hipErrorInvalidValue;
@@ -341,7 +349,7 @@ hipError_t launch_gemm(int epi, const GemmArgs& a, hipStream_t s) {
                     // 129-256 rows: one 256-row panel per column tile, so the weight streams from
                     // HBM once per launch (two 128-row tiles read it twice: 1.54x the algorithmic
                     // bytes at B = 256, profiles/pmc_gateup.json r01)
-                    if (a.M > 128 && a.M <= 256) return launch<EPI_STORE, 4, 1, 4, 4, 2, 16, 3>(a, s);
+                    if (a.M > 128 && a.M <= 256 && !a.force_tiled) return launch<EPI_STORE, 4, 1, 4, 4, 2, 16, 3>(a, s);
                     return launch<EPI_STORE, 2, 2, 4, 4, 2, 16, 4>(a, s);
             }
         default:

@@ -274,6 +274,45 @@ __device__ __forceinline__ void direct_epilogue(const GemmArgs& p, const f32x4 (
             }
             return;
         }
+        if (p.lse_rows) {
+            // scoring partials instead of the logits (DESIGN.md "Scoring"): per row, this wave's
+            // 16 * TN columns reduced to (m, s, idx) — m the maximum over the valid columns by the
+            // argmax rule above (so a NaN column makes it NaN), s = sum of exp(v - m) over the same
+            // columns as exp2 of a log2(e)-prescaled difference, idx the first index of m.  A tile
+            // of -inf only subtracts 0 instead of m, so its s is 0 and not (-inf) - (-inf) = NaN
+            if (ncol0 >= p.N) return;  // a wave wholly past the last column owns no record
+#pragma unroll
+            for (int i = 0; i < TM; ++i) {
+                const int row = mrow0 + i * 16 + frow;
+                const int tgt = p.lse_targets[min(row, p.M - 1)];
+                float best = -INFINITY;
+                int bi = 0x7fffffff;
+                float v[4 * TN];
+#pragma unroll
+                for (int j = 0; j < TN; ++j)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int col = ncol0 + j * 16 + fq4 + r;
+                        const float x = acc[i][j][r] * rs[i];
+                        v[4 * j + r] = col < p.N ? x : -INFINITY;  // a padded column adds exp(-inf) = 0
+                        const bool vn = x != x, bn = best != best;
+                        const bool take = col < p.N && (bi == 0x7fffffff || x > best || (vn && !bn));
+                        best = take ? x : best;
+                        bi = take ? col : bi;
+                        // one lane of the launch holds column tgt of this row: a plain store
+                        if (col == tgt && col < p.N && row < p.M) p.lse_tgt[row] = x;
+                    }
+                argmax_xor16_32<true, true>(best, bi, lane);
+                const float sub = best == -INFINITY ? 0.f : best;
+                float s = 0.f;
+#pragma unroll
+                for (int k = 0; k < 4 * TN; ++k) s += __builtin_amdgcn_exp2f((v[k] - sub) * 1.4426950408889634f);
+                s = sum_xor16_32(s);
+                if (lane < 16 && row < p.M)
+                    p.lse_rows[(int64_t)row * p.lse_nct + ncol0 / (16 * TN)] = LsePart{best, s, bi, 0};
+            }
+            return;
+        }
     }
 #pragma unroll
     for (int i = 0; i < TM; ++i) {

@@ -67,6 +67,16 @@ struct ArgmaxPart {
     int i;
 };
 
+// Teacher-forced scoring (DESIGN.md "Scoring"): what one wave leaves of a row's 64-column tile of
+// the lm_head — the tile's maximum over its valid columns (the first NaN if any), the sum of
+// exp(v - m) over the same columns (0 when every column is -inf) and the first index of m
+struct alignas(16) LsePart {
+    float m;
+    float s;
+    int idx;
+    int pad;
+};
+
 // Device-resident state of the greedy decode loop (graph replay).  pos is first, so &st->pos
 // is the pos_dev the captured kernels read.
 struct DecState {
@@ -162,6 +172,12 @@ struct GemmArgs {
     // logits, each wave's (value, index) argmax over its 64 columns of every row ->
     // amax_rows[row][column tile], amax_nct tiles per row (C is not written)
     ArgmaxPart* amax_rows; int amax_nct;
+    // EPI_STORE on the tiled kernel (teacher-forced scoring): instead of the logits, each wave's
+    // (max, sum of exp, argmax) record over its 64 columns of every row -> lse_rows[row][column
+    // tile], lse_nct tiles per row; the lane that holds column lse_targets[row] also stores that
+    // logit to lse_tgt[row] (a target outside [0, N): nothing is stored).  C is not written.
+    LsePart* lse_rows; int lse_nct;
+    const int32_t* lse_targets; float* lse_tgt;
     DecState* pos_adv;             // ... and block 0 moves the decode position on (a captured step
                                    // whose argmax the next step's layer-0 QKV folds in)
     // EPI_QKV on the one-row GEMV (a captured batch-1 decode step after the first of a graph): the
@@ -179,6 +195,10 @@ struct GemmArgs {
     // the skinny MFMA kernel whatever M and W (a pruned last layer: every row rounds the same
     // way for any batch split, runtime.hip run_layer last_rows)
     bool force_skinny;
+    // EPI_STORE: that gemm_store_config id (1..3) on the tiled kernels whatever M, N and K (0: by
+    // shape) — scoring keeps one configuration for every row chunk of a call, so a row rounds the
+    // same way wherever the chunk boundaries fall; 3 is always the 128 x 128 tile
+    int force_tiled;
     // tiled kernel: tile order within each XCD's run of tiles — 0 row-major (n fastest), g > 0
     // groups of g row tiles walked column by column, so a k-step's concurrent blocks share g A
     // slices and ~blocks / g W slices in L2 (set by launch_gemm for long K; results identical)
@@ -439,6 +459,10 @@ bool gemv_direct(const GemmArgs& a);
 // which EPI_STORE kernel launch_gemm picks (0 = GEMV): launches of equal id round identically
 // row by row, whatever their M
 int gemm_store_config(const GemmArgs& a);
+// scoring: row r's log-probability of targets[r] from the lm_head's partials (GemmArgs::lse_rows)
+// and target logits; a target < 0 scores 0.  lse / argmax optional (null)
+hipError_t launch_score_combine(const LsePart* parts, int nparts, const float* tgt_logit, const int32_t* targets,
+                                int64_t rows, int n, float* logprob, float* lse, int32_t* argmax, hipStream_t s);
 hipError_t launch_softmax(const float* x, float* y, int64_t rows, int n, hipStream_t s);
 hipError_t launch_silu(const float* x, float* y, int64_t n, hipStream_t s);
 hipError_t launch_rmsnorm(const float* x, const float* w, float* y, int64_t rows, int dim,
@@ -461,6 +485,7 @@ hipError_t dcheck_collect_gemm(unsigned* out);
 hipError_t dcheck_collect_attention(unsigned* out);
 hipError_t dcheck_collect_misc(unsigned* out);
 hipError_t dcheck_collect_sample(unsigned* out);
+hipError_t dcheck_collect_score(unsigned* out);
 hipError_t dcheck_collect_persist(unsigned* out);
 hipError_t launch_dcheck_selftest(hipStream_t s);
 hipError_t launch_rope(const float* x, float* y, const float* cos_t, const float* sin_t, int B,

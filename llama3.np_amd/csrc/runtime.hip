@@ -239,6 +239,16 @@ struct l3_ctx {
     // no persistent step, no argmax fold, no per-row argmax partials.
     SampleParams samp{0.f, 0, 1.f, 0u, 0u};
     SampleParams* samp_dev = nullptr;  // the kernel's copy (allocated by the first l3_set_sampling)
+    // teacher-forced scoring (l3_score_host, l3_op_linear_logprob_host): the lm_head's partials of
+    // one row chunk [chunk rows][ceil(N / 64)] live in score_ws (allocated on first use, bounded:
+    // l3_set_score_workspace), the per-row targets / target logits / results in score_rows
+    static constexpr int64_t SCORE_WS_DEFAULT = (int64_t)64 << 20;
+    int64_t score_ws_bytes = SCORE_WS_DEFAULT;  // the size asked for
+    void* score_ws = nullptr;
+    int64_t score_ws_have = 0;                  // bytes allocated (0: none yet)
+    int32_t* score_rows = nullptr;              // [5][score_rows_cap]: targets, target logit, logprob, lse, argmax
+    int64_t score_rows_cap = 0;
+    std::vector<int32_t> score_tgt_host;        // int32 staging of the int64 host targets
 };
 
 static bool sampling_on(const l3_ctx* c) { return c->samp.temperature > 0.f; }
@@ -500,6 +510,7 @@ extern "C" int l3_destroy(l3_ctx* c) {
     for (auto& t : c->timers) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
     drop_decode_graph(c);
     dfree(c->dec_ids); dfree(c->dec_state); dfree(c->kv_bak); dfree(c->samp_dev);
+    dfree(c->score_ws); dfree(c->score_rows);
     if (c->dec_host) (void)hipHostFree(c->dec_host);
     for (auto& q : c->spec_q) { (void)hipEventDestroy(q.ev0); (void)hipEventDestroy(q.ev1); (void)hipEventDestroy(q.ev); }
     for (hipEvent_t e : c->spec_free) (void)hipEventDestroy(e);
@@ -2060,6 +2071,144 @@ extern "C" int l3_op_ffn_host(l3_ctx* c, const float* x, int64_t rows, int32_t d
 }
 
 // ---------------------------------------------------------------------------------------
+// Teacher-forced scoring (extension of Llama.__call__, llama3.py:285-308; DESIGN.md "Scoring"):
+// the lm_head over every row with the lse_rows epilogue, in row chunks against the bounded
+// partials workspace, each chunk followed by the combine kernel.
+static int64_t score_row_bytes(int64_t N) { return ((N + 63) / 64) * (int64_t)sizeof(LsePart); }
+
+// device arrays of `rows` entries each: targets (int32), target logit, logprob, lse, argmax
+static int score_row_bufs(l3_ctx* c, int64_t rows) {
+    if (rows <= c->score_rows_cap) return 0;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    dfree(c->score_rows);
+    c->score_rows = nullptr;
+    c->score_rows_cap = 0;
+    HIP_TRY(hipMalloc(&c->score_rows, (size_t)rows * 5 * 4));
+    c->score_rows_cap = rows;
+    return 0;
+}
+
+// A [rows, K] (row stride lda) against W [N, K]: logprob / lse / argmax of rows (device, the last
+// two optional).  The kernel configuration comes from the call's row count and holds for every
+// chunk, so a row's bits do not depend on the workspace size.
+static int score_lm(l3_ctx* c, const float* A, int64_t lda, int64_t rows, int K, int N, const float* W, bool norm,
+                    const int32_t* targets_dev, float* tgt_logit_dev, float* logprob_dev, float* lse_dev,
+                    int32_t* argmax_dev) {
+    const int64_t row_bytes = score_row_bytes(N);
+    const int64_t chunk = c->score_ws_bytes / row_bytes / 256 * 256;
+    if (chunk < 256)
+        return fail("scoring: the %lld-byte workspace holds fewer than 256 rows of %lld bytes (N = %d); "
+                    "l3_set_score_workspace", (long long)c->score_ws_bytes, (long long)row_bytes, N);
+    if (c->score_ws_have != c->score_ws_bytes) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        dfree(c->score_ws);
+        c->score_ws = nullptr;
+        c->score_ws_have = 0;
+        HIP_TRY(hipMalloc(&c->score_ws, (size_t)c->score_ws_bytes));
+        c->score_ws_have = c->score_ws_bytes;
+    }
+    GemmArgs g{};
+    g.lda = lda; g.W = W; g.N = N; g.K = K; g.norm = norm; g.eps = c->d.norm_eps;
+    g.C = nullptr; g.ldc = N;
+    g.force_tiled = rows <= 32 ? 1 : rows <= 64 ? 2 : 3;
+    g.lse_rows = static_cast<LsePart*>(c->score_ws); g.lse_nct = (N + 63) / 64;
+    for (int64_t r0 = 0; r0 < rows; r0 += chunk) {
+        const int64_t m = rows - r0 < chunk ? rows - r0 : chunk;
+        g.A = A + r0 * lda; g.M = (int)m;
+        g.lse_targets = targets_dev + r0; g.lse_tgt = tgt_logit_dev + r0;
+        if (timed(c, L3_K_LMHEAD, [&] { return launch_gemm(EPI_STORE, g, c->stream); })) return 1;
+        if (timed(c, L3_K_ARGMAX, [&] {
+                return launch_score_combine(g.lse_rows, g.lse_nct, g.lse_tgt, g.lse_targets, m, N, logprob_dev + r0,
+                                            lse_dev ? lse_dev + r0 : nullptr, argmax_dev ? argmax_dev + r0 : nullptr,
+                                            c->stream);
+            }))
+            return 1;
+    }
+    return 0;
+}
+
+extern "C" int l3_set_score_workspace(l3_ctx* c, int64_t bytes) {
+    CHECK_CTX(c);
+    if (bytes < 0) return fail("l3_set_score_workspace: %lld bytes", (long long)bytes);
+    if (bytes == 0) bytes = l3_ctx::SCORE_WS_DEFAULT;
+    const int64_t least = 256 * score_row_bytes(c->d.vocab_size);
+    if (bytes < least)
+        return fail("l3_set_score_workspace: %lld bytes hold fewer than one 256-row chunk of the vocabulary's "
+                    "partials (%lld bytes)", (long long)bytes, (long long)least);
+    c->score_ws_bytes = bytes;  // reallocated by the next scoring call
+    return 0;
+}
+
+// targets [T]: -1 (no target) or a column of [0, N); checked before any launch
+template <typename Tgt>
+static int check_targets(const char* who, const Tgt* t, int64_t T, int64_t N) {
+    for (int64_t i = 0; i < T; ++i)
+        if (t[i] < -1 || t[i] >= N)
+            return fail("%s: target %lld at %lld outside [0, %lld) (-1: no target)", who, (long long)t[i],
+                        (long long)i, (long long)N);
+    return 0;
+}
+
+extern "C" int l3_score_host(l3_ctx* c, const int64_t* ids_host, const int64_t* targets_host, int32_t B, int32_t L,
+                             int32_t start_pos, float* logprobs_host, int32_t* argmax_host) {
+    CHECK_CTX(c);
+    if (need_model(c) || check_call(c, B, L, start_pos)) return 1;
+    if (!ids_host || !targets_host || !logprobs_host) return fail("l3_score_host: null argument");
+    if (c->group && group_members(c->group) > 1)
+        return fail("l3_score_host: this context is a member of a multi-device l3_group (not supported)");
+    const int64_t T = (int64_t)B * L;
+    if (check_targets("l3_score_host", targets_host, T, c->d.vocab_size)) return 1;
+    if (set_dev(c) || spec_resolve(c) || ensure_ws(c, B, L) || score_row_bufs(c, T)) return 1;
+    if (upload_ids(c, ids_host, T)) return 1;
+    c->score_tgt_host.resize((size_t)T);
+    for (int64_t i = 0; i < T; ++i) c->score_tgt_host[(size_t)i] = (int32_t)targets_host[i];
+    int32_t* tgt = c->score_rows;
+    float* tl = reinterpret_cast<float*>(c->score_rows + T);
+    float* lp = reinterpret_cast<float*>(c->score_rows + 2 * T);
+    int32_t* am = argmax_host ? c->score_rows + 4 * T : nullptr;
+    HIP_TRY(hipMemcpyAsync(tgt, c->score_tgt_host.data(), (size_t)T * 4, hipMemcpyHostToDevice, c->stream));
+    // every layer on every row (the last block too, whatever l3_set_last_layer_rows says): the
+    // K / V slots [start_pos, start_pos + L) are written as a forward writes them
+    const int nl = (int)c->layers.size();
+    for (int li = 0; li < nl; ++li)
+        if (run_layer(c, li, B, L, start_pos, nullptr, li == 0 ? c->ids : nullptr)) return 1;
+    if (score_lm(c, c->h, c->d.dim, T, c->d.dim, c->d.vocab_size, c->lm_head, true, tgt, tl, lp, nullptr, am))
+        return 1;
+    HIP_TRY(hipMemcpyAsync(logprobs_host, lp, (size_t)T * 4, hipMemcpyDeviceToHost, c->stream));
+    if (am) HIP_TRY(hipMemcpyAsync(argmax_host, am, (size_t)T * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+extern "C" int l3_op_linear_logprob_host(l3_ctx* c, const float* x, int64_t rows, int32_t K, int32_t N,
+                                         const float* w, const int32_t* targets, float* logprob, float* lse,
+                                         int32_t* argmax) {
+    CHECK_CTX(c);
+    if (rows <= 0 || rows > INT32_MAX || N <= 0 || K <= 0)
+        return fail("l3_op_linear_logprob: bad shape %lld x %d x %d", (long long)rows, K, N);
+    if (K % 32) return fail("l3_op_linear_logprob: K=%d must be a multiple of 32", K);
+    if (N % 4) return fail("l3_op_linear_logprob: N=%d must be a multiple of 4", N);
+    if (!x || !w || !targets || !logprob) return fail("l3_op_linear_logprob: null argument");
+    if (check_targets("l3_op_linear_logprob", targets, rows, N)) return 1;
+    if (set_dev(c)) return 1;
+    Scratch S{c};
+    SCRATCH(dx, rows * K);
+    SCRATCH(dw, (int64_t)N * K);
+    SCRATCH(dr, rows * 5);
+    H2D(dx, x, rows * K);
+    H2D(dw, w, (int64_t)N * K);
+    H2D(dr, targets, rows);
+    if (score_lm(c, dx, K, rows, K, N, dw, false, reinterpret_cast<int32_t*>(dr), dr + rows, dr + 2 * rows,
+                 lse ? dr + 3 * rows : nullptr, argmax ? reinterpret_cast<int32_t*>(dr + 4 * rows) : nullptr))
+        return 1;
+    D2H(logprob, dr + 2 * rows, rows);
+    if (lse) D2H(lse, dr + 3 * rows, rows);
+    if (argmax) D2H(argmax, dr + 4 * rows, rows);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------
 // pinned (page-locked) host memory: the copies of l3_forward_host / l3_d2h into it run as
 // DMA at PCIe rate instead of through a pageable bounce (l3hip hands such buffers out as the
 // NumPy arrays Llama.__call__ returns)
@@ -2149,6 +2298,7 @@ extern "C" int l3_device_check_counts(l3_ctx* c, uint32_t* counts, int32_t* enab
     HIP_TRY(dcheck_collect_attention(n));
     HIP_TRY(dcheck_collect_misc(n));
     HIP_TRY(dcheck_collect_sample(n));
+    HIP_TRY(dcheck_collect_score(n));
     HIP_TRY(dcheck_collect_persist(n));
     for (int i = 0; i < CHK_N; ++i) counts[i] = n[i];
     return 0;

@@ -60,6 +60,8 @@ _SIGNATURES = {
     "l3_reset_cache": (ctypes.c_int, [_P]),
     "l3_forward_host": (ctypes.c_int, [_P, _P, _I32, _I32, _I32, _P]),
     "l3_forward_dev": (ctypes.c_int, [_P, _P, _I32, _I32, _I32, _P]),
+    "l3_score_host": (ctypes.c_int, [_P, _P, _P, _I32, _I32, _I32, _P, _P]),
+    "l3_set_score_workspace": (ctypes.c_int, [_P, _I64]),
     "l3_greedy_step_host": (ctypes.c_int, [_P, _P, _I32, _I32, _I32, _P, _P]),
     "l3_layer_forward_host": (ctypes.c_int, [_P, _I32, _P, _I32, _I32, _I32, _P]),
     "l3_greedy_generate_host": (ctypes.c_int, [_P, _P, _I32, _I32, _I32, _P]),
@@ -76,6 +78,7 @@ _SIGNATURES = {
     "l3_op_rope_host": (ctypes.c_int, [_P, _P, _I32, _I32, _I32, _I32, _P, _P, _P]),
     "l3_op_ffn_host": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _P, _P, _P, _P]),
     "l3_op_linear_host": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _P, _P]),
+    "l3_op_linear_logprob_host": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _P, _P, _P, _P, _P]),
     "l3_dev_alloc": (ctypes.c_int, [_P, _SZ, _P]),
     "l3_dev_free": (ctypes.c_int, [_P, _P]),
     "l3_h2d": (ctypes.c_int, [_P, _P, _P, _SZ]),
@@ -309,6 +312,27 @@ class Context:
         out = pinned.empty((B, self.dims.vocab_size), np.float32)  # DMA target of the D2H
         check(lib().l3_forward_host(self._h, ptr(ids), B, L, start_pos, ptr(out)))
         return out
+
+    def score(self, ids: np.ndarray, targets: np.ndarray, start_pos: int, want_argmax: bool = False):
+        """Teacher-forced scoring (l3_score_host): one forward over ``ids`` [B, L] that returns
+        float32 [B, L] with the log-probability of ``targets`` [B, L] at every position (-1: no
+        target, scored 0.0), without materialising the logits; with ``want_argmax`` also the int32
+        greedy id of every position.  Writes the K / V cache as ``forward`` does."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        targets = np.ascontiguousarray(targets, dtype=np.int64)
+        if ids.ndim != 2 or targets.shape != ids.shape:
+            raise ValueError(f"ids {ids.shape} and targets {targets.shape} must be the same [B, L]")
+        B, L = ids.shape
+        lp = np.empty((B, L), np.float32)
+        am = np.empty((B, L), np.int32) if want_argmax else None
+        check(lib().l3_score_host(self._h, ptr(ids), ptr(targets), B, L, int(start_pos), ptr(lp),
+                                  ptr(am) if am is not None else None))
+        return (lp, am) if want_argmax else lp
+
+    def set_score_workspace(self, nbytes: int) -> None:
+        """Bytes of the scoring workspace (16 per row and 64 columns of the vocabulary; default
+        64 MiB, 0 restores it).  The scores do not depend on it, bit for bit."""
+        check(lib().l3_set_score_workspace(self._h, int(nbytes)))
 
     def greedy_step(self, ids: np.ndarray, start_pos: int, want_logits: bool = False):
         ids = np.ascontiguousarray(ids, dtype=np.int64)
@@ -565,6 +589,24 @@ class Context:
         y = np.empty(x.shape[:-1] + (N,), np.float32)
         check(lib().l3_op_linear_host(self._h, ptr(x), x.size // K, K, N, ptr(w), ptr(y)))
         return y
+
+    def op_linear_logprob(self, x: np.ndarray, w: np.ndarray, targets: np.ndarray):
+        """The scoring lm_head on a plain product (l3_op_linear_logprob_host): for the rows of
+        ``x @ w.T`` and int targets (-1: none), (logprob float32, lse float32, argmax int32), each
+        of shape x.shape[:-1]; the logits are never written."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        w = np.ascontiguousarray(w, dtype=np.float32)
+        t = np.ascontiguousarray(targets, dtype=np.int32)
+        K = x.shape[-1]
+        N = w.shape[0]
+        if t.shape != x.shape[:-1]:
+            raise ValueError(f"targets {t.shape} for rows {x.shape[:-1]}")
+        lp = np.empty(t.shape, np.float32)
+        lse = np.empty(t.shape, np.float32)
+        am = np.empty(t.shape, np.int32)
+        check(lib().l3_op_linear_logprob_host(self._h, ptr(x), x.size // K, K, N, ptr(w), ptr(t), ptr(lp),
+                                              ptr(lse), ptr(am)))
+        return lp, lse, am
 
     def op_ffn(self, x: np.ndarray, wg: np.ndarray, wu: np.ndarray, wd: np.ndarray) -> np.ndarray:
         x = np.ascontiguousarray(x, dtype=np.float32)

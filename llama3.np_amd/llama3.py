@@ -365,6 +365,41 @@ class Llama:
                                       "index on every member")
         self._ctx.set_sampling(temperature, top_k, top_p, seed)
 
+    def score(self, input_ids, targets=None, start_pos: int = 0, return_argmax: bool = False):
+        """Extension: teacher-forced log-probabilities from one forward (DESIGN.md "Scoring").
+
+        ``targets=None`` scores next-token prediction inside the sequence: float32 ``[B, L-1]``
+        whose entry ``[b, t]`` is ``log p(input_ids[b, t+1] | input_ids[b, :t+1])``, so the
+        perplexity of a batch is ``exp(-model.score(ids).mean())``.  With ``targets`` ``[B, L]``
+        (int; -1 = no target, scored 0.0) the result is ``[B, L]``: position t against
+        ``targets[b, t]``.  ``return_argmax=True`` also returns the int64 greedy id of every scored
+        position.  The logits are never materialised (the lm_head reduces them in its epilogue),
+        and the call fills the KV cache at ``[start_pos, start_pos + L)`` as ``__call__`` does, so
+        a long text can be scored piece by piece.  Not for a model on more than one device."""
+        if self._group is not None and self._group.n > 1:
+            raise NotImplementedError("scoring on a multi-device model: sharding it is not implemented")
+        ids = np.asarray(input_ids)
+        if ids.ndim != 2:
+            raise ValueError(f"input_ids must be [B, L], got shape {ids.shape}")
+        inner = targets is None
+        if inner:
+            VS = self.args.vocab_size
+            tg = np.full(ids.shape, -1, np.int64)
+            nxt = ids[:, 1:].astype(np.int64)
+            # negative ids wrap as the embedding lookup wraps them; anything else out of range is
+            # left for the id check to report
+            tg[:, :-1] = np.where((nxt < 0) & (nxt >= -VS), nxt + VS, nxt)
+        else:
+            tg = np.asarray(targets)
+            if tg.shape != ids.shape:
+                raise ValueError(f"targets must have input_ids' shape {ids.shape}, got {tg.shape}")
+        out = self._ctx.score(ids, tg, int(start_pos), want_argmax=return_argmax)
+        lp, am = out if return_argmax else (out, None)
+        if inner:
+            lp = lp[:, :-1]
+            am = am[:, :-1] if am is not None else None
+        return (lp, am.astype(np.int64)) if return_argmax else lp
+
     def generate(self, input_ids, max_new_tokens: int) -> Iterator[np.ndarray]:
         """Greedy decode with the reference's exact position schedule
         (llama3.py:310-321): prefill at 0, then decode step i >= 1 at pos = L + i,
