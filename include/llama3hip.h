@@ -209,6 +209,39 @@ int l3_greedy_generate_host(l3_ctx* ctx, const int64_t* ids_host, int32_t B, int
 int l3_greedy_generate_values_host(l3_ctx* ctx, const int64_t* ids_host, int32_t B, int32_t L,
                                    int32_t max_new_tokens, int64_t* out_ids_host, float* out_vals);
 
+/* ---- ragged batches (extension; DESIGN.md "Ragged batches") ---------------- */
+/* Prompts of different lengths in one batch: row b holds lens[b] >= 1 tokens, right-padded to
+ * ids_host [B, Lmax] int64 (pad entries are ignored, whatever they hold).  Row b's result is what
+ * the reference (llama3.py:285-321) gives for that row alone on a zeroed cache.
+ * The prefill of Llama.__call__ (llama3.py:285-308) at position 0: logits_host [B, VS] fp32, row b
+ * the logits of its position lens[b] - 1.  Afterwards slots [0, lens[b]) of cache row b hold its
+ * K / V and slots [lens[b], Lmax) are zero, in every layer.  Every block runs on every row
+ * whatever l3_set_last_layer_rows says (the setting, the batch split and l3_set_gemm_x6 are left
+ * as they are; x6 applies to the layers).
+ * Errors, reported before anything is launched: B > max_batch_size, a lens[b] outside [1, Lmax],
+ * Lmax > max_seq_len, a token id outside [-VS, VS) at a real position; a context that is a member
+ * of a multi-device l3_group is refused. */
+int l3_ragged_forward_host(l3_ctx* ctx, const int64_t* ids_host, const int32_t* lens, int32_t B, int32_t Lmax,
+                           float* logits_host);
+/* The greedy loop of Llama.generate (llama3.py:310-321) per row, on the device: the prefill above,
+ * then row b's first token from its position lens[b] - 1 and its decode step i >= 1 at
+ * pos = lens[b] + i (slot lens[b] of the row is never written and reads as zero, the reference's
+ * schedule), max(0, max_new_tokens - lens[b]) tokens unless the row stops earlier.  A row that
+ * emits one of stop_ids [n_stop] int64 (may be NULL with n_stop 0) keeps that id as its last token
+ * and is finished: it writes no further K / V slot, is not attended and emits nothing more; the
+ * loop ends when every row is finished.  out_ids_host [B, cap] int64 with
+ * cap = max_new_tokens - min(lens); out_lens [B] int32 = tokens of each row, the entries past
+ * them -1.  With sampling on (l3_set_sampling) row b's token at position p draws the uniform of
+ * (seed, b, p), so rows of equal length reproduce l3_greedy_generate_host.  One copy-back at the
+ * end (with stop ids also a 4-byte "rows still running" read every few steps, to leave early).
+ * Errors as above, and max_new_tokens > max_seq_len; a shape whose decode attention does not fit
+ * its LDS budget (n_heads / n_kv_heads > 8, or scores of that many heads over max_new_tokens
+ * positions past 64 KiB: about 2 800 positions at four heads per KV head) is refused, all before
+ * anything is launched. */
+int l3_ragged_generate_host(l3_ctx* ctx, const int64_t* ids_host, const int32_t* lens, int32_t B, int32_t Lmax,
+                            int32_t max_new_tokens, const int64_t* stop_ids, int32_t n_stop,
+                            int64_t* out_ids_host, int32_t* out_lens);
+
 /* ---- one block (replaces TransformerBlock.__call__, llama3.py:239-261) --- */
 /* x [B, L, D] fp32 host -> out [B, L, D]; uses and updates layer's KV cache. */
 int l3_layer_forward_host(l3_ctx* ctx, int32_t layer, const float* x_host, int32_t B,

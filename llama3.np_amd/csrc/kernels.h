@@ -391,6 +391,48 @@ __device__ __forceinline__ int start_of(const Args& p) {
     return p.pos_dev ? *p.pos_dev : p.start_pos;
 }
 
+// Ragged batches (ragged.hip; DESIGN.md "Ragged batches"): the per-row decode state, device
+// arrays of one entry per batch row
+struct RaggedState {
+    int32_t* pos;          // position the row's next token runs at (before the first token choice: len - 1)
+    int32_t* cur_id;       // the row's last token: the next step's input
+    int32_t* finished;     // 1: stop id emitted or budget spent; the row writes and emits nothing more
+    int32_t* n_out;        // tokens emitted
+    const int32_t* len;    // prompt length
+    const int32_t* budget; // tokens the row may emit: max_new_tokens - len
+    int32_t* out;          // [B, cap] emitted ids (-1 past n_out)
+    int cap;
+    const int32_t* stop;   // [n_stop] stop ids
+    int n_stop;
+    int32_t* live;         // [1] rows still running after the last ragged_advance_kernel
+};
+struct RaggedAttnArgs {
+    const float* qkv;      // [B, (H + 2 KVH) * HD] the step's raw [q | k | v] rows (no RoPE, no scale)
+    float* cache_k;        // [maxB, KVH, Smax, HD]; slot pos[b] of row b is appended
+    float* cache_v;
+    float* out;            // [B, H * HD]
+    const float* rope_cos; const float* rope_sin;  // [Smax, HD/2]
+    const int32_t* pos;    // RaggedState::pos
+    const int32_t* finished;
+    int B, H, KVH, HD, Smax;
+    int s_cap;             // score slots per head in LDS (a multiple of 4): every live pos < s_cap
+    float q_scale;         // log2(e) / sqrt(HD)
+};
+constexpr int RAGGED_MAX_REP = 8;               // query heads per KV head the ragged attention takes
+constexpr size_t RAGGED_LDS_BYTES = 64 * 1024;  // its LDS budget per workgroup
+// LDS bytes of attn_decode_ragged_kernel; whether the shape fits (head size, n_rep, LDS budget)
+size_t attn_decode_ragged_lds(int H, int KVH, int HD, int s_cap);
+bool attn_decode_ragged_ok(int H, int KVH, int HD, int s_cap);
+hipError_t launch_attn_decode_ragged(const RaggedAttnArgs& a, hipStream_t s);
+// cache[b][h][len[b] .. Lmax) = 0 for b < B, h < KVH, in both caches
+hipError_t launch_ragged_zero_tail(float* cache_k, float* cache_v, const int32_t* len, int B, int KVH, int Smax,
+                                   int HD, int Lmax, hipStream_t s);
+// u[b] = the sampling uniform of (seed, b, pos[b])
+hipError_t launch_ragged_uniform(const SampleParams* prm, const int32_t* pos, float* u, int B, hipStream_t s);
+// end of a step: tok[b] recorded, stop / budget, position advance (ragged.hip)
+hipError_t launch_ragged_advance(const RaggedState& st, const int32_t* tok, int B, int n_ids, hipStream_t s);
+hipError_t dcheck_collect_ragged(unsigned* out);
+
 // Persistent batch-1 decode step (decode_persist.hip): one launch runs a whole greedy step —
 // every layer, the lm_head and the argmax — with in-launch hand-offs between the stages
 struct DecodePersistArgs {

@@ -1,0 +1,280 @@
+// Ragged batches (DESIGN.md "Ragged batches"): decode steps whose rows sit at different
+// positions.  The per-row state (position, current id, finished flag, output count) lives in
+// device memory, so a step's launches are the same from step to step; the kernels here are the
+// ones that read it — the decode attention, the sampling uniforms, the per-step bookkeeping —
+// and the tail clear that follows a right-padded prefill.  The projections, the lm_head and the
+// token choice are the library's existing launches at M = B, L = 1 (runtime.hip ragged_step).
+#include <math.h>
+
+#include "kernels.h"
+
+namespace l3 {
+
+namespace {
+
+using f32x4 = __attribute__((ext_vector_type(4))) float;
+
+// Decode attention over rows at their own positions (llama3.py:163-211 for one new token per
+// row; the cache slice :186-187 ends at the row's pos).  One workgroup per (KV head, row): the
+// n_rep = H / KVH query heads that share the KV head are served together, so every K and V row
+// of the cache is read once per KV head, not once per query head as attn_decode_kernel does.
+//
+// Input is the raw QKV projection row of the step's token ([q | k | v], no RoPE, no scale):
+//   (0) RoPE (llama3.py:41-76, adjacent pairs) on the n_rep q heads, scaled by
+//       log2(e)/sqrt(HD), into LDS; RoPE on the new k; k and v appended to slot pos of the cache
+//       and kept in LDS — the block never reads its own global stores back;
+//   (1) scores, one cached key per thread (its HD/4 float4 loads in flight together), against
+//       the n_rep queries; the new key's scores from LDS;
+//   (2) one wave per query head: max, exp2, sum over the head's pos + 1 scores in LDS;
+//   (3) P.V with 256 / (HD/4) key groups x HD/4 float4 columns, n_rep accumulators per thread;
+//       the groups' partials meet in LDS.
+// A finished row (or one whose position is not a cache slot, which the host never launches)
+// writes zeros to its output rows and touches nothing else.
+// LDS floats: [n_rep][HD] q, [HD] k, [HD] v, [8] row sums, [n_rep][R][HD] partials,
+// [n_rep][s_cap] scores (attn_decode_ragged_lds).
+template <int HD>
+__global__ void __launch_bounds__(256) attn_decode_ragged_kernel(RaggedAttnArgs p) {
+    constexpr int D4 = HD / 4, R = 256 / D4, HALF = HD / 2;
+    extern __shared__ __attribute__((aligned(16))) float dsm[];
+    const int n_rep = p.H / p.KVH;
+    float* qs = dsm;
+    float* kn = qs + n_rep * HD;
+    float* vn = kn + HD;
+    float* ls = vn + HD;
+    float* red = ls + 8;
+    float* sc = red + n_rep * R * HD;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int kvh = blockIdx.x, b = blockIdx.y, h0 = kvh * n_rep;
+    const int pos = p.pos[b];
+    const bool dead = p.finished[b] != 0;
+    if (tid == 0 && !dead) {
+        L3_DCHECK(pos >= 0 && pos < p.Smax, CHK_KV_SLOT);
+        L3_DCHECK(pos >= 0 && pos < p.Smax && pos < p.s_cap, CHK_ATTN_KEYS);
+    }
+    float* orow = p.out + ((int64_t)b * p.H + h0) * HD;  // the n_rep heads' rows are adjacent
+    if (dead || pos < 0 || pos >= p.Smax || pos >= p.s_cap) {
+        for (int i = tid; i < n_rep * D4; i += 256) reinterpret_cast<f32x4*>(orow)[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        return;
+    }
+    const int qdim = p.H * HD, kvdim = p.KVH * HD;
+    const float* row = p.qkv + (int64_t)b * (qdim + 2 * kvdim);
+    const float* cs = p.rope_cos + (int64_t)pos * HALF;
+    const float* sn = p.rope_sin + (int64_t)pos * HALF;
+    const int64_t kv_base = ((int64_t)b * p.KVH + kvh) * p.Smax * HD;
+    // (0) the step's q, k, v
+    for (int t = tid; t < n_rep * HALF; t += 256) {
+        const int r = t / HALF, i = t - r * HALF;
+        const float2 v = *reinterpret_cast<const float2*>(row + (h0 + r) * HD + 2 * i);
+        const float c = cs[i], s = sn[i];
+        const float r0 = v.x * c - v.y * s, r1 = v.x * s + v.y * c;
+        *reinterpret_cast<float2*>(qs + r * HD + 2 * i) = float2{r0 * p.q_scale, r1 * p.q_scale};
+    }
+    if (tid < HALF) {
+        const int i = tid;
+        const float2 v = *reinterpret_cast<const float2*>(row + qdim + kvh * HD + 2 * i);
+        const float c = cs[i], s = sn[i];
+        const float2 k2 = float2{v.x * c - v.y * s, v.x * s + v.y * c};
+        *reinterpret_cast<float2*>(kn + 2 * i) = k2;
+        *reinterpret_cast<float2*>(p.cache_k + kv_base + (int64_t)pos * HD + 2 * i) = k2;
+    } else if (tid < HD) {
+        const int i = tid - HALF;
+        const float2 v2 = *reinterpret_cast<const float2*>(row + qdim + kvdim + kvh * HD + 2 * i);
+        *reinterpret_cast<float2*>(vn + 2 * i) = v2;
+        *reinterpret_cast<float2*>(p.cache_v + kv_base + (int64_t)pos * HD + 2 * i) = v2;
+    }
+    __syncthreads();
+    const f32x4* K4 = reinterpret_cast<const f32x4*>(p.cache_k + kv_base);
+    const f32x4* V4 = reinterpret_cast<const f32x4*>(p.cache_v + kv_base);
+    const f32x4* q4 = reinterpret_cast<const f32x4*>(qs);
+    // (1) scores of the cached keys [0, pos): each K row loaded once for the n_rep heads
+    for (int k = tid; k < pos; k += 256) {
+        f32x4 kv[D4];
+#pragma unroll
+        for (int i = 0; i < D4; ++i) kv[i] = K4[(int64_t)k * D4 + i];
+#pragma unroll
+        for (int r = 0; r < RAGGED_MAX_REP; ++r) {
+            if (r < n_rep) {
+                float s = 0.f;
+#pragma unroll
+                for (int i = 0; i < D4; ++i) {
+                    const f32x4 q = q4[r * D4 + i];
+                    s += kv[i].x * q.x + kv[i].y * q.y + kv[i].z * q.z + kv[i].w * q.w;
+                }
+                sc[r * p.s_cap + k] = s;
+            }
+        }
+    }
+    if (tid < n_rep) {  // the new key, from LDS
+        const f32x4* k4 = reinterpret_cast<const f32x4*>(kn);
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < D4; ++i) {
+            const f32x4 q = q4[tid * D4 + i], k = k4[i];
+            s += k.x * q.x + k.y * q.y + k.z * q.z + k.w * q.w;
+        }
+        sc[tid * p.s_cap + pos] = s;
+    }
+    __syncthreads();
+    // (2) softmax numerators and row sums, one wave per head
+    for (int r = wid; r < n_rep; r += 4) {
+        float* s = sc + r * p.s_cap;
+        float m = -INFINITY;
+        for (int k = lane; k <= pos; k += 64) m = fmaxf(m, s[k]);
+        m = group_max<64>(m);
+        float l = 0.f;
+        for (int k = lane; k <= pos; k += 64) {
+            const float e = __builtin_amdgcn_exp2f(s[k] - m);
+            s[k] = e;
+            l += e;
+        }
+        l = group_sum<64>(l);
+        if (lane == 0) ls[r] = l;
+    }
+    __syncthreads();
+    // (3) P.V: each V row loaded once for the n_rep heads
+    const int rg = tid / D4, d4 = tid - rg * D4;
+    if (rg < R) {
+        f32x4 acc[RAGGED_MAX_REP];
+#pragma unroll
+        for (int r = 0; r < RAGGED_MAX_REP; ++r) acc[r] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int k = rg; k < pos; k += R) {
+            const f32x4 v = V4[(int64_t)k * D4 + d4];
+#pragma unroll
+            for (int r = 0; r < RAGGED_MAX_REP; ++r)
+                if (r < n_rep) acc[r] += sc[r * p.s_cap + k] * v;
+        }
+        if (rg == 0) {  // the new value, from LDS
+            const f32x4 v = reinterpret_cast<const f32x4*>(vn)[d4];
+#pragma unroll
+            for (int r = 0; r < RAGGED_MAX_REP; ++r)
+                if (r < n_rep) acc[r] += sc[r * p.s_cap + pos] * v;
+        }
+#pragma unroll
+        for (int r = 0; r < RAGGED_MAX_REP; ++r)
+            if (r < n_rep) reinterpret_cast<f32x4*>(red)[(r * R + rg) * D4 + d4] = acc[r];
+    }
+    __syncthreads();
+    for (int t = tid; t < n_rep * D4; t += 256) {
+        const int r = t / D4, d = t - r * D4;
+        f32x4 o = {0.f, 0.f, 0.f, 0.f};
+        for (int g = 0; g < R; ++g) o += reinterpret_cast<const f32x4*>(red)[(r * R + g) * D4 + d];
+        reinterpret_cast<f32x4*>(orow)[t] = o * (1.0f / ls[r]);
+    }
+}
+
+// After a right-padded prefill at position 0 (llama3.py:285-308 on [B, Lmax]): slots
+// [len[b], Lmax) of row b hold the pads' K / V; a row run alone would have left them zero
+// (slot len[b] is the one the reference's loop never writes, :312-318).  grid (KVH, B)
+__global__ void __launch_bounds__(256) ragged_zero_tail_kernel(float* __restrict__ ck, float* __restrict__ cv,
+                                                               const int32_t* __restrict__ len, int KVH, int Smax,
+                                                               int HD, int Lmax) {
+    const int h = blockIdx.x, b = blockIdx.y;
+    const int l = len[b];
+    if (threadIdx.x == 0) L3_DCHECK(l >= 1 && l <= Lmax && Lmax <= Smax, CHK_KV_SLOT);
+    if (l < 0 || l >= Lmax || Lmax > Smax) return;
+    const int64_t base = (((int64_t)b * KVH + h) * Smax + l) * HD;
+    const int n4 = (Lmax - l) * (HD / 4);
+    f32x4* k4 = reinterpret_cast<f32x4*>(ck + base);
+    f32x4* v4 = reinterpret_cast<f32x4*>(cv + base);
+    for (int i = threadIdx.x; i < n4; i += 256) {
+        k4[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        v4[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+}
+
+// the uniform row b's token choice draws: the counter of l3_set_sampling, (seed, b, pos[b])
+__global__ void ragged_uniform_kernel(const SampleParams* __restrict__ prm, const int32_t* __restrict__ pos,
+                                      float* __restrict__ u, int B) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < B) u[b] = (float)sample_bits24(prm->seed_lo, prm->seed_hi, b, pos[b]) * 0x1p-24f;
+}
+
+// End of a step (llama3.py:312-320 per row): a live row keeps its token, stops on a stop id or
+// at its budget, and otherwise moves to the position its next token runs at — len + 1 after the
+// prefill's token (the reference's loop skips slot len), one further after every decode step.
+// One workgroup; live[0] = rows still running.
+__global__ void __launch_bounds__(256) ragged_advance_kernel(RaggedState st, const int32_t* __restrict__ tok, int B,
+                                                             int n_ids) {
+    __shared__ int live;
+    if (threadIdx.x == 0) live = 0;
+    __syncthreads();
+    for (int b = threadIdx.x; b < B; b += 256) {
+        if (st.finished[b]) continue;
+        const int id = tok[b];
+        const bool ok = id >= 0 && id < n_ids;
+        L3_DCHECK(ok, CHK_TOKEN_ID);
+        const int n = st.n_out[b];
+        if (n < st.cap) st.out[(int64_t)b * st.cap + n] = id;
+        st.n_out[b] = n + 1;
+        st.cur_id[b] = ok ? id : 0;
+        bool fin = n + 1 >= st.budget[b];
+        for (int s = 0; s < st.n_stop; ++s) fin |= st.stop[s] == id;
+        if (fin) {
+            st.finished[b] = 1;
+        } else {
+            const int q = st.pos[b], l = st.len[b];
+            st.pos[b] = q == l - 1 ? l + 1 : q + 1;
+            atomicAdd(&live, 1);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) st.live[0] = live;
+}
+
+template <int HD>
+hipError_t launch_ragged_hd(const RaggedAttnArgs& a, size_t lds, hipStream_t s) {
+    hipLaunchKernelGGL((attn_decode_ragged_kernel<HD>), dim3(a.KVH, a.B), dim3(256), lds, s, a);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+size_t attn_decode_ragged_lds(int H, int KVH, int HD, int s_cap) {
+    const size_t n_rep = (size_t)(H / KVH), R = 256 / (size_t)(HD / 4);
+    return (n_rep * HD + 2 * (size_t)HD + 8 + n_rep * R * HD + n_rep * (size_t)s_cap) * 4;
+}
+
+bool attn_decode_ragged_ok(int H, int KVH, int HD, int s_cap) {
+    if (KVH <= 0 || H % KVH != 0 || H / KVH > RAGGED_MAX_REP || s_cap <= 0 || s_cap % 4) return false;
+    if (!(HD == 16 || HD == 32 || HD == 48 || HD == 64 || HD == 96 || HD == 128)) return false;
+    return attn_decode_ragged_lds(H, KVH, HD, s_cap) <= RAGGED_LDS_BYTES;
+}
+
+hipError_t launch_attn_decode_ragged(const RaggedAttnArgs& a, hipStream_t s) {
+    if (a.B <= 0) return hipSuccess;
+    if (!attn_decode_ragged_ok(a.H, a.KVH, a.HD, a.s_cap)) return hipErrorInvalidValue;
+    const size_t lds = attn_decode_ragged_lds(a.H, a.KVH, a.HD, a.s_cap);
+    switch (a.HD) {
+        case 16: return launch_ragged_hd<16>(a, lds, s);
+        case 32: return launch_ragged_hd<32>(a, lds, s);
+        case 48: return launch_ragged_hd<48>(a, lds, s);
+        case 64: return launch_ragged_hd<64>(a, lds, s);
+        case 96: return launch_ragged_hd<96>(a, lds, s);
+        case 128: return launch_ragged_hd<128>(a, lds, s);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_ragged_zero_tail(float* cache_k, float* cache_v, const int32_t* len, int B, int KVH, int Smax,
+                                   int HD, int Lmax, hipStream_t s) {
+    if (B <= 0 || Lmax <= 1) return hipSuccess;  // Lmax 1: every len is 1, no tail
+    if (Lmax > Smax || HD % 4) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ragged_zero_tail_kernel, dim3(KVH, B), dim3(256), 0, s, cache_k, cache_v, len, KVH, Smax, HD, Lmax);
+    return hipGetLastError();
+}
+
+hipError_t launch_ragged_uniform(const SampleParams* prm, const int32_t* pos, float* u, int B, hipStream_t s) {
+    if (B <= 0) return hipSuccess;
+    hipLaunchKernelGGL(ragged_uniform_kernel, dim3((B + 255) / 256), dim3(256), 0, s, prm, pos, u, B);
+    return hipGetLastError();
+}
+
+hipError_t launch_ragged_advance(const RaggedState& st, const int32_t* tok, int B, int n_ids, hipStream_t s) {
+    if (B <= 0) return hipSuccess;
+    hipLaunchKernelGGL(ragged_advance_kernel, dim3(1), dim3(256), 0, s, st, tok, B, n_ids);
+    return hipGetLastError();
+}
+
+hipError_t dcheck_collect_ragged(unsigned* out) { return dcheck_collect(out); }
+
+}  // namespace l3

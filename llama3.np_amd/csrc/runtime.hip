@@ -249,6 +249,19 @@ struct l3_ctx {
     int32_t* score_rows = nullptr;              // [5][score_rows_cap]: targets, target logit, logprob, lse, argmax
     int64_t score_rows_cap = 0;
     std::vector<int32_t> score_tgt_host;        // int32 staging of the int64 host targets
+    // ragged batches (l3_ragged_*; ragged.hip): per-row device state [RAG_WORDS][max_batch_size]
+    // int32 (pos, cur_id, finished, n_out, len, budget, lm_head rows, token) + the live word, the
+    // step's raw QKV rows and sampling uniforms, the output ids and the stop list (grown on demand)
+    static constexpr int RAG_WORDS = 8;
+    int32_t* rag_state = nullptr;
+    float* rag_qkv = nullptr;                   // [max_batch_size, qkvn]
+    float* rag_u = nullptr;                     // [max_batch_size]
+    int32_t* rag_out = nullptr;                 // [B, cap]
+    int64_t rag_out_n = 0;
+    int32_t* rag_stop = nullptr;
+    int64_t rag_stop_n = 0;
+    std::vector<int32_t> rag_host;              // host staging of rag_state (kept until the call's sync)
+    std::vector<int64_t> rag_ids_host;          // the padded ids with the pads replaced
 };
 
 static bool sampling_on(const l3_ctx* c) { return c->samp.temperature > 0.f; }
@@ -511,6 +524,7 @@ extern "C" int l3_destroy(l3_ctx* c) {
     drop_decode_graph(c);
     dfree(c->dec_ids); dfree(c->dec_state); dfree(c->kv_bak); dfree(c->samp_dev);
     dfree(c->score_ws); dfree(c->score_rows);
+    dfree(c->rag_state); dfree(c->rag_qkv); dfree(c->rag_u); dfree(c->rag_out); dfree(c->rag_stop);
     if (c->dec_host) (void)hipHostFree(c->dec_host);
     for (auto& q : c->spec_q) { (void)hipEventDestroy(q.ev0); (void)hipEventDestroy(q.ev1); (void)hipEventDestroy(q.ev); }
     for (hipEvent_t e : c->spec_free) (void)hipEventDestroy(e);
@@ -1838,6 +1852,227 @@ extern "C" int l3_greedy_generate_values_host(l3_ctx* c, const int64_t* ids_host
     return greedy_generate(c, ids_host, B, L, max_new_tokens, out_ids_host, out_vals);
 }
 
+// ---------------------------------------------------------------------------------------
+// Ragged batches (extension of llama3.py:285-321; DESIGN.md "Ragged batches"): prompts of
+// different lengths, right-padded to [B, Lmax].  The prefill is the ordinary causal one (pads only
+// follow a row's real tokens, so every real position is computed as if the row ran alone) with the
+// lm_head reading each row's own last position and the pads' K / V slots cleared afterwards; the
+// decode steps keep every row's position, id and finished flag on the device (ragged.hip).
+enum RagWord : int { RAG_POS = 0, RAG_CUR, RAG_FIN, RAG_NOUT, RAG_LEN, RAG_BUDGET, RAG_ROWS, RAG_TOK };
+static_assert(RAG_TOK + 1 == l3_ctx::RAG_WORDS, "one array of max_batch_size words per RagWord");
+
+static int32_t* rag_word(l3_ctx* c, int w) { return c->rag_state + (int64_t)w * c->d.max_batch_size; }
+
+// everything that can be refused, before anything is allocated or launched
+static int ragged_check(l3_ctx* c, const char* who, const int64_t* ids_host, const int32_t* lens, int B, int Lmax) {
+    if (!ids_host || !lens) return fail("%s: null argument", who);
+    if (need_model(c) || check_call(c, B, Lmax, 0)) return 1;
+    if (c->group && group_members(c->group) > 1)
+        return fail("%s: this context is a member of a multi-device l3_group (not supported)", who);
+    for (int b = 0; b < B; ++b)
+        if (lens[b] < 1 || lens[b] > Lmax) return fail("%s: lens[%d] = %d outside [1, %d]", who, b, lens[b], Lmax);
+    const int64_t VS = c->d.vocab_size;
+    for (int b = 0; b < B; ++b)
+        for (int t = 0; t < lens[b]; ++t) {  // pads are never looked at
+            const int64_t id = ids_host[(int64_t)b * Lmax + t];
+            if (id < -VS || id >= VS)  // NumPy fancy indexing raises IndexError here (llama3.py:287)
+                return fail("token id %lld out of range for vocab_size %lld", (long long)id, (long long)VS);
+        }
+    return 0;
+}
+
+static int ragged_bufs(l3_ctx* c) {
+    if (c->rag_state) return 0;
+    const int64_t mb = c->d.max_batch_size;
+    HIP_TRY(hipMalloc(&c->rag_state, (size_t)(l3_ctx::RAG_WORDS * mb + 4) * 4));
+    HIP_TRY(hipMalloc(&c->rag_qkv, (size_t)mb * c->qkvn * 4));
+    HIP_TRY(hipMalloc(&c->rag_u, (size_t)mb * 4));
+    return 0;
+}
+
+// The prefill at position 0 (llama3.py:285-308) on the padded batch: the per-row state uploaded,
+// every block on every row (as l3_score_host runs them), row b's logits from its position
+// lens[b] - 1 into c->logits, then the pads' slots [lens[b], Lmax) cleared in every layer.
+// max_new_tokens: the generate loop's (0: a forward only).
+static int ragged_prefill(l3_ctx* c, const int64_t* ids_host, const int32_t* lens, int B, int Lmax,
+                          int max_new_tokens) {
+    const int64_t mb = c->d.max_batch_size;
+    c->rag_ids_host.assign((size_t)B * Lmax, 0);  // pads become a valid id
+    c->rag_host.assign((size_t)(l3_ctx::RAG_WORDS * mb + 4), 0);
+    for (int b = 0; b < B; ++b) {
+        for (int t = 0; t < lens[b]; ++t) c->rag_ids_host[(size_t)b * Lmax + t] = ids_host[(int64_t)b * Lmax + t];
+        int32_t* h = c->rag_host.data() + b;
+        h[RAG_POS * mb] = lens[b] - 1;  // the position the first token is chosen (and drawn) at
+        h[RAG_LEN * mb] = lens[b];
+        h[RAG_BUDGET * mb] = max_new_tokens - lens[b];
+        h[RAG_FIN * mb] = max_new_tokens - lens[b] <= 0;
+        h[RAG_ROWS * mb] = b * Lmax + lens[b] - 1;
+    }
+    if (upload_ids(c, c->rag_ids_host.data(), (int64_t)B * Lmax)) return 1;
+    HIP_TRY(hipMemcpyAsync(c->rag_state, c->rag_host.data(), c->rag_host.size() * 4, hipMemcpyHostToDevice, c->stream));
+    const int nl = (int)c->layers.size();
+    for (int li = 0; li < nl; ++li)
+        if (run_layer(c, li, B, Lmax, 0, nullptr, li == 0 ? c->ids : nullptr)) return 1;
+    GemmArgs lm = lm_head_args(c, B, 1, c->logits, 0);  // A row b = h row b * Lmax + lens[b] - 1
+    lm.a_rows = rag_word(c, RAG_ROWS);
+    if (timed(c, L3_K_LMHEAD, [&] { return launch_gemm(EPI_STORE, lm, c->stream); })) return 1;
+    for (auto& Ly : c->layers)
+        HIP_TRY(launch_ragged_zero_tail(Ly.cache_k, Ly.cache_v, rag_word(c, RAG_LEN), B, c->d.n_kv_heads,
+                                        c->d.max_seq_len, c->HD, Lmax, c->stream));
+    return 0;
+}
+
+extern "C" int l3_ragged_forward_host(l3_ctx* c, const int64_t* ids_host, const int32_t* lens, int32_t B,
+                                      int32_t Lmax, float* logits_host) {
+    CHECK_CTX(c);
+    if (!logits_host) return fail("l3_ragged_forward_host: null argument");
+    if (ragged_check(c, "l3_ragged_forward_host", ids_host, lens, B, Lmax)) return 1;
+    if (set_dev(c) || spec_resolve(c) || ensure_ws(c, B, Lmax) || ragged_bufs(c)) return 1;
+    if (ragged_prefill(c, ids_host, lens, B, Lmax, 0)) return 1;
+    HIP_TRY(hipMemcpyAsync(logits_host, c->logits, (size_t)B * c->d.vocab_size * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// One decode step of every row at its own position (llama3.py:239-261 per block at B x 1 tokens,
+// then :304-307): per layer the raw QKV rows (layer 0 from the embedding rows of cur_id), the
+// ragged attention (RoPE, K / V append at pos[b], one K / V read per KV head), O-proj, gate|up
+// and down at M = B; then the lm_head into c->logits.  Decode keeps the fp32 kernels (no x6).
+static int ragged_step(l3_ctx* c, int B, int s_cap) {
+    const int D = c->d.dim, FD = c->d.hidden_dim;
+    const int32_t* cur = rag_word(c, RAG_CUR);
+    hipStream_t s = c->stream;
+    for (size_t li = 0; li < c->layers.size(); ++li) {
+        Layer& Ly = c->layers[li];
+        GemmArgs g{};  // rmsnorm -> QKV, raw
+        g.eps = c->d.norm_eps;
+        g.A = c->h; g.lda = D; g.W = Ly.wqkv; g.C = c->rag_qkv; g.ldc = c->qkvn;
+        g.M = B; g.N = c->qkvn; g.K = D; g.norm = true;
+        g.ws = c->skws; g.ws_cap = c->skws_cap;
+        if (li == 0) { g.A = c->emb; g.a_rows = cur; }
+        if (timed(c, L3_K_QKV, [&] { return launch_gemm(EPI_STORE, g, s); })) return 1;
+        RaggedAttnArgs a{};
+        a.qkv = c->rag_qkv; a.cache_k = Ly.cache_k; a.cache_v = Ly.cache_v; a.out = c->attn;
+        a.rope_cos = c->rope_cos; a.rope_sin = c->rope_sin;
+        a.pos = rag_word(c, RAG_POS); a.finished = rag_word(c, RAG_FIN);
+        a.B = B; a.H = c->d.n_heads; a.KVH = c->d.n_kv_heads; a.HD = c->HD; a.Smax = c->d.max_seq_len;
+        a.s_cap = s_cap;
+        a.q_scale = (float)(1.4426950408889634 / std::sqrt((double)c->HD));
+        if (timed(c, L3_K_ATTN, [&] { return launch_attn_decode_ragged(a, s); })) return 1;
+        GemmArgs o{};  // O-proj + residual (layer 0: h = emb[cur_id] + attn . Wo^T)
+        o.A = c->attn; o.lda = c->qdim; o.W = Ly.wo; o.C = c->h; o.ldc = D;
+        o.M = B; o.N = D; o.K = c->qdim; o.norm = false;
+        o.ws = c->skws; o.ws_cap = c->skws_cap;
+        if (li == 0) { o.res_src = c->emb; o.res_rows = cur; }
+        if (timed(c, L3_K_OPROJ, [&] { return launch_gemm(EPI_RESID, o, s); })) return 1;
+        GemmArgs gu{};  // rmsnorm -> gate|up -> SwiGLU
+        gu.A = c->h; gu.lda = D; gu.W = Ly.wgu; gu.C = c->hid; gu.ldc = FD;
+        gu.M = B; gu.N = 2 * FD; gu.K = D; gu.norm = true; gu.eps = c->d.norm_eps;
+        GemmArgs dn{};  // down + residual
+        dn.A = c->hid; dn.lda = FD; dn.W = Ly.wd; dn.C = c->h; dn.ldc = D;
+        dn.M = B; dn.N = D; dn.K = FD; dn.norm = false;
+        gu.ws = dn.ws = c->skws; gu.ws_cap = dn.ws_cap = c->skws_cap;
+        if (timed(c, L3_K_GATEUP, [&] { return launch_gemm(EPI_SWIGLU, gu, s); })) return 1;
+        if (timed(c, L3_K_DOWN, [&] { return launch_gemm(EPI_RESID, dn, s); })) return 1;
+    }
+    const GemmArgs lm = lm_head_args(c, B, 1, c->logits, 0);
+    return timed(c, L3_K_LMHEAD, [&] { return launch_gemm(EPI_STORE, lm, s); });
+}
+
+// Token choice on c->logits (llama3.py:320, or the sampling rule with row b's uniform of
+// (seed, b, pos[b])), then the rows' bookkeeping
+static int ragged_choose(l3_ctx* c, const RaggedState& st, int B) {
+    int32_t* tok = rag_word(c, RAG_TOK);
+    const int VS = c->d.vocab_size;
+    if (timed(c, L3_K_ARGMAX, [&] {
+            if (!sampling_on(c)) return launch_argmax(c->logits, B, VS, tok, c->stream);
+            const hipError_t e = launch_ragged_uniform(c->samp_dev, st.pos, c->rag_u, B, c->stream);
+            if (e != hipSuccess) return e;
+            return launch_sample(c->logits, B, VS, tok, c->samp_dev, c->rag_u, 0, 0, c->stream);
+        }))
+        return 1;
+    HIP_TRY(launch_ragged_advance(st, tok, B, VS, c->stream));
+    return 0;
+}
+
+extern "C" int l3_ragged_generate_host(l3_ctx* c, const int64_t* ids_host, const int32_t* lens, int32_t B,
+                                       int32_t Lmax, int32_t max_new_tokens, const int64_t* stop_ids,
+                                       int32_t n_stop, int64_t* out_ids_host, int32_t* out_lens) {
+    CHECK_CTX(c);
+    const char* who = "l3_ragged_generate_host";
+    if (!out_lens || n_stop < 0 || (n_stop > 0 && !stop_ids)) return fail("%s: null argument", who);
+    if (ragged_check(c, who, ids_host, lens, B, Lmax)) return 1;
+    // the last decode step runs at position max_new_tokens - 1, which must be a cache slot
+    // (the reference fails there with a broadcast error, llama3.py:184)
+    if (max_new_tokens > c->d.max_seq_len)
+        return fail("generate: last decode position %d exceeds max_seq_len %d", max_new_tokens - 1, c->d.max_seq_len);
+    int min_len = lens[0];
+    for (int b = 0; b < B; ++b) {
+        min_len = lens[b] < min_len ? lens[b] : min_len;
+        out_lens[b] = 0;
+    }
+    const int cap = max_new_tokens - min_len;
+    if (cap <= 0) return 0;  // no row has a token to emit
+    if (!out_ids_host) return fail("%s: null argument", who);
+    const int s_cap = (max_new_tokens + 3) & ~3;
+    if (!attn_decode_ragged_ok(c->d.n_heads, c->d.n_kv_heads, c->HD, s_cap))
+        return fail("%s: the decode attention takes at most %d query heads per KV head and %zu bytes of LDS "
+                    "(%d heads per KV head over %d positions need %zu)", who, RAGGED_MAX_REP, RAGGED_LDS_BYTES,
+                    c->d.n_heads / c->d.n_kv_heads, max_new_tokens,
+                    attn_decode_ragged_lds(c->d.n_heads, c->d.n_kv_heads, c->HD, s_cap));
+    if (set_dev(c) || spec_resolve(c) || ensure_ws(c, B, Lmax) || ragged_bufs(c)) return 1;
+    const int64_t n_out_ids = (int64_t)B * cap;
+    if (n_out_ids > c->rag_out_n) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        dfree(c->rag_out);
+        c->rag_out = nullptr;
+        c->rag_out_n = 0;
+        HIP_TRY(hipMalloc(&c->rag_out, (size_t)n_out_ids * 4));
+        c->rag_out_n = n_out_ids;
+    }
+    std::vector<int32_t> stops;  // an id outside the vocabulary is never emitted
+    for (int i = 0; i < n_stop; ++i)
+        if (stop_ids[i] >= 0 && stop_ids[i] < c->d.vocab_size) stops.push_back((int32_t)stop_ids[i]);
+    if ((int64_t)stops.size() > c->rag_stop_n) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        dfree(c->rag_stop);
+        c->rag_stop = nullptr;
+        c->rag_stop_n = 0;
+        HIP_TRY(hipMalloc(&c->rag_stop, stops.size() * 4));
+        c->rag_stop_n = (int64_t)stops.size();
+    }
+    if (!stops.empty()) {  // (every earlier call ended with the stream idle: nothing reads the old list)
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(hipMemcpy(c->rag_stop, stops.data(), stops.size() * 4, hipMemcpyHostToDevice));
+    }
+    HIP_TRY(hipMemsetAsync(c->rag_out, 0xFF, (size_t)n_out_ids * 4, c->stream));  // -1
+    if (ragged_prefill(c, ids_host, lens, B, Lmax, max_new_tokens)) return 1;
+    RaggedState st{};
+    st.pos = rag_word(c, RAG_POS); st.cur_id = rag_word(c, RAG_CUR); st.finished = rag_word(c, RAG_FIN);
+    st.n_out = rag_word(c, RAG_NOUT); st.len = rag_word(c, RAG_LEN); st.budget = rag_word(c, RAG_BUDGET);
+    st.out = c->rag_out; st.cap = cap;
+    st.stop = c->rag_stop; st.n_stop = (int)stops.size();
+    st.live = c->rag_state + (int64_t)l3_ctx::RAG_WORDS * c->d.max_batch_size;
+    if (ragged_choose(c, st, B)) return 1;  // each row's first token, from its position lens[b] - 1
+    for (int i = 1; i < cap; ++i) {
+        if (ragged_step(c, B, s_cap) || ragged_choose(c, st, B)) return 1;
+        // with stop ids the rows may all be finished early: a 4-byte read every 8 steps
+        if (st.n_stop > 0 && i % 8 == 0 && i + 1 < cap) {
+            int32_t live = 1;
+            HIP_TRY(hipMemcpyAsync(&live, st.live, 4, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            if (live == 0) break;
+        }
+    }
+    std::vector<int32_t> all((size_t)n_out_ids), n_out((size_t)B);
+    HIP_TRY(hipMemcpyAsync(all.data(), c->rag_out, all.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(n_out.data(), st.n_out, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int64_t i = 0; i < n_out_ids; ++i) out_ids_host[i] = all[(size_t)i];
+    for (int b = 0; b < B; ++b) out_lens[b] = n_out[(size_t)b];
+    return 0;
+}
+
 extern "C" int l3_layer_forward_host(l3_ctx* c, int32_t layer, const float* x_host, int32_t B,
                                      int32_t L, int32_t start_pos, float* out_host) {
     CHECK_CTX(c);
@@ -2300,6 +2535,7 @@ extern "C" int l3_device_check_counts(l3_ctx* c, uint32_t* counts, int32_t* enab
     HIP_TRY(dcheck_collect_sample(n));
     HIP_TRY(dcheck_collect_score(n));
     HIP_TRY(dcheck_collect_persist(n));
+    HIP_TRY(dcheck_collect_ragged(n));
     for (int i = 0; i < CHK_N; ++i) counts[i] = n[i];
     return 0;
 }

@@ -66,6 +66,8 @@ _SIGNATURES = {
     "l3_layer_forward_host": (ctypes.c_int, [_P, _I32, _P, _I32, _I32, _I32, _P]),
     "l3_greedy_generate_host": (ctypes.c_int, [_P, _P, _I32, _I32, _I32, _P]),
     "l3_greedy_generate_values_host": (ctypes.c_int, [_P, _P, _I32, _I32, _I32, _P, _P]),
+    "l3_ragged_forward_host": (ctypes.c_int, [_P, _P, _P, _I32, _I32, _P]),
+    "l3_ragged_generate_host": (ctypes.c_int, [_P, _P, _P, _I32, _I32, _I32, _P, _I32, _P, _P]),
     "l3_attention_forward_host": (ctypes.c_int, [_P, _I32, _P, _I32, _I32, _I32, _P]),
     "l3_op_softmax_host": (ctypes.c_int, [_P, _P, _I64, _I64, _P]),
     "l3_op_argmax_host": (ctypes.c_int, [_P, _P, _I64, _I64, _P]),
@@ -368,6 +370,41 @@ class Context:
         vals = np.empty(out.shape, np.float32)
         check(lib().l3_greedy_generate_values_host(self._h, ptr(ids), B, L, max_new_tokens, ptr(out), ptr(vals)))
         return out, vals
+
+    @staticmethod
+    def _ragged_args(ids, lens):
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        lens = np.ascontiguousarray(lens, dtype=np.int32)
+        if ids.ndim != 2 or lens.shape != (ids.shape[0],):
+            raise ValueError(f"ids {ids.shape} must be [B, Lmax] and lens {lens.shape} [B]")
+        return ids, lens
+
+    def ragged_forward(self, ids: np.ndarray, lens) -> np.ndarray:
+        """Prefill of prompts of different lengths (l3_ragged_forward_host): ``ids`` [B, Lmax]
+        right-padded (pad entries are ignored), ``lens`` [B]; float32 [B, VS], row b the logits of
+        its position ``lens[b] - 1``.  Leaves slots ``[lens[b], Lmax)`` of cache row b zero."""
+        ids, lens = self._ragged_args(ids, lens)
+        B, Lmax = ids.shape
+        out = pinned.empty((B, self.dims.vocab_size), np.float32)
+        check(lib().l3_ragged_forward_host(self._h, ptr(ids), ptr(lens), B, Lmax, ptr(out)))
+        return out
+
+    def ragged_generate(self, ids: np.ndarray, lens, max_new_tokens: int, stop_ids=()):
+        """The device-side decode loop over rows of different lengths (l3_ragged_generate_host):
+        (out int64 [B, max_new_tokens - min(lens)], out_lens int32 [B]); row b holds
+        ``out_lens[b]`` tokens — at most ``max_new_tokens - lens[b]``, fewer when it emitted one of
+        ``stop_ids`` (kept as its last token) — and -1 after them.  Sampled when ``set_sampling``
+        is on, with the uniforms of (seed, row, position)."""
+        ids, lens = self._ragged_args(ids, lens)
+        B, Lmax = ids.shape
+        stops = np.ascontiguousarray(list(stop_ids), dtype=np.int64).reshape(-1)
+        cap = max(0, int(max_new_tokens) - int(lens.min())) if B else 0
+        out = np.full((B, cap), -1, np.int64)
+        out_lens = np.zeros(B, np.int32)
+        check(lib().l3_ragged_generate_host(self._h, ptr(ids), ptr(lens), B, Lmax, int(max_new_tokens),
+                                            ptr(stops) if stops.size else None, int(stops.size),
+                                            ptr(out), ptr(out_lens)))
+        return out, out_lens
 
     def layer_forward(self, layer: int, x: np.ndarray, start_pos: int) -> np.ndarray:
         x = np.ascontiguousarray(x, dtype=np.float32)

@@ -444,6 +444,39 @@ class Llama:
         return out
 
 
+    def _ragged(self, prompts):
+        """``prompts`` (a sequence of id sequences) right-padded to int64 [B, Lmax], and their
+        lengths; an empty prompt keeps length 0 for the library to refuse."""
+        if self._group is not None and self._group.n > 1:
+            raise NotImplementedError("ragged batches on a multi-device model: not implemented")
+        rows = [np.asarray(p, dtype=np.int64).reshape(-1) for p in prompts]
+        lens = np.array([r.size for r in rows], np.int32)
+        ids = np.zeros((len(rows), int(lens.max()) if len(rows) else 0), np.int64)
+        for b, r in enumerate(rows):
+            ids[b, :r.size] = r
+        return ids, lens
+
+    def forward_ragged(self, prompts) -> np.ndarray:
+        """Extension (DESIGN.md "Ragged batches"): ``__call__`` at position 0 for prompts of
+        different lengths in one batch.  Returns float32 ``[B, 1, VS]``: row b holds the logits
+        of its own last token, as ``model(prompts[b][None], 0)`` gives on a zeroed cache.  Not for
+        a model on more than one device."""
+        ids, lens = self._ragged(prompts)
+        return self._ctx.ragged_forward(ids, lens)[:, None, :]
+
+    def generate_ragged(self, prompts, max_new_tokens: int, stop_ids=()):
+        """Extension (DESIGN.md "Ragged batches"): ``generate_all`` for prompts of different
+        lengths, as one device-side loop.  Returns one int64 array per row: what ``generate``
+        yields for that row alone on a zeroed cache (the reference's schedule, decode hole
+        included) — ``max_new_tokens - len(prompts[b])`` ids, or fewer when the row emitted one of
+        ``stop_ids``, which ends the row and stays its last id.  After ``set_sampling`` the ids
+        are sampled with the uniforms of (seed, row, position), so rows of equal length give
+        ``generate_all``'s ids.  Not for a model on more than one device."""
+        ids, lens = self._ragged(prompts)
+        out, n = self._ctx.ragged_generate(ids, lens, int(max_new_tokens), stop_ids)
+        return [out[b, :n[b]].copy() for b in range(len(n))]
+
+
 def main(argv=None, tokenizer_path="./tokenizer.model.np", model_path="./stories15M.model.npz"):
     """CLI of reference llama3.py:324-349: stream greedy tokens for a prompt, stop on
     EOS/BOS, then print the reference's counter line (prompt + generated tokens
