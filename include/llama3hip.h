@@ -65,10 +65,13 @@ enum l3_weight_kind {
 
 /* Kernel ids for l3_kernel_stats (per-kind HIP-event timing).  L3_K_EMBED counts nothing
  * since layer 0 gathers its input rows from the embedding table (llama3.py:287 fused into
- * its QKV and O-proj launches); the id is kept so the numbering stays stable. */
+ * its QKV and O-proj launches); the id is kept so the numbering stays stable.
+ * L3_K_EMBED_QKV counts the table lookups that stand in for layer 0's QKV GEMM
+ * (l3_set_embed_qkv), so L3_K_QKV stays the GEMM launches' alone. */
 enum l3_kernel_id {
     L3_K_EMBED = 0, L3_K_QKV = 1, L3_K_ATTN = 2, L3_K_OPROJ = 3, L3_K_GATEUP = 4,
-    L3_K_DOWN = 5, L3_K_LMHEAD = 6, L3_K_ARGMAX = 7, L3_K_GATHER = 8, L3_K_COUNT = 9
+    L3_K_DOWN = 5, L3_K_LMHEAD = 6, L3_K_ARGMAX = 7, L3_K_GATHER = 8, L3_K_EMBED_QKV = 9,
+    L3_K_COUNT = 10
 };
 
 /* ---- errors / devices ---------------------------------------------------- */
@@ -131,8 +134,23 @@ int l3_set_last_layer_rows(l3_ctx* ctx, int32_t all_rows);
  * below the fp32 MFMA kernel's, tools/gemm_tune x6acc) — with 1.5x the layer weights' memory for
  * the pieces, made now (or at l3_finalize).  Results round differently from the fp32 MFMA path
  * (not bit-identical to it); batch-1 / batched decode (<= 256 rows), the lm_head and the
- * attention keep their fp32 kernels.  on == 0 frees the pieces. */
+ * attention keep their fp32 kernels.  Layer 0's QKV is among the x6 GEMMs: while x6 is on it
+ * stays a GEMM, and the table lookup of l3_set_embed_qkv (built from the fp32 kernel) is not
+ * used.  on == 0 frees the pieces. */
 int l3_set_gemm_x6(l3_ctx* ctx, int32_t on);
+/* Layer 0's QKV of a prefill as a table lookup (extension; default on, env L3_EMBED_QKV=0 turns
+ * it off for new contexts).  Layer 0's QKV rows before RoPE depend on the token id and the weights
+ * only, and the weights are fixed after l3_finalize, so a table [vocab_size, (H + 2 KVH) * HD] fp32
+ * of them — built once per context by the fp32 QKV kernel itself, at the first call that uses
+ * it — replaces that GEMM by a gather + RoPE + q store / K, V append wherever the GEMM would have
+ * run as the tiled fp32 kernel on embedding rows: a model forward, score or ragged prefill of more
+ * than 256 rows per batch part (B*L), outside captured decode steps and with l3_set_gemm_x6 off.
+ * Logits, q and every K / V slot are bit-identical to the GEMM's.  The table is built only when
+ * its bytes are at most max_bytes (default 256 MB; max_bytes <= 0 keeps the current limit) and
+ * the allocation succeeds; otherwise, and for every other shape, the GEMM runs as before.
+ * on == 0, or a limit below an existing table's size, frees the table.  Its launches count under
+ * L3_K_EMBED_QKV. */
+int l3_set_embed_qkv(l3_ctx* ctx, int32_t on, int64_t max_bytes);
 /* Same with device-resident ids (int32 [B, L]) and logits ([B, VS]); async. */
 int l3_forward_dev(l3_ctx* ctx, const int32_t* ids_dev, int32_t B, int32_t L,
                    int32_t start_pos, float* logits_dev);

@@ -4,6 +4,7 @@
 
 #include "gemm_kernel.h"
 #include "gemm_x6.h"
+#include "embed_qkv.h"
 
 namespace l3 {
 
@@ -355,6 +356,34 @@ hipError_t launch_gemm(int epi, const GemmArgs& a, hipStream_t s) {
         default:
             return hipErrorInvalidValue;
     }
+}
+
+// The layer-0 QKV table (embed_qkv.h): the tile choice of the fp32 EPI_QKV launch above for this N
+// and K past 32 rows, so every entry went through that launch's MFMA chain and row factor
+hipError_t launch_qkv_table(const GemmArgs& a, hipStream_t s) {
+    if (a.M <= 0 || a.N <= 0) return hipSuccess;
+    if (a.K % 32 != 0 || a.K <= 0 || a.N % 4 != 0 || a.ldc % 4 != 0 || a.lda % 4 != 0 || a.a_rows || a.col_base || !a.C)
+        return hipErrorInvalidValue;
+    if (a.N % 96 == 0 && a.K <= 1024) return launch<EPI_QKV_TABLE, 2, 2, 4, 3, 4, 16>(a, s);
+    return launch<EPI_QKV_TABLE, 2, 2, 4, 4, 3, 16>(a, s);
+}
+
+template <int CPB>
+static hipError_t launch_embed_qkv_cpb(const EmbedQkvArgs& a, int nq, hipStream_t s) {
+    constexpr int rows = 256 / CPB * EQ_ROWS;
+    const dim3 grid((unsigned)(((int64_t)a.T + rows - 1) / rows), (unsigned)((nq + CPB - 1) / CPB));
+    hipLaunchKernelGGL(embed_qkv_kernel<CPB>, grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// a narrow row (few float4 columns) puts several row groups side by side in a block
+hipError_t launch_embed_qkv(const EmbedQkvArgs& a, hipStream_t s) {
+    if (a.T <= 0) return hipSuccess;
+    if (a.L <= 0 || a.HD % 4 != 0 || a.HD <= 0) return hipErrorInvalidValue;
+    const int nq = (a.H + 2 * a.KVH) * a.HD / 4;
+    if (nq <= 64) return launch_embed_qkv_cpb<64>(a, nq, s);
+    if (nq <= 128) return launch_embed_qkv_cpb<128>(a, nq, s);
+    return launch_embed_qkv_cpb<256>(a, nq, s);
 }
 
 hipError_t dcheck_collect_gemm(unsigned* out) { return dcheck_collect(out); }

@@ -237,6 +237,29 @@ __device__ __forceinline__ void qkv_epilogue_full(const GemmArgs& p, const f32x4
     }
 }
 
+// EPI_QKV_TABLE: the value the QKV epilogues above hold just before the rotation — the same
+// expression — stored row-major at C[row][col] (the layer-0 table, embed_qkv.h; col_base is 0).
+// Rows and columns past the edge are skipped: the table's row count is the vocabulary's
+template <int TM, int TN>
+__device__ __forceinline__ void qkv_table_epilogue(const GemmArgs& p, const f32x4 (&acc)[TM][TN],
+                                                   const float (&rs)[TM], int mrow0, int ncol0, int lane) {
+    const int frow = lane & 15, fq4 = 4 * (lane >> 4);
+    const int qdim = p.H * p.HD;
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+        const int row = mrow0 + i * 16 + frow;
+        if (row >= p.M) continue;
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+            const int col = ncol0 + j * 16 + fq4;
+            if (col >= p.N) continue;
+            const int sec = col < qdim ? 0 : 1;
+            const f32x4 v = acc[i][j] * (sec == 0 ? rs[i] * p.q_scale : rs[i]);
+            *reinterpret_cast<f32x4*>(p.C + (int64_t)row * p.ldc + col) = v;
+        }
+    }
+}
+
 // Register-direct epilogue (EPI_STORE / EPI_RESID / EPI_SWIGLU).  The MFMA operands are swapped
 // (W fragment as the A operand, activation fragment as B), so the accumulator of tile (i, j) is C^T: lane l
 // holds C[row = 16i + (l&15)][col = 16j + 4(l>>4) + r], r = 0..3 — four consecutive columns
@@ -750,6 +773,7 @@ __global__ void __launch_bounds__(64 * WM * WN, WAVES_PER_EU) gemm_lds_kernel(Ge
         else
             qkv_epilogue<TM, TN>(p, acc, rs, m0 + arow0, n0 + brow0, lane);
     }
+    else if constexpr (EPI == EPI_QKV_TABLE) qkv_table_epilogue<TM, TN>(p, acc, rs, m0 + arow0, n0 + brow0, lane);
     else direct_epilogue<TM, TN, EPI, RES_PREFETCH>(p, acc, rs, res, m0 + arow0, n0 + brow0, lane);
     L3_STAMP(3);
     if constexpr (STAMP) {

@@ -11,7 +11,8 @@ namespace l3 {
 //   runtime.hip  L3_BATCH_SPLIT (2), L3_LAST_LAYER_ALL_ROWS (0), L3_DECODE_FUSE_O (1),
 //                L3_LM_AMAX (1), L3_DECODE_FOLD_ARGMAX (1), L3_DECODE_SPECULATE (1), L3_DECODE_GRAPH_STEPS (8),
 //                L3_DECODE_GRAPH (1), L3_COMM_MODE (1), L3_COMM_PRIORITY (1), L3_GROUP_MULTI_PATH (0),
-//                L3_DECODE_PERSIST (1 persistent step; 0 graph), L3_DECODE_ROWS_AMAX (1)
+//                L3_DECODE_PERSIST (1 persistent step; 0 graph), L3_DECODE_ROWS_AMAX (1),
+//                L3_EMBED_QKV (1 layer-0 QKV of a prefill from the table; 0 its GEMM)
 //   test knobs   L3_DECODE_PERSIST_MAX_CUS (cap the CUs the persistent step sees), L3_DECODE_PERSIST_FAULT
 //                (a workgroup gives up in the step at that position; L3_DECODE_PERSIST_FAULT_WG which),
 //                L3_GROUP_VIRTUAL (a group's members may share one device; D2D copies for the gather),
@@ -60,6 +61,8 @@ enum Epilogue : int {
     EPI_RESID = 1,   // C += acc                        (O-proj / down-proj + residual)
     EPI_SWIGLU = 2,  // C[:, j] = silu(s*g_j) * (s*u_j) (gate/up interleaved by 16 rows)
     EPI_QKV = 3,     // s_row * acc -> RoPE(q,k) -> q buffer + KV cache append
+    EPI_QKV_TABLE = 4,  // C = s_row * acc (* q_scale on the q columns): EPI_QKV's values just before
+                        // the rotation, row-major (the layer-0 table of embed_qkv.h)
 };
 
 struct ArgmaxPart {
@@ -476,6 +479,25 @@ int decode_persist_grid(const DecodePersistArgs& a);
 hipError_t launch_decode_persist(const DecodePersistArgs& a, int grid, hipStream_t s);
 
 hipError_t launch_gemm(int epi, const GemmArgs& a, hipStream_t s);
+
+// Layer 0's QKV as a table lookup (embed_qkv.h; DESIGN.md "Layer-0 QKV table"): row r of that
+// GEMM before the rotation depends on the token id and the weights only, so a prefill gathers it
+// from table[id] instead of multiplying
+struct EmbedQkvArgs {
+    const float* table;            // [VS, (H + 2 KVH) * HD]: launch_qkv_table's output
+    const int32_t* ids;            // [T] token ids
+    float* q_out;                  // [T, H*HD]
+    float* cache_k; float* cache_v;// [maxB, KVH, Smax, HD], at the launch's first batch row
+    const float* rope_cos; const float* rope_sin;  // [Smax, HD/2]
+    int T, L, start_pos, H, KVH, HD, Smax, VS;
+};
+// the table: a.A = the embedding [a.M = VS, K], a.W = layer 0's folded wqkv, a.C [VS, a.N] (ldc),
+// norm / eps / q_scale / H / KVH / HD as the EPI_QKV launch's; the tile, BK and K order of the
+// tiled fp32 EPI_QKV launch of that N and K, so each entry is bit for bit what that launch holds
+// for a row of this id just before its rotation
+hipError_t launch_qkv_table(const GemmArgs& a, hipStream_t s);
+// gather -> RoPE -> q store and K / V append for T rows
+hipError_t launch_embed_qkv(const EmbedQkvArgs& a, hipStream_t s);
 // W [rows][K] fp32 -> W3 [rows][3][K] bf16 pieces for the x6 path (gemm_x6.h)
 hipError_t launch_split_planes(const float* w, unsigned short* w3, int64_t rows, int K, hipStream_t s);
 hipError_t launch_attention(const AttnArgs& a, hipStream_t s);

@@ -101,6 +101,14 @@ struct l3_ctx {
     hipEvent_t lag_ev[MAX_PARTS - 1] = {};
     int split = 2;                   // parts (1 = off); l3_set_batch_split, L3_BATCH_SPLIT
     bool gemm_x6 = false;            // prefill GEMMs on the x6 path (l3_set_gemm_x6, L3_GEMM_X6)
+    // layer 0's QKV of a prefill as a lookup in a table of its pre-RoPE rows per token id
+    // (embed_qkv.h, l3_set_embed_qkv, L3_EMBED_QKV): built at the first call that qualifies, on
+    // stream, if its bytes fit embed_qkv_cap; a refused allocation is not retried
+    static constexpr int64_t EMBED_QKV_CAP_DEFAULT = (int64_t)256 << 20;
+    bool embed_qkv = true;
+    int64_t embed_qkv_cap = EMBED_QKV_CAP_DEFAULT;
+    float* embed_tab = nullptr;      // [vocab_size, qkvn]
+    bool embed_tab_failed = false;
     bool prune_last = true;          // last layer: attention / O-proj / FFN on the last rows only
                                      // (l3_set_last_layer_rows, L3_LAST_LAYER_ALL_ROWS)
     int64_t split_min_tokens = 8192; // a part must hold at least this many tokens
@@ -379,7 +387,7 @@ extern "C" const char* l3_last_error(void) { return g_err.c_str(); }
 
 extern "C" int l3_version(int32_t* major, int32_t* minor) {
     if (major) *major = 0;
-    if (minor) *minor = 15;
+    if (minor) *minor = 16;
     return 0;
 }
 
@@ -446,6 +454,7 @@ extern "C" int l3_create(int32_t device, const l3_dims* dims, l3_ctx** out) {
     c->d = d;
     c->prune_last = env_knob("L3_LAST_LAYER_ALL_ROWS", 0) == 0;
     c->gemm_x6 = env_knob("L3_GEMM_X6", 0) != 0;
+    c->embed_qkv = env_knob("L3_EMBED_QKV", 1) != 0;
     {  // batch-split default for new contexts
         const int n = env_knob("L3_BATCH_SPLIT", c->split);
         c->split = n < 1 ? 1 : n > l3_ctx::MAX_PARTS ? l3_ctx::MAX_PARTS : n;
@@ -517,7 +526,7 @@ extern "C" int l3_destroy(l3_ctx* c) {
     dfree(c->emb); dfree(c->lm_head); dfree(c->final_norm); dfree(c->rope_cos); dfree(c->rope_sin);
     dfree(c->h); dfree(c->q); dfree(c->attn); dfree(c->hid); dfree(c->logits); dfree(c->ids);
     dfree(c->oparts); dfree(c->amax_part); dfree(c->hsum); dfree(c->skws); dfree(c->amax_rows);
-    dfree(c->amax); dfree(c->gather_ids);
+    dfree(c->amax); dfree(c->gather_ids); dfree(c->embed_tab);
     if (c->ids_pin) (void)hipHostFree(c->ids_pin);
     for (void* p : c->scratch) dfree(p);
     for (auto& t : c->timers) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
@@ -688,6 +697,56 @@ extern "C" int l3_set_gemm_x6(l3_ctx* c, int32_t on) {
     return 0;
 }
 
+// q is stored pre-scaled by log2(e) / sqrt(HD) (the attention's exp2 softmax)
+static float qkv_q_scale(const l3_ctx* c) { return (float)(1.4426950408889634 / std::sqrt((double)c->HD)); }
+
+// The layer-0 QKV table (embed_qkv.h): true when it exists.  may_build: make it now, on c->stream
+// (the caller's launches are ordered after c->stream: run_layer on it, forward_dev before its
+// fork event).  It is a function of the finalized weights alone, so it stays valid for the
+// context's life; too large for the cap or refused by the allocator: false, the GEMM path stays
+static bool embed_table(l3_ctx* c, bool may_build) {
+    if (c->embed_tab) return true;
+    if (!may_build || c->embed_tab_failed || !c->finalized || !c->emb || c->layers.empty() ||
+        !c->layers[0].folded_qkv)
+        return false;
+    const int64_t VS = c->d.vocab_size, bytes = VS * c->qkvn * 4;
+    if (VS <= 0 || bytes > c->embed_qkv_cap) return false;
+    float* tab = nullptr;
+    if (hipMalloc(&tab, (size_t)bytes) != hipSuccess) {
+        (void)hipGetLastError();  // clear the sticky error: the next launch check must not see it
+        c->embed_tab_failed = true;
+        return false;
+    }
+    GemmArgs t{};
+    t.A = c->emb; t.lda = c->d.dim; t.W = c->layers[0].wqkv; t.C = tab; t.ldc = c->qkvn;
+    t.M = (int)VS; t.N = c->qkvn; t.K = c->d.dim; t.norm = true; t.eps = c->d.norm_eps;
+    t.H = c->d.n_heads; t.KVH = c->d.n_kv_heads; t.HD = c->HD; t.q_scale = qkv_q_scale(c);
+    if (launch_qkv_table(t, c->stream) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(tab);
+        c->embed_tab_failed = true;
+        return false;
+    }
+    c->embed_tab = tab;
+    return true;
+}
+
+// the launches that read the table are all ordered before the end of c->stream's queue (a batch
+// split's parts are joined there), so the table is freed after a synchronize
+extern "C" int l3_set_embed_qkv(l3_ctx* c, int32_t on, int64_t max_bytes) {
+    CHECK_CTX(c);
+    if (set_dev(c)) return 1;
+    c->embed_qkv = on != 0;
+    if (max_bytes > 0) c->embed_qkv_cap = max_bytes;
+    c->embed_tab_failed = false;
+    if (c->embed_tab && (!c->embed_qkv || (int64_t)c->d.vocab_size * c->qkvn * 4 > c->embed_qkv_cap)) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        dfree(c->embed_tab);
+        c->embed_tab = nullptr;
+    }
+    return 0;
+}
+
 extern "C" int l3_finalize(l3_ctx* c) {
     CHECK_CTX(c);
     if (c->finalized) return 0;
@@ -807,7 +866,7 @@ static int run_layer(l3_ctx* c, int li, int B, int L, int start_pos, const int* 
     g.L = L; g.start_pos = start_pos; g.H = c->d.n_heads; g.KVH = c->d.n_kv_heads; g.HD = c->HD;
     g.Smax = c->d.max_seq_len;
     g.pos_dev = pos_dev;
-    g.q_scale = (float)(1.4426950408889634 / std::sqrt((double)c->HD));
+    g.q_scale = qkv_q_scale(c);
     if (emb_ids) { g.A = c->emb; g.a_rows = emb_ids; }
     if (emb_ids && c->fold_in) {  // the id comes from the previous step's lm_head partials
         g.a_rows = nullptr;
@@ -828,7 +887,19 @@ static int run_layer(l3_ctx* c, int li, int B, int L, int start_pos, const int* 
         g.W = Ly.wqkv + (int64_t)c->qdim * D; g.N = 2 * c->kvdim; g.col_base = c->qdim;
         if (g.W3) g.W3 += (int64_t)c->qdim * 3 * D;
     }
-    if (timed_on(c, L3_K_QKV, s, [&] { return launch_gemm(EPI_QKV, g, s); })) return 1;
+    // Layer 0 on embedding rows, exactly where launch_gemm would reach the tiled fp32 kernel with
+    // a_rows set (more than 256 rows: past the GEMV, the skinny kernel and split-K, which round
+    // differently; no device-side position, argmax fold or undo slots, i.e. no captured decode
+    // step; x6 off): the rows come from the table instead, bit for bit (embed_qkv.h)
+    if (emb_ids && c->embed_qkv && T > 256 && !pos_dev && !c->fold_in && !g.kv_bak && !g.W3 &&
+        embed_table(c, s == c->stream)) {
+        EmbedQkvArgs e{};
+        e.table = c->embed_tab; e.ids = emb_ids; e.q_out = q; e.cache_k = g.cache_k; e.cache_v = g.cache_v;
+        e.rope_cos = c->rope_cos; e.rope_sin = c->rope_sin;
+        e.T = (int)T; e.L = L; e.start_pos = start_pos; e.H = g.H; e.KVH = g.KVH; e.HD = g.HD; e.Smax = g.Smax;
+        e.VS = c->d.vocab_size;
+        if (timed_on(c, L3_K_EMBED_QKV, s, [&] { return launch_embed_qkv(e, s); })) return 1;
+    } else if (timed_on(c, L3_K_QKV, s, [&] { return launch_gemm(EPI_QKV, g, s); })) return 1;
     if (prune) {
         const int D4 = D;
         float* hl = h + (int64_t)(L - 1) * D4;  // row b's last position: hl + b * L * D
@@ -1000,10 +1071,17 @@ static int forward_dev(l3_ctx* c, const int32_t* ids_dev, int B, int L, int star
     // part's lm_head (the writer of the rows it reads) waits for it below (gather_pending)
     const bool after_gather = c->gather_tail;
     c->gather_tail = false;
+    // the layer-0 QKV table is made on stream before the parts fork (run_layer makes it only there);
+    // the call that makes it forks after it even behind a gather (that one call gives up the overlap)
+    bool tab_new = false;
+    if (ids_dev && c->embed_qkv && !pos_dev && (int64_t)(B / parts) * L > 256 && !c->layers.empty() &&
+        !c->layers[0].wqkv3 && !c->embed_tab)
+        tab_new = embed_table(c, true);
+    const bool fork_early = after_gather && !tab_new;
     if (parts > 1) {  // the aux streams join the work queued so far on stream
-        if (!after_gather) HIP_TRY(hipEventRecord(c->fork_ev, c->stream));
+        if (!fork_early) HIP_TRY(hipEventRecord(c->fork_ev, c->stream));
         for (int p = 1; p < parts; ++p)
-            HIP_TRY(hipStreamWaitEvent(st[p], after_gather ? c->comm_fwd_ev : c->fork_ev, 0));
+            HIP_TRY(hipStreamWaitEvent(st[p], fork_early ? c->comm_fwd_ev : c->fork_ev, 0));
     }
     // the lm_head too runs per part when every part picks the unsplit batch's tile (then each
     // part's lm_head overlaps the other parts' last layer); otherwise once after the join

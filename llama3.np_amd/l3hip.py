@@ -23,7 +23,7 @@ HEADER = os.path.join(os.path.dirname(HERE), "include", "llama3hip.h")
 # weight kinds / kernel ids (mirror the enums in include/llama3hip.h)
 W_EMBED, W_Q, W_K, W_V, W_O, W_GATE, W_UP, W_DOWN = range(8)
 W_ATTN_NORM, W_FFN_NORM, W_FINAL_NORM, W_LM_HEAD = 8, 9, 10, 11
-KERNELS = ["embed", "qkv", "attn", "oproj", "gateup", "down", "lmhead", "argmax", "gather"]
+KERNELS = ["embed", "qkv", "attn", "oproj", "gateup", "down", "lmhead", "argmax", "gather", "embed_qkv"]
 
 
 class Dims(ctypes.Structure):
@@ -88,6 +88,7 @@ _SIGNATURES = {
     "l3_synchronize": (ctypes.c_int, [_P]),
     "l3_set_batch_split": (ctypes.c_int, [_P, _I32, _I64]),
     "l3_set_gemm_x6": (ctypes.c_int, [_P, _I32]),
+    "l3_set_embed_qkv": (ctypes.c_int, [_P, _I32, _I64]),
     "l3_set_last_layer_rows": (ctypes.c_int, [_P, _I32]),
     "l3_kernel_timing": (ctypes.c_int, [_P, _I32]),
     "l3_kernel_stats": (ctypes.c_int, [_P, _P, _P]),
@@ -455,6 +456,12 @@ class Context:
         cut exactly into three bf16 pieces, six bf16 MFMA products per fp32 product (error
         against fp64 at or below the fp32 MFMA kernel's); off (default) frees the pieces."""
         check(lib().l3_set_gemm_x6(self._h, int(bool(on))))
+
+    def set_embed_qkv(self, on: bool, max_bytes: int = 0) -> None:
+        """Extension (l3_set_embed_qkv): layer 0's QKV of a prefill past 256 rows as a lookup in a
+        table of its pre-RoPE rows per token id (bit-identical to the GEMM; on by default).  The
+        table is built at first use if it fits max_bytes (0 keeps the limit, 256 MB by default)."""
+        check(lib().l3_set_embed_qkv(self._h, int(bool(on)), int(max_bytes)))
 
     def synchronize(self) -> None:
         check(lib().l3_synchronize(self._h))
