@@ -134,10 +134,38 @@ int l3_set_last_layer_rows(l3_ctx* ctx, int32_t all_rows);
  * below the fp32 MFMA kernel's, tools/gemm_tune x6acc) — with 1.5x the layer weights' memory for
  * the pieces, made now (or at l3_finalize).  Results round differently from the fp32 MFMA path
  * (not bit-identical to it); batch-1 / batched decode (<= 256 rows), the lm_head and the
- * attention keep their fp32 kernels.  Layer 0's QKV is among the x6 GEMMs: while x6 is on it
+ * attention keep their fp32 kernels (or, for the GEMV launches, the bf16 copies of
+ * l3_set_weight_bf16, which is independent of this setting).  Layer 0's QKV is among the x6 GEMMs: while x6 is on it
  * stays a GEMM, and the table lookup of l3_set_embed_qkv (built from the fp32 kernel) is not
  * used.  on == 0 frees the pieces. */
 int l3_set_gemm_x6(l3_ctx* ctx, int32_t on);
+/* bf16 weight storage for the weight-streaming decode GEMVs (extension; default off, env
+ * L3_WEIGHT_BF16=1|2 sets the mode for new single-device contexts; DESIGN.md "bf16 weight storage").
+ * The reference holds every projection as the fp32 array np.load gives (llama3.py:219-237, 280-281) and
+ * multiplies x @ W.T in that precision (:166-168, :211, :99-102, :304-307); with mode != 0 the context
+ * computes, still in fp32, the model whose q / k / v / o / gate / up / down projections and lm_head
+ * are W_b = bf16(W): round-to-nearest-even on the top 16 bits (a NaN stays a NaN, a value past the
+ * largest bf16 goes to +-inf, subnormals round like any value, -0 is kept).  The embedding and the
+ * RMSNorm weights stay fp32.  l3_finalize makes a bf16 copy of each of those tensors (unfolded, in
+ * the fp32 tensor's row layout, 2 bytes per element beside the 4 of the fp32 tensor), and every
+ * launch that runs on the weight-streaming GEMV — decode and prompts of up to 8 rows — streams
+ * that copy instead of the fp32 tensor and applies the norm weight to the activations; every
+ * other kernel keeps reading the fp32 tensors, which hold the same model:
+ *   mode 1 (exact): every element must already be a bf16 value; otherwise l3_finalize fails,
+ *     naming the first offending tensor (layer, kind) and its count of inexact elements, the
+ *     context stays un-finalized and the mode may be changed before finalizing again.  Results
+ *     equal the fp32 path's to fp32 rounding.
+ *   mode 2 (round): the fp32 tensors are replaced by float(W_b) before the norm fold, so prefill
+ *     and decode agree on one model (which is not the uploaded one).
+ *   mode 0: everything as without this call.
+ * Errors: a mode outside [0, 2]; a call after l3_finalize (the fold has consumed the unfolded
+ * weights); mode != 0 on a member of a multi-device l3_group. */
+int l3_set_weight_bf16(l3_ctx* ctx, int32_t mode);
+/* The mode in force, the bytes of the bf16 copies (0 before l3_finalize and in mode 0) and the
+ * GEMV launches issued on them since l3_create (a captured decode step counts when it is
+ * captured, not per replay); any pointer may be NULL.  No reference counterpart (llama3.py:265-283
+ * keeps one copy of each weight). */
+int l3_weight_bf16_info(l3_ctx* ctx, int32_t* mode, int64_t* bytes, int64_t* gemv_launches);
 /* Layer 0's QKV of a prefill as a table lookup (extension; default on, env L3_EMBED_QKV=0 turns
  * it off for new contexts).  Layer 0's QKV rows before RoPE depend on the token id and the weights
  * only, and the weights are fixed after l3_finalize, so a table [vocab_size, (H + 2 KVH) * HD] fp32
@@ -300,6 +328,18 @@ int l3_op_ffn_host(l3_ctx* ctx, const float* x, int64_t rows, int32_t dim, int32
 /* y [rows, N] = x [rows, K] @ W[N, K]^T (the reference's `x @ W.T`). */
 int l3_op_linear_host(l3_ctx* ctx, const float* x, int64_t rows, int32_t K, int32_t N,
                       const float* w, float* y);
+/* The conversion of l3_set_weight_bf16 on a plain array: out_u16[i] = bf16(x[i]) (the rounding
+ * above; a NaN gives 0x7fc0), *n_inexact (may be NULL) = the elements whose value changed (NaNs
+ * not counted).  The storage format of the reference's `W` (llama3.py:219-237), not an op of it. */
+int l3_op_to_bf16_host(l3_ctx* ctx, const float* x, int64_t n, uint16_t* out_u16, int64_t* n_inexact);
+/* y [rows, N] = s * ((x * g) [rows, K] @ float(w_u16) [N, K]^T) on the bf16-weight GEMV (the
+ * reference's `x @ W.T`, llama3.py:166-168, with W stored as bf16): norm_w = g [K] applies the
+ * RMSNorm of llama3.py:111-114 with eps (s = 1 / sqrt(mean(x^2) + eps) per row, of x itself);
+ * NULL: g = 1, s = 1.  rows in [1, 8], K % 32 == 0, N % 4 == 0; rows whose K does not fit one
+ * launch's 64 KB of staged rows run as several launches (K <= 16384).  Any other shape is an
+ * error: no other kernel stands in. */
+int l3_op_linear_bf16_host(l3_ctx* ctx, const float* x, int64_t rows, int32_t K, int32_t N,
+                           const uint16_t* w_u16, const float* norm_w, float eps, float* y);
 /* The scoring path of l3_score_host (llama3.py:285-308 with the logits reduced in the lm_head's
  * epilogue) on a plain product: for z = x [rows, K] @ W[N, K]^T (no norm) and targets int32 [rows]
  * (-1: no target; else in [0, N)), logprob [rows], and optionally lse [rows] and argmax int32

@@ -93,23 +93,31 @@ static hipError_t launch_gemv_lpu(const GemmArgs& a, hipStream_t s) {
     const int per_block = 4 * (64 / LPU);
     const dim3 grid((unsigned)((units + per_block - 1) / per_block), (unsigned)((a.M + MR - 1) / MR)),
         block(256);
-    hipLaunchKernelGGL((gemv_kernel<EPI, MR, LPU, PARTS, NT, FOLD>), grid, block, MR == 1 ? 0 : (size_t)MR * a.K * 4, s, a);
+    // GemmArgs::Wb (bf16 weight storage): the same grid on the bf16-weight form
+    if (a.Wb)
+        hipLaunchKernelGGL((gemv_kernel<EPI, MR, LPU, PARTS, NT, FOLD, true>), grid, block, MR == 1 ? 0 : (size_t)MR * a.K * 4, s, a);
+    else
+        hipLaunchKernelGGL((gemv_kernel<EPI, MR, LPU, PARTS, NT, FOLD>), grid, block, MR == 1 ? 0 : (size_t)MR * a.K * 4, s, a);
     return hipGetLastError();
 }
 
 // non-temporal W loads for the one-row GEMV over a weight larger than the caches would keep
-// (>= 64 MB: the Llama-3-shape decode; gemv_kernel NT); L3_GEMV_NT=0 turns them off (A/B)
+// (>= 64 MB — of the copy that is streamed: fp32, or bf16 with GemmArgs::Wb; the Llama-3-shape
+// decode; gemv_kernel NT); L3_GEMV_NT=0 turns them off (A/B)
 static bool gemv_nt(const GemmArgs& a) {
     static const int on = env_knob("L3_GEMV_NT", 1);
-    return on && (int64_t)a.N * a.K * 4 >= ((int64_t)64 << 20);
+    return on && (int64_t)a.N * a.K * (a.Wb ? 2 : 4) >= ((int64_t)64 << 20);
 }
+
+// 16-byte pieces of a W row: float4, or eight bf16 with GemmArgs::Wb
+static int gemv_pieces(const GemmArgs& a) { return a.Wb ? a.K / 8 : a.K / 4; }
 
 // the O-proj partial rows of the fused decode attention (GemmArgs::parts): EPI_SWIGLU carries
 // GEMV_MAXP partial loads per piece, so its lanes take fewer pieces (<= 4 up to K = 1024)
 template <int EPI>
 static hipError_t launch_gemv_parts(const GemmArgs& a, hipStream_t s) {
     if (a.nparts < 1 || a.nparts > GEMV_MAXP || !gemv_direct(a)) return hipErrorInvalidValue;
-    const int k4 = a.K / 4;
+    const int k4 = gemv_pieces(a);
     if constexpr (EPI == EPI_SWIGLU) {
         if (k4 <= 128) return launch_gemv_lpu<EPI, 1, 32, true>(a, s);
     } else {
@@ -120,12 +128,13 @@ static hipError_t launch_gemv_parts(const GemmArgs& a, hipStream_t s) {
     return launch_gemv_lpu<EPI, 1, 64, true>(a, s);
 }
 
-// lanes per unit from K: ~5-8 float4 per lane per W row in one chunk at the stories15M sizes;
+// lanes per unit from K: ~5-8 float4 per lane per W row in one chunk at the stories15M sizes
+// (with GemmArgs::Wb from the count of its 16-byte pieces, eight k each);
 // L3_GEMV_LPU=16/32/64 forces it (A/B tuning of the decode GEMVs)
 static int gemv_lpu(const GemmArgs& a) {
     static const int force = env_knob("L3_GEMV_LPU", 0);
     if (force == 16 || force == 32 || force == 64) return force;
-    const int k4 = a.K / 4;
+    const int k4 = gemv_pieces(a);
     return k4 <= 128 ? 16 : k4 <= 256 ? 32 : 64;
 }
 
@@ -226,7 +235,24 @@ int gemm_store_config(const GemmArgs& a) {
     return a.M <= 32 ? 1 : a.M <= 64 ? 2 : 3;
 }
 
-hipError_t launch_gemm(int epi, const GemmArgs& a, hipStream_t s) {
+// GemmArgs::Wb is used exactly where the launch goes to gemv_kernel: the fused-O-proj parts, the
+// folded-argmax QKV and the plain GEMV range (the dispatch order of launch_gemm below); every other
+// kernel reads the fp32 W, which holds the same model (runtime.hip finalize_bf16)
+bool gemm_takes_bf16(int epi, const GemmArgs& a) {
+    if (!a.Wb || a.M <= 0 || a.N <= 0) return false;
+    if (a.parts) return epi == EPI_SWIGLU || epi == EPI_RESID;
+    if (a.amax_in) return true;
+    if (a.force_skinny || a.force_tiled) return false;
+    return gemm_is_gemv(a) && !use_skinny(a);
+}
+
+hipError_t launch_gemm(int epi, const GemmArgs& a_in, hipStream_t s) {
+    GemmArgs a_own;
+    if (a_in.Wb && !gemm_takes_bf16(epi, a_in)) {  // not a GEMV launch: the fp32 kernels, as without Wb
+        a_own = a_in;
+        a_own.Wb = nullptr;
+    }
+    const GemmArgs& a = a_in.Wb && !gemm_takes_bf16(epi, a_in) ? a_own : a_in;
     if (a.M <= 0 || a.N <= 0) return hipSuccess;
     if (a.K % 32 != 0 || a.K <= 0) return hipErrorInvalidValue;  // whole 32-deep k-tiles
     if (epi == EPI_SWIGLU && a.N % 32 != 0) return hipErrorInvalidValue;

@@ -40,6 +40,7 @@
 namespace l3 {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 // silu (llama3.py:27-28) with v_rcp_f32 (1 ulp) instead of the IEEE division sequence: the
 // SwiGLU epilogue's VALU share drops, gate|up 123.5 -> 126.4 TF/s (tools/gemm_tune A/B)
@@ -941,17 +942,36 @@ __global__ void __launch_bounds__(64 * NW) gemm_skinny_kernel(GemmArgs p) {
 // launch of its own — every block reduces that step's lm_head partials (GemmArgs::amax_in, a few
 // KB from L2, loaded beside the W pieces) to the id whose embedding row is this step's input
 // (:287); block 0 publishes the id (amax_ids, amax_st's history).
-template <int EPI, int MR, int LPU, bool PARTS = false, bool NT = false, bool FOLD = false>
+//
+// WB (opt-in bf16 weight storage, GemmArgs::Wb; DESIGN.md "bf16 weight storage"): the W pieces are
+// 16 bytes of bf16, eight k each (lane j streams piece k8 = j + LPU t, as many pieces per round
+// trip as the fp32 form: half the bytes per dot product), unpacked with integer ops (u << 16,
+// u & 0xffff0000: a bf16 is the top half of an fp32) and multiplied in fp32 in a fixed k order.
+// Wb is NOT norm-folded (rounding W * w_norm would change a bf16-exact checkpoint), so on the norm
+// GEMVs the norm weight g = GemmArgs::norm_w goes into the activations: x * g once per piece — in
+// registers in the one-row form (g loaded beside x in the same round trip), while staging x into
+// LDS in the row-blocked forms, which therefore take the rows' sums of squares (of raw x) from the
+// staging pass.  Each piece takes two float4 of x (XN); everything else is the fp32 form's.
+// unpack a 32-bit pair of bf16: element 2i in the low half, 2i + 1 in the high half
+__device__ __forceinline__ float bf16_lo(unsigned u) { return __uint_as_float(u << 16); }
+__device__ __forceinline__ float bf16_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
+
+template <int EPI, int MR, int LPU, bool PARTS = false, bool NT = false, bool FOLD = false, bool WB = false>
 __global__ void __launch_bounds__(256) gemv_kernel(GemmArgs p) {
     extern __shared__ __attribute__((aligned(16))) float xs[];  // [MR][K]
     static_assert(!PARTS || MR == 1, "partial rows only on the one-row GEMV");
     static_assert(!FOLD || (MR == 1 && EPI == EPI_QKV && !PARTS), "the folded argmax feeds a one-row QKV");
     constexpr int ROWS = (EPI == EPI_SWIGLU || EPI == EPI_QKV) ? 2 : 1;
     constexpr int UPW = 64 / LPU;  // units per wave
-    constexpr int CH = PARTS ? 4 : 8;  // float4 per W row per lane in flight
     constexpr bool XPARTS = PARTS && EPI == EPI_SWIGLU;
+    // 16-byte pieces per W row per lane in flight (WB with partial rows on x: two float4 of each
+    // partial row per piece, so half the pieces keep the fp32 form's registers)
+    constexpr int CH = PARTS ? (WB && XPARTS ? 2 : 4) : 8;
+    constexpr int XN = WB ? 2 : 1;     // float4 of x per W piece
+    constexpr bool GN = WB && EPI != EPI_RESID;  // the norm weight may ride on x (p.norm_w)
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int K4 = p.K >> 2;
+    const int KP = WB ? p.K >> 3 : K4;  // pieces per W row
     const int j = lane % LPU;
     const int unit = (blockIdx.x * 4 + wid) * UPW + lane / LPU;
     const int nunits = ROWS == 2 ? p.N / 2 : p.N;
@@ -968,6 +988,9 @@ __global__ void __launch_bounds__(256) gemv_kernel(GemmArgs p) {
         wrow[0] = u;
     }
     const f32x4* W4 = reinterpret_cast<const f32x4*>(p.W);
+    const u32x4* WB4 = reinterpret_cast<const u32x4*>(p.Wb);
+    const f32x4* G4 = reinterpret_cast<const f32x4*>(p.norm_w);
+    const bool gn = GN && p.norm_w != nullptr;  // launch-uniform
     // row block: rows [m0, m0 + Mb) of A (grid.y row blocks of MR rows re-read W through L2)
     const int m0 = blockIdx.y * MR, Mb = min(MR, p.M - m0);
     // MR == 1 (batch-1 decode): each lane loads its own float4s of the input row next to its W
@@ -975,9 +998,11 @@ __global__ void __launch_bounds__(256) gemv_kernel(GemmArgs p) {
     // the rows once in LDS (re-read by every unit of the block)
     constexpr bool DIRECT = MR == 1;
     const f32x4* X4 = reinterpret_cast<const f32x4*>(FOLD ? p.A : a_row(p, m0));
-    f32x4 w[ROWS][CH];
-    f32x4 xv[DIRECT ? CH : 1];
-    f32x4 xp[XPARTS ? CH : 1][XPARTS ? GEMV_MAXP : 1];
+    f32x4 w[WB ? 1 : ROWS][WB ? 1 : CH];
+    u32x4 wb[WB ? ROWS : 1][WB ? CH : 1];
+    f32x4 xv[DIRECT ? CH * XN : 1];
+    f32x4 gv[GN && DIRECT ? CH * XN : 1];
+    f32x4 xp[XPARTS ? CH * XN : 1][XPARTS ? GEMV_MAXP : 1];
     const f32x4* P4 = reinterpret_cast<const f32x4*>(p.parts) + (int64_t)m0 * p.nparts * K4;
     // Row-blocked forms (MR > 1): W loads unpredicated from clamped addresses, x zeroed past K
     // where it is used (their predicated loads compiled to exec-masked branches that each waited
@@ -987,7 +1012,35 @@ __global__ void __launch_bounds__(256) gemv_kernel(GemmArgs p) {
     auto load_chunk = [&](int t0) {
 #pragma unroll
         for (int t = 0; t < CH; ++t) {
-            const int k4 = j + LPU * (t0 + t), kk = min(k4, K4 - 1);
+            const int k4 = j + LPU * (t0 + t), kk = min(k4, KP - 1);
+            if constexpr (WB) {
+#pragma unroll
+                for (int r = 0; r < ROWS; ++r) {
+                    if constexpr (DIRECT)
+                        wb[r][t] = k4 >= KP ? u32x4{0u, 0u, 0u, 0u}
+                                   : NT ? __builtin_nontemporal_load(&WB4[(int64_t)wrow[r] * KP + k4])
+                                        : WB4[(int64_t)wrow[r] * KP + k4];
+                    else
+                        wb[r][t] = NT ? __builtin_nontemporal_load(&WB4[(int64_t)wrow[r] * KP + kk])
+                                      : WB4[(int64_t)wrow[r] * KP + kk];
+                }
+                if constexpr (DIRECT) {
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        if (!FOLD || t0) xv[2 * t + h] = X4[2 * kk + h];
+                        if constexpr (GN) {
+                            if (gn) gv[2 * t + h] = G4[2 * kk + h];
+                        }
+                        if constexpr (XPARTS) {
+#pragma unroll
+                            for (int pp = 0; pp < GEMV_MAXP; ++pp)
+                                xp[2 * t + h][pp] = (pp < p.nparts && k4 < KP) ? P4[(int64_t)pp * K4 + 2 * k4 + h]
+                                                                               : f32x4{0.f, 0.f, 0.f, 0.f};
+                        }
+                    }
+                }
+                continue;
+            }
 #pragma unroll
             for (int r = 0; r < ROWS; ++r) {
                 if constexpr (DIRECT)
@@ -1012,7 +1065,7 @@ __global__ void __launch_bounds__(256) gemv_kernel(GemmArgs p) {
     auto add_parts = [&]() {
         if constexpr (XPARTS) {
 #pragma unroll
-            for (int t = 0; t < CH; ++t)
+            for (int t = 0; t < CH * XN; ++t)
 #pragma unroll
                 for (int pp = 0; pp < GEMV_MAXP; ++pp) xv[t] += xp[t][pp];
         }
@@ -1113,7 +1166,14 @@ __global__ void __launch_bounds__(256) gemv_kernel(GemmArgs p) {
             }
         X4 = reinterpret_cast<const f32x4*>(p.A + (int64_t)bi * p.lda);
 #pragma unroll
-        for (int t = 0; t < CH; ++t) xv[t] = X4[min(j + LPU * t, K4 - 1)];
+        for (int t = 0; t < CH; ++t) {
+            if constexpr (WB) {
+                xv[2 * t] = X4[2 * min(j + LPU * t, KP - 1)];
+                xv[2 * t + 1] = X4[2 * min(j + LPU * t, KP - 1) + 1];
+            } else {
+                xv[t] = X4[min(j + LPU * t, K4 - 1)];
+            }
+        }
         if (blockIdx.x == 0 && tid == 0) {
             p.amax_ids[0] = bi;
             // the previous step's position: its lm_head already moved pos on (pos_adv)
@@ -1127,19 +1187,45 @@ __global__ void __launch_bounds__(256) gemv_kernel(GemmArgs p) {
     // (unpredicated loads from clamped addresses, zeroed after they land: predicated loads
     // compiled to exec-masked branches that waited for each load before issuing the next)
     constexpr int SU = 8;
+    // WB: the staged rows carry the norm weight (x * g), so each row's sum of squares of raw x is
+    // taken here: per thread, then per wave (group_sum), then the four waves' sums in wave order
+    __shared__ float ss_w[WB && !DIRECT ? 4 : 1][MR];
     if constexpr (!DIRECT) {
+        float ssp[WB ? MR : 1];
+        if constexpr (WB) {
+#pragma unroll
+            for (int m = 0; m < MR; ++m) ssp[m] = 0.f;
+        }
         for (int f0 = tid; f0 < MR * K4; f0 += 256 * SU) {
-            f32x4 v[SU];
+            f32x4 v[SU], g[GN ? SU : 1];
 #pragma unroll
             for (int u = 0; u < SU; ++u) {
                 const int f = f0 + 256 * u, m = f / K4, k4 = f - m * K4;
                 const bool ok = f < MR * K4 && m < Mb;
                 v[u] = reinterpret_cast<const f32x4*>(a_row(p, m0 + (ok ? m : 0)))[ok ? k4 : 0];
+                if constexpr (GN) {
+                    if (gn) g[u] = G4[ok ? k4 : 0];
+                }
             }
 #pragma unroll
             for (int u = 0; u < SU; ++u) {
                 const int f = f0 + 256 * u, m = f / K4;
+                if constexpr (WB) {
+                    const float sq = v[u].x * v[u].x + v[u].y * v[u].y + v[u].z * v[u].z + v[u].w * v[u].w;
+#pragma unroll
+                    for (int mm = 0; mm < MR; ++mm) ssp[mm] += (f < MR * K4 && m == mm && m < Mb) ? sq : 0.f;
+                    if constexpr (GN) {
+                        if (gn) v[u] *= g[u];
+                    }
+                }
                 if (f < MR * K4) reinterpret_cast<f32x4*>(xs)[f] = m < Mb ? v[u] : f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+        }
+        if constexpr (WB) {
+#pragma unroll
+            for (int m = 0; m < MR; ++m) {
+                const float v = group_sum<64>(ssp[m]);
+                if (lane == 0) ss_w[wid][m] = v;
             }
         }
         __syncthreads();
@@ -1152,7 +1238,7 @@ __global__ void __launch_bounds__(256) gemv_kernel(GemmArgs p) {
 #pragma unroll
         for (int r = 0; r < ROWS; ++r) acc[r][m] = 0.f;
     }
-    const int nt = (K4 + LPU - 1) / LPU;
+    const int nt = (KP + LPU - 1) / LPU;
     for (int t0 = 0; t0 < nt; t0 += CH) {
         if (t0) load_chunk(t0);
         add_parts();
@@ -1161,7 +1247,14 @@ __global__ void __launch_bounds__(256) gemv_kernel(GemmArgs p) {
 #pragma unroll
                 for (int t = 0; t < CH; ++t) {
                     const int k4 = j + LPU * (t0 + t);
-                    if (k4 < K4) reinterpret_cast<f32x4*>(p.x_out + (int64_t)m0 * p.K)[k4] = xv[t];
+                    if constexpr (WB) {
+                        if (k4 < KP) {
+                            reinterpret_cast<f32x4*>(p.x_out + (int64_t)m0 * p.K)[2 * k4] = xv[2 * t];
+                            reinterpret_cast<f32x4*>(p.x_out + (int64_t)m0 * p.K)[2 * k4 + 1] = xv[2 * t + 1];
+                        }
+                    } else {
+                        if (k4 < K4) reinterpret_cast<f32x4*>(p.x_out + (int64_t)m0 * p.K)[k4] = xv[t];
+                    }
                 }
             }
         }
@@ -1170,8 +1263,44 @@ __global__ void __launch_bounds__(256) gemv_kernel(GemmArgs p) {
             if (t0 + t >= nt) break;  // wave-uniform
             // lanes past K: the one-row form reads a clamped (finite) x against its zero W and
             // counts no norm; the row-blocked form holds clamped W and zeroes x
-            const int k4 = j + LPU * (t0 + t), kk = min(k4, K4 - 1);
-            const float in = k4 < K4 ? 1.f : 0.f;
+            const int k4 = j + LPU * (t0 + t), kk = min(k4, KP - 1);
+            const float in = k4 < KP ? 1.f : 0.f;
+            if constexpr (WB) {
+                // the piece's eight weights, then fp32 FMAs in k order 0..7 for every row
+                float wf[ROWS][8];
+#pragma unroll
+                for (int r = 0; r < ROWS; ++r) {
+                    wf[r][0] = bf16_lo(wb[r][t].x); wf[r][1] = bf16_hi(wb[r][t].x);
+                    wf[r][2] = bf16_lo(wb[r][t].y); wf[r][3] = bf16_hi(wb[r][t].y);
+                    wf[r][4] = bf16_lo(wb[r][t].z); wf[r][5] = bf16_hi(wb[r][t].z);
+                    wf[r][6] = bf16_lo(wb[r][t].w); wf[r][7] = bf16_hi(wb[r][t].w);
+                }
+#pragma unroll
+                for (int m = 0; m < MR; ++m) {
+                    f32x4 xa, xb;
+                    if constexpr (DIRECT) {
+                        xa = xv[2 * t];
+                        xb = xv[2 * t + 1];
+                        ss[0] += in * (xa.x * xa.x + xa.y * xa.y + xa.z * xa.z + xa.w * xa.w +
+                                       xb.x * xb.x + xb.y * xb.y + xb.z * xb.z + xb.w * xb.w);
+                        if constexpr (GN) {
+                            if (gn) {
+                                xa *= gv[2 * t];
+                                xb *= gv[2 * t + 1];
+                            }
+                        }
+                    } else {
+                        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+                        xa = k4 < KP ? reinterpret_cast<const f32x4*>(xs + m * p.K)[2 * kk] : z;
+                        xb = k4 < KP ? reinterpret_cast<const f32x4*>(xs + m * p.K)[2 * kk + 1] : z;
+                    }
+#pragma unroll
+                    for (int r = 0; r < ROWS; ++r)
+                        acc[r][m] += wf[r][0] * xa.x + wf[r][1] * xa.y + wf[r][2] * xa.z + wf[r][3] * xa.w +
+                                     wf[r][4] * xb.x + wf[r][5] * xb.y + wf[r][6] * xb.z + wf[r][7] * xb.w;
+                }
+                continue;
+            }
             f32x4 x[MR];
             if constexpr (DIRECT) {
                 x[0] = xv[t];
@@ -1192,7 +1321,8 @@ __global__ void __launch_bounds__(256) gemv_kernel(GemmArgs p) {
     // the LPU lanes of a unit are one aligned group: VALU-only reduction (no LDS round trips)
 #pragma unroll
     for (int m = 0; m < MR; ++m) {
-        ss[m] = group_sum<LPU>(ss[m]);
+        if constexpr (WB && !DIRECT) ss[m] = ss_w[0][m] + ss_w[1][m] + ss_w[2][m] + ss_w[3][m];
+        else ss[m] = group_sum<LPU>(ss[m]);
 #pragma unroll
         for (int r = 0; r < ROWS; ++r) acc[r][m] = group_sum<LPU>(acc[r][m]);
     }

@@ -131,6 +131,13 @@ struct GemmArgs {
     const float* W;                // [N, K] row-major
     const unsigned short* W3;      // opt-in x6 path (gemm_x6.h): W as three bf16 pieces
                                    // [N][3][K] (null: the fp32 MFMA kernels)
+    // opt-in bf16 weight storage (l3_set_weight_bf16; DESIGN.md "bf16 weight storage"): W as one
+    // bf16 value per element, [N, K] row-major in W's row layout and WITHOUT the RMSNorm fold, read
+    // by the bf16-weight form of gemv_kernel only (launch_gemm takes it exactly where the launch
+    // goes to gemv_kernel, gemm_takes_bf16; every other kernel reads W).  norm_w [K]: the RMSNorm
+    // weight that form multiplies into the activations instead (null: none)
+    const unsigned short* Wb;
+    const float* norm_w;
     float* C; int64_t ldc;         // output (EPI_QKV: unused)
     int M, N, K;
     bool norm;                     // RMSNorm on A: rows scaled by 1/sqrt(mean(A^2)+eps); the norm
@@ -520,6 +527,14 @@ bool gemm_is_gemv(const GemmArgs& a);
 // true when that GEMV runs one row per block with the input row read per lane (the only form
 // that takes GemmArgs::parts)
 bool gemv_direct(const GemmArgs& a);
+// true when launch_gemm serves this launch from GemmArgs::Wb (the bf16-weight gemv_kernel)
+bool gemm_takes_bf16(int epi, const GemmArgs& a);
+// bf16 weight storage (misc.hip): out[i] = bf16(w[i]), round-to-nearest-even on the top 16 bits
+// (NaN -> 0x7fc0); *n_inexact (a pair, zeroed by the caller) += the elements whose value changed
+// (NaN not counted) — pair entry (i / sel_stride) & 1 when sel_stride > 0 (gate / up interleaved
+// in groups of that many elements), else entry 0; write_back: w[i] = float(out[i]) as well
+hipError_t launch_to_bf16(float* w, unsigned short* out, int64_t n, int64_t sel_stride, bool write_back,
+                          unsigned long long* n_inexact, hipStream_t s);
 // which EPI_STORE kernel launch_gemm picks (0 = GEMV): launches of equal id round identically
 // row by row, whatever their M
 int gemm_store_config(const GemmArgs& a);

@@ -215,7 +215,57 @@ hipError_t launch_fold_cols(float* W, int64_t rows, int K, const float* w, hipSt
     if (K % 4) return hipErrorInvalidValue;
     const int64_t n4 = rows * (K / 4);
     if (n4 == 0) return hipSuccess;
-    hipLaunchKernelGGL(fold_cols_kernel, dim3(grid_for(n4, 256)), dim3(256), 0, s, W, n4, K / 4, w);
+    // one thread per float4 (no grid stride), so the whole grid: grid_for's cap of 4096 blocks left
+    // everything past the first 4 M elements of a large tensor (an lm_head) unfolded
+    hipLaunchKernelGGL(fold_cols_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, W, n4, K / 4, w);
+    return hipGetLastError();
+}
+
+// bf16 weight storage (l3_set_weight_bf16; DESIGN.md "bf16 weight storage"): round-to-nearest-even
+// on the top 16 bits — the carry of the rounding add runs into the exponent, so a value past the
+// largest bf16 goes to +-inf and subnormals round like any other value; -0 keeps its sign; a NaN
+// becomes the quiet NaN 0x7fc0 (what torch's conversion gives)
+__device__ __forceinline__ unsigned bf16_rne(unsigned u) {
+    if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0u;
+    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+}
+
+// one thread per 4 elements (a wave: 256 contiguous elements, inside one gate / up group since
+// sel_stride is a multiple of 512); the wave's count of changed elements leaves in one vector atomic
+__global__ void to_bf16_kernel(float* w, unsigned short* out, int64_t n, int64_t sel_stride, int write_back,
+                               unsigned long long* n_inexact) {
+    const int64_t i0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    int bad = 0;
+    if (i0 + 4 <= n) {
+        const uint4 v = *reinterpret_cast<const uint4*>(w + i0);
+        const unsigned b0 = bf16_rne(v.x), b1 = bf16_rne(v.y), b2 = bf16_rne(v.z), b3 = bf16_rne(v.w);
+        *reinterpret_cast<uint2*>(out + i0) = uint2{b0 | (b1 << 16), b2 | (b3 << 16)};
+        const uint4 r = {b0 << 16, b1 << 16, b2 << 16, b3 << 16};
+        bad = (r.x != v.x && b0 != 0x7fc0u) + (r.y != v.y && b1 != 0x7fc0u) + (r.z != v.z && b2 != 0x7fc0u) +
+              (r.w != v.w && b3 != 0x7fc0u);
+        if (write_back) *reinterpret_cast<uint4*>(w + i0) = r;
+    } else {
+        for (int64_t i = i0; i < n; ++i) {
+            const unsigned v = __float_as_uint(w[i]), b = bf16_rne(v);
+            out[i] = (unsigned short)b;
+            bad += (b << 16) != v && b != 0x7fc0u;
+            if (write_back) w[i] = __uint_as_float(b << 16);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o);
+    if ((threadIdx.x & 63) == 0 && bad) {
+        const int64_t first = i0 < n ? i0 : n - 1;
+        atomicAdd(n_inexact + (sel_stride > 0 ? (first / sel_stride) & 1 : 0), (unsigned long long)bad);
+    }
+}
+
+hipError_t launch_to_bf16(float* w, unsigned short* out, int64_t n, int64_t sel_stride, bool write_back,
+                          unsigned long long* n_inexact, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    if (sel_stride % 512 != 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(to_bf16_kernel, dim3((unsigned)(((n + 3) / 4 + 255) / 256)), dim3(256), 0, s, w, out, n, sel_stride,
+                       write_back ? 1 : 0, n_inexact);
     return hipGetLastError();
 }
 

@@ -81,6 +81,10 @@ struct Layer {
     // the opt-in x6 GEMM path (gemm_x6.h, l3_set_gemm_x6): each weight as three bf16 pieces
     // [N][3][K], made from the folded fp32 weight (null when the path is off)
     unsigned short *wqkv3 = nullptr, *wo3 = nullptr, *wgu3 = nullptr, *wd3 = nullptr;
+    // opt-in bf16 weight storage (l3_set_weight_bf16): each weight as bf16, in the fp32 tensor's row
+    // layout and without the norm fold, made by l3_finalize (null when the mode is off); read by
+    // the bf16-weight GEMV, with n_attn / n_ffn applied to the activations (GemmArgs::norm_w)
+    unsigned short *wqkvb = nullptr, *wob = nullptr, *wgub = nullptr, *wdb = nullptr;
 };
 
 struct Timer {
@@ -101,6 +105,12 @@ struct l3_ctx {
     hipEvent_t lag_ev[MAX_PARTS - 1] = {};
     int split = 2;                   // parts (1 = off); l3_set_batch_split, L3_BATCH_SPLIT
     bool gemm_x6 = false;            // prefill GEMMs on the x6 path (l3_set_gemm_x6, L3_GEMM_X6)
+    // bf16 weight storage (l3_set_weight_bf16, L3_WEIGHT_BF16): 0 off, 1 exact, 2 round; taken at
+    // l3_finalize, which makes the bf16 copies (Layer::wqkvb ..., lm_headb) the decode GEMVs stream
+    int weight_bf16 = 0;
+    unsigned short* lm_headb = nullptr;
+    int64_t wb_bytes = 0;            // bytes of the bf16 copies
+    int64_t wb_launches = 0;         // GEMV launches issued on them (a captured step: at capture)
     // layer 0's QKV of a prefill as a lookup in a table of its pre-RoPE rows per token id
     // (embed_qkv.h, l3_set_embed_qkv, L3_EMBED_QKV): built at the first call that qualifies, on
     // stream, if its bytes fit embed_qkv_cap; a refused allocation is not retried
@@ -454,6 +464,10 @@ extern "C" int l3_create(int32_t device, const l3_dims* dims, l3_ctx** out) {
     c->d = d;
     c->prune_last = env_knob("L3_LAST_LAYER_ALL_ROWS", 0) == 0;
     c->gemm_x6 = env_knob("L3_GEMM_X6", 0) != 0;
+    {
+        const int m = env_knob("L3_WEIGHT_BF16", 0);
+        c->weight_bf16 = m == 1 || m == 2 ? m : 0;
+    }
     c->embed_qkv = env_knob("L3_EMBED_QKV", 1) != 0;
     {  // batch-split default for new contexts
         const int n = env_knob("L3_BATCH_SPLIT", c->split);
@@ -522,7 +536,9 @@ extern "C" int l3_destroy(l3_ctx* c) {
         dfree(L.wqkv); dfree(L.wo); dfree(L.wgu); dfree(L.wd); dfree(L.n_attn); dfree(L.n_ffn);
         dfree(L.cache_k); dfree(L.cache_v);
         dfree(L.wqkv3); dfree(L.wo3); dfree(L.wgu3); dfree(L.wd3);
+        dfree(L.wqkvb); dfree(L.wob); dfree(L.wgub); dfree(L.wdb);
     }
+    dfree(c->lm_headb);
     dfree(c->emb); dfree(c->lm_head); dfree(c->final_norm); dfree(c->rope_cos); dfree(c->rope_sin);
     dfree(c->h); dfree(c->q); dfree(c->attn); dfree(c->hid); dfree(c->logits); dfree(c->ids);
     dfree(c->oparts); dfree(c->amax_part); dfree(c->hsum); dfree(c->skws); dfree(c->amax_rows);
@@ -747,10 +763,119 @@ extern "C" int l3_set_embed_qkv(l3_ctx* c, int32_t on, int64_t max_bytes) {
     return 0;
 }
 
+// ---- bf16 weight storage (DESIGN.md "bf16 weight storage") ------------------------------------
+static int group_members(const l3_group* g);  // (below)
+
+static void free_bf16(l3_ctx* c) {
+    for (auto& L : c->layers) {
+        dfree(L.wqkvb); dfree(L.wob); dfree(L.wgub); dfree(L.wdb);
+        L.wqkvb = L.wob = L.wgub = L.wdb = nullptr;
+    }
+    dfree(c->lm_headb);
+    c->lm_headb = nullptr;
+    c->wb_bytes = 0;
+}
+
+extern "C" int l3_set_weight_bf16(l3_ctx* c, int32_t mode) {
+    CHECK_CTX(c);
+    if (mode < 0 || mode > 2) return fail("l3_set_weight_bf16: mode %d (0 off, 1 exact, 2 round)", mode);
+    if (c->finalized)
+        return fail("l3_set_weight_bf16: context already finalized (the norm weights are folded into the "
+                    "fp32 weights there; set the mode before l3_finalize)");
+    if (mode && c->group && group_members(c->group) > 1)
+        return fail("l3_set_weight_bf16: this context is a member of a multi-device l3_group (not supported)");
+    c->weight_bf16 = mode;
+    return 0;
+}
+
+extern "C" int l3_weight_bf16_info(l3_ctx* c, int32_t* mode, int64_t* bytes, int64_t* gemv_launches) {
+    CHECK_CTX(c);
+    if (mode) *mode = c->weight_bf16;
+    if (bytes) *bytes = c->wb_bytes;
+    if (gemv_launches) *gemv_launches = c->wb_launches;
+    return 0;
+}
+
+// launch_gemm, counting the launches served from the bf16 copies (l3_weight_bf16_info)
+static hipError_t gemm(l3_ctx* c, int epi, const GemmArgs& g, hipStream_t s) {
+    if (g.Wb && gemm_takes_bf16(epi, g)) c->wb_launches += 1;
+    return launch_gemm(epi, g, s);
+}
+
+// The bf16 copies of every projection whose kinds were all uploaded, and of the lm_head, from the
+// weights as uploaded (before the norm fold).  Exact mode: any element that is not a bf16 value
+// fails the call — the first (layer, kind) in upload order is named — and leaves the context as it
+// was.  Round mode: the fp32 tensors become float(bf16(W)) too, so the kernels that read them
+// (prefill, skinny, split-K, x6, the layer-0 table, the persistent step) compute the same model.
+static int finalize_bf16(l3_ctx* c) {
+    static const char* const kind_name[] = {"self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj",
+                                            "self_attn.o_proj", "mlp.gate_proj", "mlp.up_proj", "mlp.down_proj"};
+    const int64_t D = c->d.dim, FD = c->d.hidden_dim, VS = c->d.vocab_size;
+    const int nl = (int)c->layers.size();
+    const bool wr = c->weight_bf16 == 2;
+    unsigned long long* cnt = nullptr;  // [nl][8] per-kind counts (slot = kind - L3_W_Q), then the lm_head's pair
+    const size_t ncnt = (size_t)nl * 8 + 2;
+    HIP_TRY(hipMalloc(&cnt, ncnt * 8));
+    auto bail = [&](int rc) {
+        (void)hipStreamSynchronize(c->stream);
+        dfree(cnt);
+        free_bf16(c);
+        return rc;
+    };
+    if (hipMemsetAsync(cnt, 0, ncnt * 8, c->stream) != hipSuccess) return bail(fail("l3_finalize: memset failed"));
+    const unsigned QKV = (1u << L3_W_Q) | (1u << L3_W_K) | (1u << L3_W_V);
+    const unsigned GU = (1u << L3_W_GATE) | (1u << L3_W_UP);
+    hipError_t e = hipSuccess;
+    int64_t bytes = 0;
+    auto conv = [&](float* w, unsigned short** out, int64_t n, int64_t sel, unsigned long long* k) {
+        if (e != hipSuccess) return;
+        e = hipMalloc(out, (size_t)n * 2);
+        if (e == hipSuccess) e = launch_to_bf16(w, *out, n, sel, wr, k, c->stream);
+        bytes += n * 2;
+    };
+    for (int li = 0; li < nl; ++li) {
+        Layer& L = c->layers[li];
+        unsigned long long* k = cnt + (size_t)li * 8;
+        if ((L.have & QKV) == QKV) {  // q | k | v stacked: one copy, a count per section
+            if (e == hipSuccess) e = hipMalloc(&L.wqkvb, (size_t)c->qkvn * D * 2);
+            const int64_t off[4] = {0, c->qdim * D, (c->qdim + c->kvdim) * D, c->qkvn * D};
+            for (int t = 0; t < 3 && e == hipSuccess; ++t)
+                e = launch_to_bf16(L.wqkv + off[t], L.wqkvb + off[t], off[t + 1] - off[t], 0, wr, k + t, c->stream);
+            bytes += c->qkvn * D * 2;
+        }
+        if (L.have & (1u << L3_W_O)) conv(L.wo, &L.wob, D * c->qdim, 0, k + 3);
+        if ((L.have & GU) == GU) conv(L.wgu, &L.wgub, 2 * FD * D, 16 * D, k + 4);  // 16-row groups: gate, up
+        if (L.have & (1u << L3_W_DOWN)) conv(L.wd, &L.wdb, D * FD, 0, k + 6);
+    }
+    if (c->have_lm) conv(c->lm_head, &c->lm_headb, VS * D, 0, cnt + (size_t)nl * 8);
+    std::vector<unsigned long long> h(ncnt, 0);
+    if (e == hipSuccess) e = hipMemcpyAsync(h.data(), cnt, ncnt * 8, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return bail(fail("l3_finalize: making the bf16 weight copies failed: %s", hipGetErrorString(e)));
+    }
+    if (c->weight_bf16 == 1) {
+        for (int li = 0; li < nl; ++li)
+            for (int t = 0; t < 7; ++t)
+                if (h[(size_t)li * 8 + t])
+                    return bail(fail("l3_finalize: weight_bf16 exact mode: model.layers.%d.%s.weight (layer %d, kind %d) "
+                                     "has %llu elements that are not bf16-representable", li, kind_name[t], li,
+                                     t + (int)L3_W_Q, h[(size_t)li * 8 + t]));
+        if (h[(size_t)nl * 8])
+            return bail(fail("l3_finalize: weight_bf16 exact mode: lm_head.weight (kind %d) has %llu elements that are "
+                             "not bf16-representable", (int)L3_W_LM_HEAD, h[(size_t)nl * 8]));
+    }
+    dfree(cnt);
+    c->wb_bytes = bytes;
+    return 0;
+}
+
 extern "C" int l3_finalize(l3_ctx* c) {
     CHECK_CTX(c);
     if (c->finalized) return 0;
     if (set_dev(c)) return 1;
+    if (c->weight_bf16 && finalize_bf16(c)) return 1;
     // Fold each RMSNorm weight into the columns of the GEMM that consumes the normalised rows
     // (attention norm -> wqkv, FFN norm -> wgu, final norm -> lm_head): the GEMMs then apply
     // only the per-row 1/rms factor.  Only where both were uploaded: a layer-only (attention)
@@ -883,9 +1008,11 @@ static int run_layer(l3_ctx* c, int li, int B, int L, int start_pos, const int* 
     // the last row of each sequence only (its RoPE at position start_pos + L - 1)
     const bool kv_only = prune && T > 256;
     g.W3 = Ly.wqkv3;  // null unless the x6 path is on (then launch_gemm takes it past 32 rows)
+    g.Wb = Ly.wqkvb; g.norm_w = Ly.wqkvb ? Ly.n_attn : nullptr;  // null unless bf16 weight storage is on
     if (kv_only) {
         g.W = Ly.wqkv + (int64_t)c->qdim * D; g.N = 2 * c->kvdim; g.col_base = c->qdim;
         if (g.W3) g.W3 += (int64_t)c->qdim * 3 * D;
+        if (g.Wb) g.Wb += (int64_t)c->qdim * D;
     }
     // Layer 0 on embedding rows, exactly where launch_gemm would reach the tiled fp32 kernel with
     // a_rows set (more than 256 rows: past the GEMV, the skinny kernel and split-K, which round
@@ -899,7 +1026,7 @@ static int run_layer(l3_ctx* c, int li, int B, int L, int start_pos, const int* 
         e.T = (int)T; e.L = L; e.start_pos = start_pos; e.H = g.H; e.KVH = g.KVH; e.HD = g.HD; e.Smax = g.Smax;
         e.VS = c->d.vocab_size;
         if (timed_on(c, L3_K_EMBED_QKV, s, [&] { return launch_embed_qkv(e, s); })) return 1;
-    } else if (timed_on(c, L3_K_QKV, s, [&] { return launch_gemm(EPI_QKV, g, s); })) return 1;
+    } else if (timed_on(c, L3_K_QKV, s, [&] { return gemm(c, EPI_QKV, g, s); })) return 1;
     if (prune) {
         const int D4 = D;
         float* hl = h + (int64_t)(L - 1) * D4;  // row b's last position: hl + b * L * D
@@ -909,10 +1036,10 @@ static int run_layer(l3_ctx* c, int li, int B, int L, int start_pos, const int* 
         GemmArgs o{};  // O-proj + residual on the last rows, in place on h
         if (kv_only) {
             GemmArgs gq = g;  // q of the last rows: [B, qdim], compact
-            gq.A = hl; gq.lda = (int64_t)L * D4; gq.W = Ly.wqkv; gq.W3 = nullptr; gq.N = c->qdim; gq.col_base = 0;
+            gq.A = hl; gq.lda = (int64_t)L * D4; gq.W = Ly.wqkv; gq.W3 = nullptr; gq.Wb = Ly.wqkvb; gq.N = c->qdim; gq.col_base = 0;
             gq.M = B; gq.L = 1; gq.start_pos = start_pos + L - 1; gq.force_skinny = true;
             gq.ws = nullptr;
-            if (timed_on(c, L3_K_QKV, s, [&] { return launch_gemm(EPI_QKV, gq, s); })) return 1;
+            if (timed_on(c, L3_K_QKV, s, [&] { return gemm(c, EPI_QKV, gq, s); })) return 1;
             a.q = q; a.B = B; a.L = 1; a.start_pos = start_pos + L - 1;  // one query per sequence
             if (timed_on(c, L3_K_ATTN, s, [&] { return launch_attention(a, s); })) return 1;
             o.A = attn; o.lda = c->qdim;
@@ -921,25 +1048,27 @@ static int run_layer(l3_ctx* c, int li, int B, int L, int start_pos, const int* 
             if (timed_on(c, L3_K_ATTN, s, [&] { return launch_attention_last(a, s); })) return 1;
             o.A = attn + (int64_t)(L - 1) * c->qdim; o.lda = (int64_t)L * c->qdim;
         }
-        o.W = Ly.wo; o.C = hl; o.ldc = (int64_t)L * D4;
+        o.W = Ly.wo; o.Wb = Ly.wob; o.C = hl; o.ldc = (int64_t)L * D4;
         o.M = B; o.N = D4; o.K = c->qdim; o.norm = false; o.force_skinny = true;
-        if (timed_on(c, L3_K_OPROJ, s, [&] { return launch_gemm(EPI_RESID, o, s); })) return 1;
+        if (timed_on(c, L3_K_OPROJ, s, [&] { return gemm(c, EPI_RESID, o, s); })) return 1;
         GemmArgs gl{};  // rmsnorm -> gate|up -> SwiGLU on the last rows
         gl.A = hl; gl.lda = (int64_t)L * D4; gl.W = Ly.wgu; gl.C = hid; gl.ldc = FD;
+        gl.Wb = Ly.wgub; gl.norm_w = Ly.wgub ? Ly.n_ffn : nullptr;
         gl.M = B; gl.N = 2 * FD; gl.K = D4; gl.norm = true; gl.eps = c->d.norm_eps; gl.force_skinny = true;
-        if (timed_on(c, L3_K_GATEUP, s, [&] { return launch_gemm(EPI_SWIGLU, gl, s); })) return 1;
+        if (timed_on(c, L3_K_GATEUP, s, [&] { return gemm(c, EPI_SWIGLU, gl, s); })) return 1;
         GemmArgs dl{};  // down + residual on the last rows
-        dl.A = hid; dl.lda = FD; dl.W = Ly.wd; dl.C = hl; dl.ldc = (int64_t)L * D4;
+        dl.A = hid; dl.lda = FD; dl.W = Ly.wd; dl.Wb = Ly.wdb; dl.C = hl; dl.ldc = (int64_t)L * D4;
         dl.M = B; dl.N = D4; dl.K = FD; dl.norm = false; dl.force_skinny = true;
-        return timed_on(c, L3_K_DOWN, s, [&] { return launch_gemm(EPI_RESID, dl, s); });
+        return timed_on(c, L3_K_DOWN, s, [&] { return gemm(c, EPI_RESID, dl, s); });
     }
     GemmArgs gu{};  // rmsnorm -> gate|up -> SwiGLU
     gu.A = h; gu.lda = D; gu.W = Ly.wgu; gu.W3 = Ly.wgu3; gu.C = hid; gu.ldc = FD;
     gu.M = (int)T; gu.N = 2 * FD; gu.K = D; gu.norm = true;  // n_ffn folded into wgu
+    gu.Wb = Ly.wgub; gu.norm_w = Ly.wgub ? Ly.n_ffn : nullptr;
     gu.eps = c->d.norm_eps;
     GemmArgs dn{};  // down + residual
     dn.A = hid; dn.lda = FD; dn.W = Ly.wd; dn.W3 = Ly.wd3; dn.C = h; dn.ldc = D;
-    dn.M = (int)T; dn.N = D; dn.K = FD; dn.norm = false;
+    dn.M = (int)T; dn.N = D; dn.K = FD; dn.norm = false; dn.Wb = Ly.wdb;
     gu.ws = dn.ws = skws; gu.ws_cap = dn.ws_cap = c->skws_cap;
     // Batch-1 decode: the O-proj rides in the attention launch as per-head partial rows, which
     // gate|up adds to its input and down to its residual (h + attn . Wo^T, llama3.py:211,253),
@@ -965,14 +1094,14 @@ static int run_layer(l3_ctx* c, int li, int B, int L, int start_pos, const int* 
     } else {
         // O-proj + residual (in place on h)
         GemmArgs o{};
-        o.A = attn; o.lda = c->qdim; o.W = Ly.wo; o.W3 = Ly.wo3; o.C = h; o.ldc = D;
+        o.A = attn; o.lda = c->qdim; o.W = Ly.wo; o.W3 = Ly.wo3; o.Wb = Ly.wob; o.C = h; o.ldc = D;
         o.M = (int)T; o.N = D; o.K = c->qdim; o.norm = false;
         o.ws = skws; o.ws_cap = c->skws_cap;
         if (emb_ids) { o.res_src = c->emb; o.res_rows = emb_ids; }  // h = emb[ids] + attn . Wo^T
-        if (timed_on(c, L3_K_OPROJ, s, [&] { return launch_gemm(EPI_RESID, o, s); })) return 1;
+        if (timed_on(c, L3_K_OPROJ, s, [&] { return gemm(c, EPI_RESID, o, s); })) return 1;
     }
-    if (timed_on(c, L3_K_GATEUP, s, [&] { return launch_gemm(EPI_SWIGLU, gu, s); })) return 1;
-    if (timed_on(c, L3_K_DOWN, s, [&] { return launch_gemm(EPI_RESID, dn, s); })) return 1;
+    if (timed_on(c, L3_K_GATEUP, s, [&] { return gemm(c, EPI_SWIGLU, gu, s); })) return 1;
+    if (timed_on(c, L3_K_DOWN, s, [&] { return gemm(c, EPI_RESID, dn, s); })) return 1;
     return 0;
 }
 
@@ -983,6 +1112,7 @@ static GemmArgs lm_head_args(l3_ctx* c, int B, int L, float* logits_dev, int b0)
     lm.A = c->h + ((int64_t)b0 * L + L - 1) * D; lm.lda = (int64_t)L * D; lm.W = c->lm_head;
     lm.C = logits_dev + (int64_t)b0 * VS; lm.ldc = VS;
     lm.M = B; lm.N = (int)VS; lm.K = (int)D; lm.norm = true;  // final norm folded
+    lm.Wb = c->lm_headb; lm.norm_w = c->lm_headb ? c->final_norm : nullptr;
     lm.eps = c->d.norm_eps;
     return lm;
 }
@@ -1003,7 +1133,7 @@ static int run_lm_head(l3_ctx* c, int B, int L, float* logits_dev, int b0, hipSt
     c->amax_rows_n = c->rows_amax && B > 1 && b0 == 0 && !c->amax_n && gemm_store_config(lm) != 0
                          ? (int)((c->d.vocab_size + 63) / 64) : 0;
     if (c->amax_rows_n) { lm.amax_rows = c->amax_rows; lm.amax_nct = c->amax_rows_n; }
-    return timed_on(c, L3_K_LMHEAD, s, [&] { return launch_gemm(EPI_STORE, lm, s); });
+    return timed_on(c, L3_K_LMHEAD, s, [&] { return gemm(c, EPI_STORE, lm, s); });
 }
 
 // greedy argmax of the rows the last forward left in c->logits (llama3.py:320): from the
@@ -1993,7 +2123,7 @@ static int ragged_prefill(l3_ctx* c, const int64_t* ids_host, const int32_t* len
         if (run_layer(c, li, B, Lmax, 0, nullptr, li == 0 ? c->ids : nullptr)) return 1;
     GemmArgs lm = lm_head_args(c, B, 1, c->logits, 0);  // A row b = h row b * Lmax + lens[b] - 1
     lm.a_rows = rag_word(c, RAG_ROWS);
-    if (timed(c, L3_K_LMHEAD, [&] { return launch_gemm(EPI_STORE, lm, c->stream); })) return 1;
+    if (timed(c, L3_K_LMHEAD, [&] { return gemm(c, EPI_STORE, lm, c->stream); })) return 1;
     for (auto& Ly : c->layers)
         HIP_TRY(launch_ragged_zero_tail(Ly.cache_k, Ly.cache_v, rag_word(c, RAG_LEN), B, c->d.n_kv_heads,
                                         c->d.max_seq_len, c->HD, Lmax, c->stream));
@@ -2026,9 +2156,10 @@ static int ragged_step(l3_ctx* c, int B, int s_cap) {
         g.eps = c->d.norm_eps;
         g.A = c->h; g.lda = D; g.W = Ly.wqkv; g.C = c->rag_qkv; g.ldc = c->qkvn;
         g.M = B; g.N = c->qkvn; g.K = D; g.norm = true;
+        g.Wb = Ly.wqkvb; g.norm_w = Ly.wqkvb ? Ly.n_attn : nullptr;
         g.ws = c->skws; g.ws_cap = c->skws_cap;
         if (li == 0) { g.A = c->emb; g.a_rows = cur; }
-        if (timed(c, L3_K_QKV, [&] { return launch_gemm(EPI_STORE, g, s); })) return 1;
+        if (timed(c, L3_K_QKV, [&] { return gemm(c, EPI_STORE, g, s); })) return 1;
         RaggedAttnArgs a{};
         a.qkv = c->rag_qkv; a.cache_k = Ly.cache_k; a.cache_v = Ly.cache_v; a.out = c->attn;
         a.rope_cos = c->rope_cos; a.rope_sin = c->rope_sin;
@@ -2038,23 +2169,24 @@ static int ragged_step(l3_ctx* c, int B, int s_cap) {
         a.q_scale = (float)(1.4426950408889634 / std::sqrt((double)c->HD));
         if (timed(c, L3_K_ATTN, [&] { return launch_attn_decode_ragged(a, s); })) return 1;
         GemmArgs o{};  // O-proj + residual (layer 0: h = emb[cur_id] + attn . Wo^T)
-        o.A = c->attn; o.lda = c->qdim; o.W = Ly.wo; o.C = c->h; o.ldc = D;
+        o.A = c->attn; o.lda = c->qdim; o.W = Ly.wo; o.Wb = Ly.wob; o.C = c->h; o.ldc = D;
         o.M = B; o.N = D; o.K = c->qdim; o.norm = false;
         o.ws = c->skws; o.ws_cap = c->skws_cap;
         if (li == 0) { o.res_src = c->emb; o.res_rows = cur; }
-        if (timed(c, L3_K_OPROJ, [&] { return launch_gemm(EPI_RESID, o, s); })) return 1;
+        if (timed(c, L3_K_OPROJ, [&] { return gemm(c, EPI_RESID, o, s); })) return 1;
         GemmArgs gu{};  // rmsnorm -> gate|up -> SwiGLU
         gu.A = c->h; gu.lda = D; gu.W = Ly.wgu; gu.C = c->hid; gu.ldc = FD;
         gu.M = B; gu.N = 2 * FD; gu.K = D; gu.norm = true; gu.eps = c->d.norm_eps;
+        gu.Wb = Ly.wgub; gu.norm_w = Ly.wgub ? Ly.n_ffn : nullptr;
         GemmArgs dn{};  // down + residual
-        dn.A = c->hid; dn.lda = FD; dn.W = Ly.wd; dn.C = c->h; dn.ldc = D;
+        dn.A = c->hid; dn.lda = FD; dn.W = Ly.wd; dn.Wb = Ly.wdb; dn.C = c->h; dn.ldc = D;
         dn.M = B; dn.N = D; dn.K = FD; dn.norm = false;
         gu.ws = dn.ws = c->skws; gu.ws_cap = dn.ws_cap = c->skws_cap;
-        if (timed(c, L3_K_GATEUP, [&] { return launch_gemm(EPI_SWIGLU, gu, s); })) return 1;
-        if (timed(c, L3_K_DOWN, [&] { return launch_gemm(EPI_RESID, dn, s); })) return 1;
+        if (timed(c, L3_K_GATEUP, [&] { return gemm(c, EPI_SWIGLU, gu, s); })) return 1;
+        if (timed(c, L3_K_DOWN, [&] { return gemm(c, EPI_RESID, dn, s); })) return 1;
     }
     const GemmArgs lm = lm_head_args(c, B, 1, c->logits, 0);
-    return timed(c, L3_K_LMHEAD, [&] { return launch_gemm(EPI_STORE, lm, s); });
+    return timed(c, L3_K_LMHEAD, [&] { return gemm(c, EPI_STORE, lm, s); });
 }
 
 // Token choice on c->logits (llama3.py:320, or the sampling rule with row b's uniform of
@@ -2184,21 +2316,22 @@ extern "C" int l3_attention_forward_host(l3_ctx* c, int32_t layer, const float* 
     HIP_TRY(hipMemcpyAsync(c->h, x_host, T * D * 4, hipMemcpyHostToDevice, c->stream));
     GemmArgs g{};
     g.A = c->h; g.lda = D; g.W = Ly.wqkv; g.M = (int)T; g.N = c->qkvn; g.K = D; g.norm = false;
+    g.Wb = Ly.wqkvb;  // (no attention norm in this context: norm_w stays null)
     g.q_out = c->q; g.cache_k = Ly.cache_k; g.cache_v = Ly.cache_v;
     g.rope_cos = c->rope_cos; g.rope_sin = c->rope_sin;
     g.L = L; g.start_pos = start_pos; g.H = c->d.n_heads; g.KVH = c->d.n_kv_heads; g.HD = c->HD;
     g.Smax = c->d.max_seq_len;
     g.q_scale = (float)(1.4426950408889634 / std::sqrt((double)c->HD));
-    if (timed(c, L3_K_QKV, [&] { return launch_gemm(EPI_QKV, g, c->stream); })) return 1;
+    if (timed(c, L3_K_QKV, [&] { return gemm(c, EPI_QKV, g, c->stream); })) return 1;
     AttnArgs a{};
     a.q = c->q; a.cache_k = Ly.cache_k; a.cache_v = Ly.cache_v; a.out = c->attn;
     a.B = B; a.L = L; a.start_pos = start_pos; a.H = c->d.n_heads; a.KVH = c->d.n_kv_heads;
     a.HD = c->HD; a.Smax = c->d.max_seq_len;
     if (timed(c, L3_K_ATTN, [&] { return launch_attention(a, c->stream); })) return 1;
     GemmArgs o{};
-    o.A = c->attn; o.lda = c->qdim; o.W = Ly.wo; o.C = c->h; o.ldc = D;
+    o.A = c->attn; o.lda = c->qdim; o.W = Ly.wo; o.Wb = Ly.wob; o.C = c->h; o.ldc = D;
     o.M = (int)T; o.N = D; o.K = c->qdim; o.norm = false;
-    if (timed(c, L3_K_OPROJ, [&] { return launch_gemm(EPI_STORE, o, c->stream); })) return 1;
+    if (timed(c, L3_K_OPROJ, [&] { return gemm(c, EPI_STORE, o, c->stream); })) return 1;
     HIP_TRY(hipMemcpyAsync(out_host, c->h, T * D * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
@@ -2337,7 +2470,7 @@ static int op_linear(l3_ctx* c, int epi, const float* dA, int64_t rows, int K, i
     GemmArgs g{};
     g.A = dA; g.lda = K; g.W = dW; g.C = dC; g.ldc = (epi == EPI_SWIGLU) ? N / 2 : N;
     g.M = (int)rows; g.N = N; g.K = K; g.norm = norm;
-    HIP_TRY(launch_gemm(epi, g, c->stream));
+    HIP_TRY(gemm(c, epi, g, c->stream));
     return 0;
 }
 
@@ -2353,6 +2486,63 @@ extern "C" int l3_op_linear_host(l3_ctx* c, const float* x, int64_t rows, int32_
     H2D(dx, x, rows * K);
     H2D(dw, w, (int64_t)N * K);
     if (op_linear(c, EPI_STORE, dx, rows, K, N, dw, dy, false)) return 1;
+    D2H(y, dy, rows * N);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// bf16 weight storage on plain arrays: the conversion kernel of l3_finalize, and the bf16-weight
+// GEMV (gemv_kernel's WB form) with EPI_STORE
+extern "C" int l3_op_to_bf16_host(l3_ctx* c, const float* x, int64_t n, uint16_t* out_u16, int64_t* n_inexact) {
+    CHECK_CTX(c);
+    if (n < 0 || (n > 0 && (!x || !out_u16))) return fail("l3_op_to_bf16: bad argument (n = %lld)", (long long)n);
+    if (set_dev(c)) return 1;
+    Scratch S{c};
+    SCRATCH(dx, n);
+    SCRATCH(db, (n + 1) / 2);
+    SCRATCH(dn, 4);
+    H2D(dx, x, n);
+    HIP_TRY(hipMemsetAsync(dn, 0, 16, c->stream));
+    HIP_TRY(launch_to_bf16(dx, reinterpret_cast<unsigned short*>(db), n, 0, false,
+                           reinterpret_cast<unsigned long long*>(dn), c->stream));
+    unsigned long long bad[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(bad, dn, 16, hipMemcpyDeviceToHost, c->stream));
+    if (n > 0) HIP_TRY(hipMemcpyAsync(out_u16, db, (size_t)n * 2, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (n_inexact) *n_inexact = (int64_t)bad[0];
+    return 0;
+}
+
+extern "C" int l3_op_linear_bf16_host(l3_ctx* c, const float* x, int64_t rows, int32_t K, int32_t N,
+                                      const uint16_t* w_u16, const float* norm_w, float eps, float* y) {
+    CHECK_CTX(c);
+    if (!x || !w_u16 || !y) return fail("l3_op_linear_bf16: null argument");
+    if (rows < 1 || rows > 8) return fail("l3_op_linear_bf16: rows = %lld outside [1, 8] (the GEMV's range)", (long long)rows);
+    if (K <= 0 || K % 32) return fail("l3_op_linear_bf16: K=%d must be a positive multiple of 32", K);
+    if (N <= 0 || N % 4) return fail("l3_op_linear_bf16: N=%d must be a positive multiple of 4", N);
+    // rows per launch: the GEMV stages its rows in 64 KB of LDS (gemm_is_gemv), so a long K takes
+    // the rows in smaller blocks — always on the GEMV, never another kernel
+    int per = 8;
+    while (per > 1 && (int64_t)per * K > 16384) per /= 2;
+    if (set_dev(c)) return 1;
+    Scratch S{c};
+    SCRATCH(dx, rows * K);
+    SCRATCH(dw, ((int64_t)N * K + 1) / 2);
+    SCRATCH(dg, K);
+    SCRATCH(dy, rows * N);
+    H2D(dx, x, rows * K);
+    HIP_TRY(hipMemcpyAsync(dw, w_u16, (size_t)N * K * 2, hipMemcpyHostToDevice, c->stream));
+    if (norm_w) H2D(dg, norm_w, K);
+    for (int64_t r0 = 0; r0 < rows; r0 += per) {
+        GemmArgs g{};
+        g.A = dx + r0 * K; g.lda = K; g.W = nullptr; g.Wb = reinterpret_cast<const unsigned short*>(dw);
+        g.norm_w = norm_w ? dg : nullptr; g.norm = norm_w != nullptr; g.eps = eps;
+        g.C = dy + r0 * N; g.ldc = N;
+        g.M = (int)(rows - r0 < per ? rows - r0 : per); g.N = N; g.K = K;
+        if (!gemm_takes_bf16(EPI_STORE, g))
+            return fail("l3_op_linear_bf16: %d x %d x %d is not a shape of the weight-streaming GEMV", g.M, K, N);
+        HIP_TRY(gemm(c, EPI_STORE, g, c->stream));
+    }
     D2H(y, dy, rows * N);
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
@@ -2429,7 +2619,7 @@ static int score_lm(l3_ctx* c, const float* A, int64_t lda, int64_t rows, int K,
         const int64_t m = rows - r0 < chunk ? rows - r0 : chunk;
         g.A = A + r0 * lda; g.M = (int)m;
         g.lse_targets = targets_dev + r0; g.lse_tgt = tgt_logit_dev + r0;
-        if (timed(c, L3_K_LMHEAD, [&] { return launch_gemm(EPI_STORE, g, c->stream); })) return 1;
+        if (timed(c, L3_K_LMHEAD, [&] { return gemm(c, EPI_STORE, g, c->stream); })) return 1;
         if (timed(c, L3_K_ARGMAX, [&] {
                 return launch_score_combine(g.lse_rows, g.lse_nct, g.lse_tgt, g.lse_targets, m, N, logprob_dev + r0,
                                             lse_dev ? lse_dev + r0 : nullptr, argmax_dev ? argmax_dev + r0 : nullptr,
@@ -3002,6 +3192,7 @@ extern "C" int l3_group_create(int32_t ndev, const int32_t* devices, const l3_di
         c->nranks = ndev;
         c->rank = i;
         c->comm_mode = 1;  // the group's gathers are always serialized on the member streams
+        if (ndev > 1) c->weight_bf16 = 0;  // L3_WEIGHT_BF16 is for single-device contexts (l3_set_weight_bf16)
     }
     *out = g;
     return 0;

@@ -89,6 +89,10 @@ _SIGNATURES = {
     "l3_set_batch_split": (ctypes.c_int, [_P, _I32, _I64]),
     "l3_set_gemm_x6": (ctypes.c_int, [_P, _I32]),
     "l3_set_embed_qkv": (ctypes.c_int, [_P, _I32, _I64]),
+    "l3_set_weight_bf16": (ctypes.c_int, [_P, _I32]),
+    "l3_weight_bf16_info": (ctypes.c_int, [_P, _P, _P, _P]),
+    "l3_op_to_bf16_host": (ctypes.c_int, [_P, _P, _I64, _P, _P]),
+    "l3_op_linear_bf16_host": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _P, _P, _F, _P]),
     "l3_set_last_layer_rows": (ctypes.c_int, [_P, _I32]),
     "l3_kernel_timing": (ctypes.c_int, [_P, _I32]),
     "l3_kernel_stats": (ctypes.c_int, [_P, _P, _P]),
@@ -463,6 +467,18 @@ class Context:
         table is built at first use if it fits max_bytes (0 keeps the limit, 256 MB by default)."""
         check(lib().l3_set_embed_qkv(self._h, int(bool(on)), int(max_bytes)))
 
+    def set_weight_bf16(self, mode: int) -> None:
+        """Extension (l3_set_weight_bf16): bf16 storage of the projections and the lm_head for the
+        weight-streaming decode GEMVs — 0 off, 1 exact (every element must be a bf16 value, else
+        ``finalize`` fails), 2 round (the weights are rounded).  Before ``finalize`` only."""
+        check(lib().l3_set_weight_bf16(self._h, int(mode)))
+
+    def weight_bf16_info(self) -> dict:
+        """The mode, the bytes of the bf16 copies and the GEMV launches issued on them."""
+        m, b, n = ctypes.c_int32(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        check(lib().l3_weight_bf16_info(self._h, ctypes.byref(m), ctypes.byref(b), ctypes.byref(n)))
+        return {"mode": m.value, "bytes": b.value, "gemv_launches": n.value}
+
     def synchronize(self) -> None:
         check(lib().l3_synchronize(self._h))
 
@@ -632,6 +648,32 @@ class Context:
         N = w.shape[0]
         y = np.empty(x.shape[:-1] + (N,), np.float32)
         check(lib().l3_op_linear_host(self._h, ptr(x), x.size // K, K, N, ptr(w), ptr(y)))
+        return y
+
+    def op_to_bf16(self, x: np.ndarray):
+        """(uint16 array of x's shape, count): the device bf16 conversion of l3_set_weight_bf16
+        (round-to-nearest-even, ``utils.round_bf16``'s rule) and how many elements it changed."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        out = np.empty(x.shape, np.uint16)
+        n = ctypes.c_int64(0)
+        check(lib().l3_op_to_bf16_host(self._h, ptr(x), x.size, ptr(out), ctypes.byref(n)))
+        return out, int(n.value)
+
+    def op_linear_bf16(self, x: np.ndarray, w_u16: np.ndarray, norm_w: Optional[np.ndarray] = None,
+                       eps: float = 0.0) -> np.ndarray:
+        """``x [rows <= 8, K] @ W.T`` with W [N, K] given as bf16 bit patterns (uint16), on the
+        bf16-weight GEMV (l3_op_linear_bf16_host); with ``norm_w`` the RMSNorm of x (weight norm_w,
+        ``eps``) is applied first.  A shape that kernel does not take raises."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        w = np.ascontiguousarray(w_u16, dtype=np.uint16)
+        if x.ndim != 2 or w.ndim != 2 or w.shape[1] != x.shape[1]:
+            raise ValueError(f"x {x.shape} and w {w.shape} must be [rows, K] and [N, K]")
+        g = None if norm_w is None else np.ascontiguousarray(norm_w, dtype=np.float32)
+        if g is not None and g.shape != (x.shape[1],):
+            raise ValueError(f"norm_w {g.shape} must be [K = {x.shape[1]}]")
+        y = np.empty((x.shape[0], w.shape[0]), np.float32)
+        check(lib().l3_op_linear_bf16_host(self._h, ptr(x), x.shape[0], x.shape[1], w.shape[0], ptr(w),
+                                           ptr(g) if g is not None else None, float(eps), ptr(y)))
         return y
 
     def op_linear_logprob(self, x: np.ndarray, w: np.ndarray, targets: np.ndarray):

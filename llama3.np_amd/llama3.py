@@ -51,6 +51,9 @@ _NPZ_READER = os.environ.get("L3_NPZ_READER", "threads")
 
 DEFAULT_DEVICE = int(os.environ.get("LLAMA3_HIP_DEVICE", "0"))
 
+# Llama(..., weight_dtype=...) -> l3_set_weight_bf16 mode
+_WEIGHT_DTYPES = {None: 0, "bf16": 1, "bf16-round": 2}
+
 
 # ---- module functions (reference llama3.py:22-83) ----------------------------
 #
@@ -268,8 +271,16 @@ class Llama:
     ``generate`` runs argmax on the device and copies back only ids."""
 
     def __init__(self, model_path: str, args: ModelArgs, device: Optional[int] = None,
-                 keep_host_weights: bool = True, devices: Optional[Sequence[int]] = None):
-        """``device`` / ``keep_host_weights`` / ``devices`` are extensions.
+                 keep_host_weights: bool = True, devices: Optional[Sequence[int]] = None,
+                 weight_dtype: Optional[str] = None):
+        """``device`` / ``keep_host_weights`` / ``devices`` / ``weight_dtype`` are extensions.
+
+        ``weight_dtype`` (DESIGN.md "bf16 weight storage"): ``None`` keeps every weight fp32;
+        ``"bf16"`` also stores the projections and the lm_head as bf16 for the weight-streaming
+        decode GEMVs (half the bytes per token) and needs a checkpoint whose values are bf16
+        already, as published Llama-3 weights are — a tensor that is not raises ``ValueError``
+        naming it; ``"bf16-round"`` rounds them (``utils.round_bf16``), and the model computed is
+        the rounded one on every path.  Not with more than one device.
 
         ``devices=[0, ..., N-1]``: one process drives N GPUs (``l3hip.Group``, the C ABI's
         l3_group_*).  Every call keeps the reference's signature and result: batch row r runs on
@@ -284,6 +295,10 @@ class Llama:
         ``model_path`` may also be a mapping of the ``.npz`` keys to arrays (what
         ``load_parameters`` returns; extension) — uploaded as given, no file read."""
         self.args = args
+        if weight_dtype not in _WEIGHT_DTYPES:
+            raise ValueError(f"weight_dtype {weight_dtype!r}: expected one of {sorted(map(str, _WEIGHT_DTYPES))}")
+        if weight_dtype is not None and devices is not None and len(devices) > 1:
+            raise NotImplementedError("bf16 weight storage on a multi-device model: not implemented")
         keep = keep_host_weights
         pool = None
         if isinstance(model_path, Mapping):
@@ -316,6 +331,8 @@ class Llama:
             self._group = None
             self._ctx = l3hip.Context(dims, DEFAULT_DEVICE if device is None else device)
             tgt = self._ctx
+        if weight_dtype is not None:
+            self._ctx.set_weight_bf16(_WEIGHT_DTYPES[weight_dtype])
         self._target = tgt
         emb = weight.get("model.embed_tokens.weight")
         tgt.upload(0, l3hip.W_EMBED, emb)
@@ -330,7 +347,12 @@ class Llama:
         tgt.upload(0, l3hip.W_LM_HEAD, lm)
         self.lm_head_weight = lm.T if keep else _Dropped(lm.shape[::-1])
         del lm
-        tgt.finalize()
+        try:
+            tgt.finalize()
+        except RuntimeError as e:  # "bf16": a tensor that is not bf16 already (named in the message)
+            if "not bf16-representable" in str(e):
+                raise ValueError(str(e)) from None
+            raise
         del weight, norm_w
         if pool is not None:
             pool.clear()

@@ -28,6 +28,22 @@ def load_parameters(model_path):
     return np.load(model_path, allow_pickle=False)
 
 
+def bf16_bits(a) -> np.ndarray:
+    """The bf16 bit patterns (uint16, ``a``'s shape) of fp32 values: round-to-nearest-even on the top
+    16 bits — the carry of the rounding add runs into the exponent, so a value past the largest
+    bf16 gives +-inf and subnormals round like any other value; -0 keeps its sign; a NaN gives the
+    quiet NaN 0x7fc0.  The rule of the library's conversion kernel (l3_set_weight_bf16)."""
+    u = np.ascontiguousarray(a, dtype=np.float32).view(np.uint32).astype(np.uint64)
+    r = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint16)
+    return np.where((u & 0x7FFFFFFF) > 0x7F800000, np.uint16(0x7FC0), r)
+
+
+def round_bf16(a) -> np.ndarray:
+    """fp32 values rounded to bf16 and widened back to fp32 (extension; ``bf16_bits``'s rule): the
+    weights a ``Llama(..., weight_dtype="bf16-round")`` computes with."""
+    return (bf16_bits(a).astype(np.uint32) << 16).view(np.float32)
+
+
 class StreamingNpz:
     """Extension: the streaming loader's view of an ``.npz``.
 
