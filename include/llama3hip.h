@@ -280,13 +280,31 @@ int l3_ragged_forward_host(l3_ctx* ctx, const int64_t* ids_host, const int32_t* 
  * them -1.  With sampling on (l3_set_sampling) row b's token at position p draws the uniform of
  * (seed, b, p), so rows of equal length reproduce l3_greedy_generate_host.  One copy-back at the
  * end (with stop ids also a 4-byte "rows still running" read every few steps, to leave early).
- * Errors as above, and max_new_tokens > max_seq_len; a shape whose decode attention does not fit
- * its LDS budget (n_heads / n_kv_heads > 8, or scores of that many heads over max_new_tokens
- * positions past 64 KiB: about 2 800 positions at four heads per KV head) is refused, all before
- * anything is launched. */
+ * max_new_tokens is bounded by max_seq_len only: where the single-pass decode attention's scores
+ * (n_heads / n_kv_heads heads over max_new_tokens positions) do not fit its 64 KiB of LDS — past
+ * about 2 800 positions at four heads per KV head — the split-KV form below runs instead.
+ * Errors as above, and max_new_tokens > max_seq_len, n_heads / n_kv_heads > 8, and a split-KV
+ * workspace that cannot be allocated, all before anything is launched. */
 int l3_ragged_generate_host(l3_ctx* ctx, const int64_t* ids_host, const int32_t* lens, int32_t B, int32_t Lmax,
                             int32_t max_new_tokens, const int64_t* stop_ids, int32_t n_stop,
                             int64_t* out_ids_host, int32_t* out_lens);
+/* Split-KV decode attention of the ragged decode step (DESIGN.md "Split-KV decode attention"): the
+ * key axis in chunks of `chunk` keys, one workgroup per (chunk, KV head, row) with an LDS
+ * footprint that does not depend on the context, and a second launch that merges the chunks'
+ * partial results (online-softmax rule).  mode 0 (default): auto — the single-pass kernel wherever
+ * its LDS fits (same kernel, same bits as without this call), split only otherwise; mode 1: split
+ * for every ragged decode step.  chunk: a multiple of 64 in [64, 4096]; 0 keeps the current value
+ * (default 256).  The chunk in force is the largest multiple of 64 not above it whose LDS fits
+ * 64 KiB at the context's shape.  Other values are errors; a member of a multi-device l3_group is
+ * refused.  Env L3_RAGGED_SPLIT=1 and L3_RAGGED_SPLIT_CHUNK=n set these for new contexts.  For a
+ * fixed chunk the results do not depend on max_new_tokens or the batch. */
+int l3_set_ragged_attn_split(l3_ctx* ctx, int32_t mode, int32_t chunk);
+/* Any pointer may be NULL.  split_launches: ragged decode-attention launches served by the split
+ * form since l3_create (l3_op_attn_decode_ragged_host's too); workspace_bytes: the chunk partials'
+ * buffer (max_batch_size * n_heads * chunks * (head size + 2) floats, allocated on first use and
+ * grown as needed). */
+int l3_ragged_attn_info(l3_ctx* ctx, int32_t* mode, int32_t* chunk_in_force, int64_t* split_launches,
+                        int64_t* workspace_bytes);
 
 /* ---- one block (replaces TransformerBlock.__call__, llama3.py:239-261) --- */
 /* x [B, L, D] fp32 host -> out [B, L, D]; uses and updates layer's KV cache. */
@@ -322,6 +340,19 @@ int l3_op_rmsnorm_host(l3_ctx* ctx, const float* x, const float* w, int64_t rows
  * cos/sin tables [L, HD/2]. */
 int l3_op_rope_host(l3_ctx* ctx, const float* x, int32_t B, int32_t L, int32_t nh,
                     int32_t hd, const float* cos_t, const float* sin_t, float* y);
+/* One ragged decode-attention launch (llama3.py:163-211 for one new token per row, each row at its
+ * own position) on plain arrays: qkv [B, (H + 2 KVH) * HD] the raw [q | k | v] rows (no RoPE, no
+ * scale), cache_k / cache_v [B, KVH, Smax, HD] (copied in, and back out with slot pos[b] of row b
+ * appended), rope_cos / rope_sin [Smax, HD/2], pos / finished [B] int32, 1 <= s_cap <= Smax the
+ * bound the launch is sized by (every live pos < s_cap), out [B, H * HD].  split 0: the
+ * single-pass kernel (s_cap % 4 == 0; a shape that does not fit its LDS is an error, nothing else
+ * stands in); else the split-KV form at that chunk length (a multiple of 64 in [64, 4096] whose
+ * LDS fits).  A finished row, or one whose pos is no slot below s_cap, gets zeros and touches no
+ * cache slot. */
+int l3_op_attn_decode_ragged_host(l3_ctx* ctx, const float* qkv, float* cache_k, float* cache_v,
+                                  const float* rope_cos, const float* rope_sin, const int32_t* pos,
+                                  const int32_t* finished, int32_t B, int32_t H, int32_t KVH, int32_t HD,
+                                  int32_t Smax, int32_t s_cap, int32_t split, float* out);
 /* FeedForward.__call__ (llama3.py:97-103): x [rows, D], W as stored. */
 int l3_op_ffn_host(l3_ctx* ctx, const float* x, int64_t rows, int32_t dim, int32_t hidden,
                    const float* w_gate, const float* w_up, const float* w_down, float* y);

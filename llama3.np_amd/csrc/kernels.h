@@ -427,13 +427,30 @@ struct RaggedAttnArgs {
     int B, H, KVH, HD, Smax;
     int s_cap;             // score slots per head in LDS (a multiple of 4): every live pos < s_cap
     float q_scale;         // log2(e) / sqrt(HD)
+    // split-KV form only (launch_attn_decode_ragged_split)
+    int chunk;             // keys per chunk (a multiple of 64)
+    float* ws;             // chunk partials: o [B, H, n_split, HD], then (m, l) [B, H, n_split, 2]
 };
 constexpr int RAGGED_MAX_REP = 8;               // query heads per KV head the ragged attention takes
 constexpr size_t RAGGED_LDS_BYTES = 64 * 1024;  // its LDS budget per workgroup
+constexpr int RAGGED_CHUNK_MIN = 64, RAGGED_CHUNK_MAX = 4096;  // split-KV chunk lengths (multiples of 64)
 // LDS bytes of attn_decode_ragged_kernel; whether the shape fits (head size, n_rep, LDS budget)
 size_t attn_decode_ragged_lds(int H, int KVH, int HD, int s_cap);
 bool attn_decode_ragged_ok(int H, int KVH, int HD, int s_cap);
+// the head size and n_rep both ragged attention forms take, whatever the context length
+bool attn_decode_ragged_shape_ok(int H, int KVH, int HD);
 hipError_t launch_attn_decode_ragged(const RaggedAttnArgs& a, hipStream_t s);
+// Split-KV form (DESIGN.md "Split-KV decode attention"): LDS bytes of attn_decode_split_kernel at
+// a chunk length (no context length in it); the largest multiple of 64 not above `want` that fits
+// the LDS budget (0: none); chunks per row and workspace floats for B rows at s_cap
+size_t attn_decode_split_lds(int H, int KVH, int HD, int chunk);
+int attn_decode_split_chunk(int H, int KVH, int HD, int want);
+inline int attn_decode_split_n(int s_cap, int chunk) { return (s_cap + chunk - 1) / chunk; }
+inline int64_t attn_decode_split_ws_floats(int64_t B, int H, int HD, int n_split) {
+    return B * H * n_split * (int64_t)(HD + 2);
+}
+// two launches on s: the chunk kernel on grid (n_split, KVH, B), then the combine on (H, B)
+hipError_t launch_attn_decode_ragged_split(const RaggedAttnArgs& a, hipStream_t s);
 // cache[b][h][len[b] .. Lmax) = 0 for b < B, h < KVH, in both caches
 hipError_t launch_ragged_zero_tail(float* cache_k, float* cache_v, const int32_t* len, int B, int KVH, int Smax,
                                    int HD, int Lmax, hipStream_t s);

@@ -162,6 +162,197 @@ __global__ void __launch_bounds__(256) attn_decode_ragged_kernel(RaggedAttnArgs 
     }
 }
 
+// Split-KV form of the kernel above (DESIGN.md "Split-KV decode attention"): the key axis is cut
+// into chunks of CH = p.chunk keys, chunk c = keys [c * CH, (c + 1) * CH), and every (chunk, KV
+// head, row) is a workgroup of its own whose LDS does not depend on the context length.  The host
+// sizes the grid by s_cap (positions live on the device); a workgroup whose row is finished, whose
+// position is no cache slot, or whose chunk starts past the position returns at once.
+//
+// Append invariant: slot pos of the cache is written by exactly one workgroup per (KV head, row),
+// the one whose chunk holds it (c == pos / CH), and that workgroup scores and accumulates the new
+// key / value from LDS.  Every workgroup reads cached keys < pos only, so no workgroup reads a
+// slot that another workgroup writes in the same launch, and none reads its own stores back.
+//
+// Per active workgroup: (0) RoPE + scale of the n_rep queries into LDS (recomputed per chunk),
+// the owner also k / v; (1) scores, one key per thread; (2) one wave per head: the chunk's max m
+// (log2 domain), exp2(s - m) and their sum l; (3) P.V in 256 / (HD/4) key groups.  Out, per
+// (row, head, chunk), to the workspace: the unnormalised o[HD], m and l — plain stores, no
+// atomics, no flags: attn_decode_combine_kernel is the next launch on the stream.
+// LDS floats: [n_rep][HD] q, [HD] k, [HD] v, [8] row sums, [n_rep][R][HD] partials, [n_rep][CH]
+// scores (attn_decode_split_lds).
+template <int HD>
+__global__ void __launch_bounds__(256) attn_decode_split_kernel(RaggedAttnArgs p) {
+    constexpr int D4 = HD / 4, R = 256 / D4, HALF = HD / 2;
+    extern __shared__ __attribute__((aligned(16))) float dsm[];
+    const int n_rep = p.H / p.KVH, CH = p.chunk;
+    float* qs = dsm;
+    float* kn = qs + n_rep * HD;
+    float* vn = kn + HD;
+    float* ls = vn + HD;
+    float* red = ls + 8;
+    float* sc = red + n_rep * R * HD;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int c = blockIdx.x, n_split = gridDim.x, kvh = blockIdx.y, b = blockIdx.z, h0 = kvh * n_rep;
+    const int pos = p.pos[b];
+    const bool dead = p.finished[b] != 0;
+    if (tid == 0 && c == 0 && !dead) {
+        L3_DCHECK(pos >= 0 && pos < p.Smax, CHK_KV_SLOT);
+        L3_DCHECK(pos >= 0 && pos < p.Smax && pos < p.s_cap, CHK_ATTN_KEYS);
+    }
+    // (pos < s_cap <= n_split * CH: the owner's chunk is in the grid)
+    if (dead || pos < 0 || pos >= p.Smax || pos >= p.s_cap) return;
+    const int k0 = c * CH;
+    if (k0 > pos) return;
+    const bool own = pos < k0 + CH;        // c == pos / CH
+    const int nc = own ? pos - k0 : CH;    // cached keys of the chunk: [k0, k0 + nc), all < pos
+    const int nk = own ? nc + 1 : nc;      // with the new key, local index nc (< CH)
+    const int qdim = p.H * HD, kvdim = p.KVH * HD;
+    const float* row = p.qkv + (int64_t)b * (qdim + 2 * kvdim);
+    const float* cs = p.rope_cos + (int64_t)pos * HALF;
+    const float* sn = p.rope_sin + (int64_t)pos * HALF;
+    const int64_t kv_base = ((int64_t)b * p.KVH + kvh) * p.Smax * HD;
+    // (0) the step's q; in the owner also k, v and their append to slot pos
+    for (int t = tid; t < n_rep * HALF; t += 256) {
+        const int r = t / HALF, i = t - r * HALF;
+        const float2 v = *reinterpret_cast<const float2*>(row + (h0 + r) * HD + 2 * i);
+        const float cc = cs[i], s = sn[i];
+        const float r0 = v.x * cc - v.y * s, r1 = v.x * s + v.y * cc;
+        *reinterpret_cast<float2*>(qs + r * HD + 2 * i) = float2{r0 * p.q_scale, r1 * p.q_scale};
+    }
+    if (own) {
+        if (tid < HALF) {
+            const int i = tid;
+            const float2 v = *reinterpret_cast<const float2*>(row + qdim + kvh * HD + 2 * i);
+            const float cc = cs[i], s = sn[i];
+            const float2 k2 = float2{v.x * cc - v.y * s, v.x * s + v.y * cc};
+            *reinterpret_cast<float2*>(kn + 2 * i) = k2;
+            *reinterpret_cast<float2*>(p.cache_k + kv_base + (int64_t)pos * HD + 2 * i) = k2;
+        } else if (tid < HD) {
+            const int i = tid - HALF;
+            const float2 v2 = *reinterpret_cast<const float2*>(row + qdim + kvdim + kvh * HD + 2 * i);
+            *reinterpret_cast<float2*>(vn + 2 * i) = v2;
+            *reinterpret_cast<float2*>(p.cache_v + kv_base + (int64_t)pos * HD + 2 * i) = v2;
+        }
+    }
+    __syncthreads();
+    const f32x4* K4 = reinterpret_cast<const f32x4*>(p.cache_k + kv_base) + (int64_t)k0 * D4;
+    const f32x4* V4 = reinterpret_cast<const f32x4*>(p.cache_v + kv_base) + (int64_t)k0 * D4;
+    const f32x4* q4 = reinterpret_cast<const f32x4*>(qs);
+    // (1) scores of the chunk's cached keys: each K row loaded once for the n_rep heads
+    for (int k = tid; k < nc; k += 256) {
+        f32x4 kv[D4];
+#pragma unroll
+        for (int i = 0; i < D4; ++i) kv[i] = K4[(int64_t)k * D4 + i];
+#pragma unroll
+        for (int r = 0; r < RAGGED_MAX_REP; ++r) {
+            if (r < n_rep) {
+                float s = 0.f;
+#pragma unroll
+                for (int i = 0; i < D4; ++i) {
+                    const f32x4 q = q4[r * D4 + i];
+                    s += kv[i].x * q.x + kv[i].y * q.y + kv[i].z * q.z + kv[i].w * q.w;
+                }
+                sc[r * CH + k] = s;
+            }
+        }
+    }
+    if (own && tid < n_rep) {  // the new key, from LDS
+        const f32x4* k4 = reinterpret_cast<const f32x4*>(kn);
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < D4; ++i) {
+            const f32x4 q = q4[tid * D4 + i], k = k4[i];
+            s += k.x * q.x + k.y * q.y + k.z * q.z + k.w * q.w;
+        }
+        sc[tid * CH + nc] = s;
+    }
+    __syncthreads();
+    // (2) the chunk's max, softmax numerators and their sum, one wave per head
+    float* ml = p.ws + (int64_t)p.B * p.H * n_split * HD;
+    for (int r = wid; r < n_rep; r += 4) {
+        float* s = sc + r * CH;
+        float m = -INFINITY;
+        for (int k = lane; k < nk; k += 64) m = fmaxf(m, s[k]);
+        m = group_max<64>(m);
+        float l = 0.f;
+        for (int k = lane; k < nk; k += 64) {
+            const float e = __builtin_amdgcn_exp2f(s[k] - m);
+            s[k] = e;
+            l += e;
+        }
+        l = group_sum<64>(l);
+        if (lane == 0) {
+            ls[r] = l;
+            ml[(((int64_t)b * p.H + h0 + r) * n_split + c) * 2] = m;
+        }
+    }
+    __syncthreads();
+    // (3) P.V: each V row loaded once for the n_rep heads
+    const int rg = tid / D4, d4 = tid - rg * D4;
+    if (rg < R) {
+        f32x4 acc[RAGGED_MAX_REP];
+#pragma unroll
+        for (int r = 0; r < RAGGED_MAX_REP; ++r) acc[r] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int k = rg; k < nc; k += R) {
+            const f32x4 v = V4[(int64_t)k * D4 + d4];
+#pragma unroll
+            for (int r = 0; r < RAGGED_MAX_REP; ++r)
+                if (r < n_rep) acc[r] += sc[r * CH + k] * v;
+        }
+        if (own && rg == 0) {  // the new value, from LDS
+            const f32x4 v = reinterpret_cast<const f32x4*>(vn)[d4];
+#pragma unroll
+            for (int r = 0; r < RAGGED_MAX_REP; ++r)
+                if (r < n_rep) acc[r] += sc[r * CH + nc] * v;
+        }
+#pragma unroll
+        for (int r = 0; r < RAGGED_MAX_REP; ++r)
+            if (r < n_rep) reinterpret_cast<f32x4*>(red)[(r * R + rg) * D4 + d4] = acc[r];
+    }
+    __syncthreads();
+    for (int t = tid; t < n_rep * D4; t += 256) {
+        const int r = t / D4, d = t - r * D4;
+        f32x4 o = {0.f, 0.f, 0.f, 0.f};
+        for (int g = 0; g < R; ++g) o += reinterpret_cast<const f32x4*>(red)[(r * R + g) * D4 + d];
+        const int64_t part = ((int64_t)b * p.H + h0 + r) * n_split + c;
+        reinterpret_cast<f32x4*>(p.ws)[part * D4 + d] = o;
+        if (d == 0) ml[part * 2 + 1] = ls[r];
+    }
+}
+
+// The merge of a row's chunk partials (online-softmax rule), grid (H, B), one wave: over the
+// active chunks c = 0 .. pos / CH in ascending order, M = max m_c, then
+// out = sum(o_c * exp2(m_c - M)) / sum(l_c * exp2(m_c - M)).  Only chunks the launch before wrote
+// are read, so the workspace is never cleared; a finished row (or one whose position is no cache
+// slot) gets zeros.  n_split: the chunk kernel's grid, i.e. the workspace's stride.
+template <int HD>
+__global__ void __launch_bounds__(64) attn_decode_combine_kernel(RaggedAttnArgs p, int n_split) {
+    constexpr int D4 = HD / 4;
+    const int h = blockIdx.x, b = blockIdx.y, d = threadIdx.x;
+    if (d >= D4) return;
+    const int pos = p.pos[b];
+    f32x4* out = reinterpret_cast<f32x4*>(p.out + ((int64_t)b * p.H + h) * HD);
+    if (p.finished[b] != 0 || pos < 0 || pos >= p.Smax || pos >= p.s_cap) {
+        out[d] = f32x4{0.f, 0.f, 0.f, 0.f};
+        return;
+    }
+    const int n = pos / p.chunk + 1;  // <= n_split, as pos < s_cap
+    const int64_t part0 = ((int64_t)b * p.H + h) * n_split;
+    const f32x4* o4 = reinterpret_cast<const f32x4*>(p.ws) + part0 * D4;
+    const float2* ml = reinterpret_cast<const float2*>(p.ws + (int64_t)p.B * p.H * n_split * HD) + part0;
+    float M = -INFINITY;
+    for (int c = 0; c < n; ++c) M = fmaxf(M, ml[c].x);
+    f32x4 o = {0.f, 0.f, 0.f, 0.f};
+    float l = 0.f;
+    for (int c = 0; c < n; ++c) {
+        const float2 x = ml[c];
+        const float w = __builtin_amdgcn_exp2f(x.x - M);
+        l += x.y * w;
+        o += o4[(int64_t)c * D4 + d] * w;
+    }
+    out[d] = o * (1.0f / l);
+}
+
 // After a right-padded prefill at position 0 (llama3.py:285-308 on [B, Lmax]): slots
 // [len[b], Lmax) of row b hold the pads' K / V; a row run alone would have left them zero
 // (slot len[b] is the one the reference's loop never writes, :312-318).  grid (KVH, B)
@@ -227,6 +418,15 @@ hipError_t launch_ragged_hd(const RaggedAttnArgs& a, size_t lds, hipStream_t s) 
     return hipGetLastError();
 }
 
+template <int HD>
+hipError_t launch_split_hd(const RaggedAttnArgs& a, int n_split, size_t lds, hipStream_t s) {
+    hipLaunchKernelGGL((attn_decode_split_kernel<HD>), dim3(n_split, a.KVH, a.B), dim3(256), lds, s, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((attn_decode_combine_kernel<HD>), dim3(a.H, a.B), dim3(64), 0, s, a, n_split);
+    return hipGetLastError();
+}
+
 }  // namespace
 
 size_t attn_decode_ragged_lds(int H, int KVH, int HD, int s_cap) {
@@ -234,10 +434,42 @@ size_t attn_decode_ragged_lds(int H, int KVH, int HD, int s_cap) {
     return (n_rep * HD + 2 * (size_t)HD + 8 + n_rep * R * HD + n_rep * (size_t)s_cap) * 4;
 }
 
+bool attn_decode_ragged_shape_ok(int H, int KVH, int HD) {
+    if (KVH <= 0 || H <= 0 || H % KVH != 0 || H / KVH > RAGGED_MAX_REP) return false;
+    return HD == 16 || HD == 32 || HD == 48 || HD == 64 || HD == 96 || HD == 128;
+}
+
 bool attn_decode_ragged_ok(int H, int KVH, int HD, int s_cap) {
-    if (KVH <= 0 || H % KVH != 0 || H / KVH > RAGGED_MAX_REP || s_cap <= 0 || s_cap % 4) return false;
-    if (!(HD == 16 || HD == 32 || HD == 48 || HD == 64 || HD == 96 || HD == 128)) return false;
+    if (!attn_decode_ragged_shape_ok(H, KVH, HD) || s_cap <= 0 || s_cap % 4) return false;
     return attn_decode_ragged_lds(H, KVH, HD, s_cap) <= RAGGED_LDS_BYTES;
+}
+
+// the single-pass kernel's footprint with the chunk in place of the context
+size_t attn_decode_split_lds(int H, int KVH, int HD, int chunk) { return attn_decode_ragged_lds(H, KVH, HD, chunk); }
+
+int attn_decode_split_chunk(int H, int KVH, int HD, int want) {
+    if (!attn_decode_ragged_shape_ok(H, KVH, HD)) return 0;
+    int ch = (want < RAGGED_CHUNK_MAX ? want : RAGGED_CHUNK_MAX) / 64 * 64;
+    while (ch >= RAGGED_CHUNK_MIN && attn_decode_split_lds(H, KVH, HD, ch) > RAGGED_LDS_BYTES) ch -= 64;
+    return ch >= RAGGED_CHUNK_MIN ? ch : 0;
+}
+
+hipError_t launch_attn_decode_ragged_split(const RaggedAttnArgs& a, hipStream_t s) {
+    if (a.B <= 0) return hipSuccess;
+    if (!attn_decode_ragged_shape_ok(a.H, a.KVH, a.HD) || a.s_cap <= 0 || !a.ws) return hipErrorInvalidValue;
+    if (a.chunk < RAGGED_CHUNK_MIN || a.chunk > RAGGED_CHUNK_MAX || a.chunk % 64) return hipErrorInvalidValue;
+    const size_t lds = attn_decode_split_lds(a.H, a.KVH, a.HD, a.chunk);
+    if (lds > RAGGED_LDS_BYTES || a.B > 65535 || a.KVH > 65535) return hipErrorInvalidValue;
+    const int n_split = attn_decode_split_n(a.s_cap, a.chunk);
+    switch (a.HD) {
+        case 16: return launch_split_hd<16>(a, n_split, lds, s);
+        case 32: return launch_split_hd<32>(a, n_split, lds, s);
+        case 48: return launch_split_hd<48>(a, n_split, lds, s);
+        case 64: return launch_split_hd<64>(a, n_split, lds, s);
+        case 96: return launch_split_hd<96>(a, n_split, lds, s);
+        case 128: return launch_split_hd<128>(a, n_split, lds, s);
+        default: return hipErrorInvalidValue;
+    }
 }
 
 hipError_t launch_attn_decode_ragged(const RaggedAttnArgs& a, hipStream_t s) {

@@ -280,6 +280,16 @@ struct l3_ctx {
     int64_t rag_stop_n = 0;
     std::vector<int32_t> rag_host;              // host staging of rag_state (kept until the call's sync)
     std::vector<int64_t> rag_ids_host;          // the padded ids with the pads replaced
+    // split-KV decode attention of the ragged step (l3_set_ragged_attn_split; DESIGN.md "Split-KV
+    // decode attention"): mode 0 auto (split only where the single-pass kernel's LDS does not
+    // fit), 1 always; the chunk asked for (the one in force: ragged_chunk); the chunk partials'
+    // workspace, allocated on first use and grown as needed
+    static constexpr int RAG_SPLIT_CHUNK_DEFAULT = 256;  // measured: DESIGN.md "Split-KV decode attention"
+    int rag_split_mode = 0;
+    int rag_split_chunk = RAG_SPLIT_CHUNK_DEFAULT;
+    float* rag_split_ws = nullptr;
+    int64_t rag_split_ws_n = 0;                 // floats
+    int64_t rag_split_launches = 0;             // split-kernel launches since l3_create (stats)
 };
 
 static bool sampling_on(const l3_ctx* c) { return c->samp.temperature > 0.f; }
@@ -469,6 +479,11 @@ extern "C" int l3_create(int32_t device, const l3_dims* dims, l3_ctx** out) {
         c->weight_bf16 = m == 1 || m == 2 ? m : 0;
     }
     c->embed_qkv = env_knob("L3_EMBED_QKV", 1) != 0;
+    {  // split-KV ragged decode attention defaults for new contexts (values out of range: ignored)
+        c->rag_split_mode = env_knob("L3_RAGGED_SPLIT", 0) == 1 ? 1 : 0;
+        const int ch = env_knob("L3_RAGGED_SPLIT_CHUNK", 0);
+        if (ch >= RAGGED_CHUNK_MIN && ch <= RAGGED_CHUNK_MAX && ch % 64 == 0) c->rag_split_chunk = ch;
+    }
     {  // batch-split default for new contexts
         const int n = env_knob("L3_BATCH_SPLIT", c->split);
         c->split = n < 1 ? 1 : n > l3_ctx::MAX_PARTS ? l3_ctx::MAX_PARTS : n;
@@ -550,6 +565,7 @@ extern "C" int l3_destroy(l3_ctx* c) {
     dfree(c->dec_ids); dfree(c->dec_state); dfree(c->kv_bak); dfree(c->samp_dev);
     dfree(c->score_ws); dfree(c->score_rows);
     dfree(c->rag_state); dfree(c->rag_qkv); dfree(c->rag_u); dfree(c->rag_out); dfree(c->rag_stop);
+    dfree(c->rag_split_ws);
     if (c->dec_host) (void)hipHostFree(c->dec_host);
     for (auto& q : c->spec_q) { (void)hipEventDestroy(q.ev0); (void)hipEventDestroy(q.ev1); (void)hipEventDestroy(q.ev); }
     for (hipEvent_t e : c->spec_free) (void)hipEventDestroy(e);
@@ -2098,6 +2114,64 @@ static int ragged_bufs(l3_ctx* c) {
     return 0;
 }
 
+// Split-KV decode attention (ragged.hip attn_decode_split_kernel; DESIGN.md "Split-KV decode
+// attention").  The chunk in force: the largest multiple of 64 not above the one asked for whose
+// LDS fits the budget at this context's shape (0: the shape has no ragged attention at all).
+static int ragged_chunk(const l3_ctx* c) {
+    return attn_decode_split_chunk(c->d.n_heads, c->d.n_kv_heads, c->HD, c->rag_split_chunk);
+}
+
+static int64_t ragged_split_floats(const l3_ctx* c, int n_split) {
+    return attn_decode_split_ws_floats(c->d.max_batch_size, c->d.n_heads, c->HD, n_split);
+}
+
+// the chunk partials of max_batch_size rows at n_split chunks: allocated on first use, grown as
+// needed, freed with the context; a refused allocation is reported before any launch
+static int ragged_split_ws(l3_ctx* c, const char* who, int n_split) {
+    const int64_t n = ragged_split_floats(c, n_split);
+    if (n <= c->rag_split_ws_n) return 0;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    dfree(c->rag_split_ws);
+    c->rag_split_ws = nullptr;
+    c->rag_split_ws_n = 0;
+    if (hipMalloc(&c->rag_split_ws, (size_t)n * 4) != hipSuccess) {
+        (void)hipGetLastError();  // clear the sticky error: the next launch check must not see it
+        c->rag_split_ws = nullptr;
+        return fail("%s: the split-KV attention workspace (%lld bytes: %d rows x %d heads x %d chunks) could not "
+                    "be allocated", who, (long long)n * 4, c->d.max_batch_size, c->d.n_heads, n_split);
+    }
+    c->rag_split_ws_n = n;
+    return 0;
+}
+
+static int check_ragged_split(int32_t mode, int32_t chunk) {
+    if (mode != 0 && mode != 1) return fail("l3_set_ragged_attn_split: mode %d (0 auto, 1 always)", mode);
+    if (chunk != 0 && (chunk < RAGGED_CHUNK_MIN || chunk > RAGGED_CHUNK_MAX || chunk % 64))
+        return fail("l3_set_ragged_attn_split: chunk %d (a multiple of 64 in [%d, %d]; 0 keeps the current one)",
+                    chunk, RAGGED_CHUNK_MIN, RAGGED_CHUNK_MAX);
+    return 0;
+}
+
+extern "C" int l3_set_ragged_attn_split(l3_ctx* c, int32_t mode, int32_t chunk) {
+    if (check_ragged_split(mode, chunk)) return 1;  // the values first: wrong for every context
+    CHECK_CTX(c);
+    if (c->group && group_members(c->group) > 1)
+        return fail("l3_set_ragged_attn_split: this context is a member of a multi-device l3_group (not supported)");
+    c->rag_split_mode = mode;
+    if (chunk) c->rag_split_chunk = chunk;
+    return 0;
+}
+
+extern "C" int l3_ragged_attn_info(l3_ctx* c, int32_t* mode, int32_t* chunk_in_force, int64_t* split_launches,
+                                   int64_t* workspace_bytes) {
+    CHECK_CTX(c);
+    if (mode) *mode = c->rag_split_mode;
+    if (chunk_in_force) *chunk_in_force = ragged_chunk(c);
+    if (split_launches) *split_launches = c->rag_split_launches;
+    if (workspace_bytes) *workspace_bytes = c->rag_split_ws_n * 4;
+    return 0;
+}
+
 // The prefill at position 0 (llama3.py:285-308) on the padded batch: the per-row state uploaded,
 // every block on every row (as l3_score_host runs them), row b's logits from its position
 // lens[b] - 1 into c->logits, then the pads' slots [lens[b], Lmax) cleared in every layer.
@@ -2146,7 +2220,10 @@ extern "C" int l3_ragged_forward_host(l3_ctx* c, const int64_t* ids_host, const 
 // then :304-307): per layer the raw QKV rows (layer 0 from the embedding rows of cur_id), the
 // ragged attention (RoPE, K / V append at pos[b], one K / V read per KV head), O-proj, gate|up
 // and down at M = B; then the lm_head into c->logits.  Decode keeps the fp32 kernels (no x6).
-static int ragged_step(l3_ctx* c, int B, int s_cap) {
+// chunk: 0 the single-pass attention, else the split-KV form at that chunk length (the caller
+// chose once for the whole call, ragged_split_pick, and the workspace is there); its two launches
+// are one timed L3_K_ATTN entry, so ms per entry compares with the single-pass kernel's.
+static int ragged_step(l3_ctx* c, int B, int s_cap, int chunk) {
     const int D = c->d.dim, FD = c->d.hidden_dim;
     const int32_t* cur = rag_word(c, RAG_CUR);
     hipStream_t s = c->stream;
@@ -2167,7 +2244,12 @@ static int ragged_step(l3_ctx* c, int B, int s_cap) {
         a.B = B; a.H = c->d.n_heads; a.KVH = c->d.n_kv_heads; a.HD = c->HD; a.Smax = c->d.max_seq_len;
         a.s_cap = s_cap;
         a.q_scale = (float)(1.4426950408889634 / std::sqrt((double)c->HD));
-        if (timed(c, L3_K_ATTN, [&] { return launch_attn_decode_ragged(a, s); })) return 1;
+        a.chunk = chunk; a.ws = c->rag_split_ws;
+        if (chunk) c->rag_split_launches += 1;
+        if (timed(c, L3_K_ATTN, [&] {
+                return chunk ? launch_attn_decode_ragged_split(a, s) : launch_attn_decode_ragged(a, s);
+            }))
+            return 1;
         GemmArgs o{};  // O-proj + residual (layer 0: h = emb[cur_id] + attn . Wo^T)
         o.A = c->attn; o.lda = c->qdim; o.W = Ly.wo; o.Wb = Ly.wob; o.C = c->h; o.ldc = D;
         o.M = B; o.N = D; o.K = c->qdim; o.norm = false;
@@ -2225,12 +2307,18 @@ extern "C" int l3_ragged_generate_host(l3_ctx* c, const int64_t* ids_host, const
     if (cap <= 0) return 0;  // no row has a token to emit
     if (!out_ids_host) return fail("%s: null argument", who);
     const int s_cap = (max_new_tokens + 3) & ~3;
-    if (!attn_decode_ragged_ok(c->d.n_heads, c->d.n_kv_heads, c->HD, s_cap))
-        return fail("%s: the decode attention takes at most %d query heads per KV head and %zu bytes of LDS "
-                    "(%d heads per KV head over %d positions need %zu)", who, RAGGED_MAX_REP, RAGGED_LDS_BYTES,
-                    c->d.n_heads / c->d.n_kv_heads, max_new_tokens,
-                    attn_decode_ragged_lds(c->d.n_heads, c->d.n_kv_heads, c->HD, s_cap));
-    if (set_dev(c) || spec_resolve(c) || ensure_ws(c, B, Lmax) || ragged_bufs(c)) return 1;
+    if (!attn_decode_ragged_shape_ok(c->d.n_heads, c->d.n_kv_heads, c->HD))
+        return fail("%s: the decode attention takes at most %d query heads per KV head and head sizes 16, 32, 48, "
+                    "64, 96, 128 (%d heads per KV head, head size %d)", who, RAGGED_MAX_REP,
+                    c->d.n_heads / c->d.n_kv_heads, c->HD);
+    // the attention kernel, once per call: the single-pass one wherever its LDS fits (auto mode:
+    // same kernel, same bits as before the split form existed), the split-KV one otherwise or always
+    const bool split = c->rag_split_mode == 1 || !attn_decode_ragged_ok(c->d.n_heads, c->d.n_kv_heads, c->HD, s_cap);
+    const int chunk = split ? ragged_chunk(c) : 0;
+    if (split && chunk == 0) return fail("%s: no split-KV chunk length fits the attention's LDS budget", who);
+    if (set_dev(c) || spec_resolve(c)) return 1;
+    if (split && ragged_split_ws(c, who, attn_decode_split_n(s_cap, chunk))) return 1;
+    if (ensure_ws(c, B, Lmax) || ragged_bufs(c)) return 1;
     const int64_t n_out_ids = (int64_t)B * cap;
     if (n_out_ids > c->rag_out_n) {
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2265,7 +2353,7 @@ extern "C" int l3_ragged_generate_host(l3_ctx* c, const int64_t* ids_host, const
     st.live = c->rag_state + (int64_t)l3_ctx::RAG_WORDS * c->d.max_batch_size;
     if (ragged_choose(c, st, B)) return 1;  // each row's first token, from its position lens[b] - 1
     for (int i = 1; i < cap; ++i) {
-        if (ragged_step(c, B, s_cap) || ragged_choose(c, st, B)) return 1;
+        if (ragged_step(c, B, s_cap, chunk) || ragged_choose(c, st, B)) return 1;
         // with stop ids the rows may all be finished early: a 4-byte read every 8 steps
         if (st.n_stop > 0 && i % 8 == 0 && i + 1 < cap) {
             int32_t live = 1;
@@ -2461,6 +2549,68 @@ extern "C" int l3_op_rope_host(l3_ctx* c, const float* x, int32_t B, int32_t L, 
     H2D(ds, sin_t, nt);
     HIP_TRY(launch_rope(dx, dy, dc, ds, B, L, nh, hd, c->stream));
     D2H(y, dy, n);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// One ragged decode-attention launch on plain arrays (ragged.hip): split 0 the single-pass kernel,
+// else the split-KV form at that chunk length — the A/B between the two on identical inputs.
+// cache_k / cache_v [B, KVH, Smax, HD] are copied in and, with slot pos[b] appended, back out.
+extern "C" int l3_op_attn_decode_ragged_host(l3_ctx* c, const float* qkv, float* cache_k, float* cache_v,
+                                             const float* rope_cos, const float* rope_sin, const int32_t* pos,
+                                             const int32_t* finished, int32_t B, int32_t H, int32_t KVH, int32_t HD,
+                                             int32_t Smax, int32_t s_cap, int32_t split, float* out) {
+    CHECK_CTX(c);
+    const char* who = "l3_op_attn_decode_ragged";
+    if (!qkv || !cache_k || !cache_v || !rope_cos || !rope_sin || !pos || !finished || !out)
+        return fail("%s: null argument", who);
+    if (B < 1 || B > 65535 || Smax < 1 || s_cap < 1 || s_cap > Smax)
+        return fail("%s: bad shape (B %d, Smax %d, s_cap %d: need 1 <= s_cap <= Smax)", who, B, Smax, s_cap);
+    if (!attn_decode_ragged_shape_ok(H, KVH, HD))
+        return fail("%s: the decode attention takes at most %d query heads per KV head and head sizes 16, 32, 48, "
+                    "64, 96, 128 (H %d, KVH %d, head size %d)", who, RAGGED_MAX_REP, H, KVH, HD);
+    if (split == 0 && !attn_decode_ragged_ok(H, KVH, HD, s_cap))
+        return fail("%s: the single-pass kernel needs s_cap %% 4 == 0 and %zu bytes of LDS at s_cap %d (budget %zu)",
+                    who, attn_decode_ragged_lds(H, KVH, HD, s_cap), s_cap, RAGGED_LDS_BYTES);
+    if (split != 0 && (split < RAGGED_CHUNK_MIN || split > RAGGED_CHUNK_MAX || split % 64 ||
+                       attn_decode_split_lds(H, KVH, HD, split) > RAGGED_LDS_BYTES))
+        return fail("%s: chunk %d (a multiple of 64 in [%d, %d] whose LDS fits %zu bytes)", who, split,
+                    RAGGED_CHUNK_MIN, RAGGED_CHUNK_MAX, RAGGED_LDS_BYTES);
+    if (set_dev(c)) return 1;
+    const int64_t nq = (int64_t)B * (H + 2 * KVH) * HD, nc = (int64_t)B * KVH * Smax * HD;
+    const int64_t nt = (int64_t)Smax * (HD / 2), no = (int64_t)B * H * HD;
+    const int n_split = split ? attn_decode_split_n(s_cap, split) : 0;
+    Scratch S{c};
+    SCRATCH(dq, nq);
+    SCRATCH(dk, nc);
+    SCRATCH(dv, nc);
+    SCRATCH(dc, nt);
+    SCRATCH(ds, nt);
+    SCRATCH(dp, B);
+    SCRATCH(df, B);
+    SCRATCH(dout, no);
+    SCRATCH(dws, attn_decode_split_ws_floats(B, H, HD, n_split));
+    H2D(dq, qkv, nq);
+    H2D(dk, cache_k, nc);
+    H2D(dv, cache_v, nc);
+    H2D(dc, rope_cos, nt);
+    H2D(ds, rope_sin, nt);
+    H2D(dp, pos, B);
+    H2D(df, finished, B);
+    RaggedAttnArgs a{};
+    a.qkv = dq; a.cache_k = dk; a.cache_v = dv; a.out = dout; a.rope_cos = dc; a.rope_sin = ds;
+    a.pos = reinterpret_cast<const int32_t*>(dp); a.finished = reinterpret_cast<const int32_t*>(df);
+    a.B = B; a.H = H; a.KVH = KVH; a.HD = HD; a.Smax = Smax; a.s_cap = s_cap;
+    a.q_scale = (float)(1.4426950408889634 / std::sqrt((double)HD));
+    a.chunk = split; a.ws = dws;
+    if (split) c->rag_split_launches += 1;
+    if (timed(c, L3_K_ATTN, [&] {
+            return split ? launch_attn_decode_ragged_split(a, c->stream) : launch_attn_decode_ragged(a, c->stream);
+        }))
+        return 1;
+    D2H(out, dout, no);
+    D2H(cache_k, dk, nc);
+    D2H(cache_v, dv, nc);
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }

@@ -68,6 +68,10 @@ _SIGNATURES = {
     "l3_greedy_generate_values_host": (ctypes.c_int, [_P, _P, _I32, _I32, _I32, _P, _P]),
     "l3_ragged_forward_host": (ctypes.c_int, [_P, _P, _P, _I32, _I32, _P]),
     "l3_ragged_generate_host": (ctypes.c_int, [_P, _P, _P, _I32, _I32, _I32, _P, _I32, _P, _P]),
+    "l3_set_ragged_attn_split": (ctypes.c_int, [_P, _I32, _I32]),
+    "l3_ragged_attn_info": (ctypes.c_int, [_P, _P, _P, _P, _P]),
+    "l3_op_attn_decode_ragged_host": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32,
+                                                     _I32, _I32, _P]),
     "l3_attention_forward_host": (ctypes.c_int, [_P, _I32, _P, _I32, _I32, _I32, _P]),
     "l3_op_softmax_host": (ctypes.c_int, [_P, _P, _I64, _I64, _P]),
     "l3_op_argmax_host": (ctypes.c_int, [_P, _P, _I64, _I64, _P]),
@@ -410,6 +414,47 @@ class Context:
                                             ptr(stops) if stops.size else None, int(stops.size),
                                             ptr(out), ptr(out_lens)))
         return out, out_lens
+
+    def set_ragged_attn_split(self, mode: int, chunk: int = 0) -> None:
+        """Extension (l3_set_ragged_attn_split): the split-KV decode attention of the ragged
+        decode step — ``mode`` 0 auto (only where the single-pass kernel's LDS does not fit; the
+        default), 1 always; ``chunk`` keys per chunk, a multiple of 64 in [64, 4096] (0 keeps the
+        current one)."""
+        check(lib().l3_set_ragged_attn_split(self._h, int(mode), int(chunk)))
+
+    def ragged_attn_info(self) -> dict:
+        """The split mode, the chunk length in force, the attention launches served by the split
+        form and the bytes of its workspace."""
+        m, ch, n, b = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        check(lib().l3_ragged_attn_info(self._h, ctypes.byref(m), ctypes.byref(ch), ctypes.byref(n), ctypes.byref(b)))
+        return {"mode": m.value, "chunk": ch.value, "split_launches": n.value, "workspace_bytes": b.value}
+
+    def op_attn_decode_ragged(self, qkv, cache_k, cache_v, rope_cos, rope_sin, pos, finished, n_heads: int,
+                              s_cap: int, split: int = 0):
+        """One ragged decode-attention launch on plain arrays (l3_op_attn_decode_ragged_host):
+        ``qkv`` [B, (H + 2 KVH) * HD] raw rows, ``cache_k`` / ``cache_v`` [B, KVH, Smax, HD],
+        ``rope_cos`` / ``rope_sin`` [Smax, HD/2], ``pos`` / ``finished`` [B]; ``split`` 0 runs the
+        single-pass kernel, else the split-KV form at that chunk length.  Returns
+        (out [B, H * HD], cache_k, cache_v) — the caches are copies with slot ``pos[b]`` appended."""
+        ck = np.array(cache_k, dtype=np.float32, order="C")
+        cv = np.array(cache_v, dtype=np.float32, order="C")
+        if ck.ndim != 4 or cv.shape != ck.shape:
+            raise ValueError(f"cache_k {ck.shape} / cache_v {cv.shape} must be [B, KVH, Smax, HD]")
+        B, KVH, Smax, HD = ck.shape
+        H = int(n_heads)
+        qkv = np.ascontiguousarray(qkv, dtype=np.float32)
+        c = np.ascontiguousarray(rope_cos, dtype=np.float32)
+        s = np.ascontiguousarray(rope_sin, dtype=np.float32)
+        pos = np.ascontiguousarray(pos, dtype=np.int32)
+        fin = np.ascontiguousarray(finished, dtype=np.int32)
+        if qkv.shape != (B, (H + 2 * KVH) * HD) or c.shape != (Smax, HD // 2) or s.shape != c.shape:
+            raise ValueError(f"qkv {qkv.shape} / rope tables {c.shape} do not match the caches {ck.shape}")
+        if pos.shape != (B,) or fin.shape != (B,):
+            raise ValueError(f"pos {pos.shape} and finished {fin.shape} must be [{B}]")
+        out = np.empty((B, H * HD), np.float32)
+        check(lib().l3_op_attn_decode_ragged_host(self._h, ptr(qkv), ptr(ck), ptr(cv), ptr(c), ptr(s), ptr(pos),
+                                                  ptr(fin), B, H, KVH, HD, Smax, int(s_cap), int(split), ptr(out)))
+        return out, ck, cv
 
     def layer_forward(self, layer: int, x: np.ndarray, start_pos: int) -> np.ndarray:
         x = np.ascontiguousarray(x, dtype=np.float32)

@@ -272,8 +272,14 @@ class Llama:
 
     def __init__(self, model_path: str, args: ModelArgs, device: Optional[int] = None,
                  keep_host_weights: bool = True, devices: Optional[Sequence[int]] = None,
-                 weight_dtype: Optional[str] = None):
-        """``device`` / ``keep_host_weights`` / ``devices`` / ``weight_dtype`` are extensions.
+                 weight_dtype: Optional[str] = None, ragged_split: Optional[int] = None):
+        """``device`` / ``keep_host_weights`` / ``devices`` / ``weight_dtype`` / ``ragged_split``
+        are extensions.
+
+        ``ragged_split`` (DESIGN.md "Split-KV decode attention"): ``None`` leaves
+        ``generate_ragged``'s decode attention on auto (the split-KV kernels only where the
+        single-pass one does not fit); a chunk length (a multiple of 64 in [64, 4096]) runs the
+        split-KV kernels at that chunk on every ragged decode step.  Not with more than one device.
 
         ``weight_dtype`` (DESIGN.md "bf16 weight storage"): ``None`` keeps every weight fp32;
         ``"bf16"`` also stores the projections and the lm_head as bf16 for the weight-streaming
@@ -299,6 +305,8 @@ class Llama:
             raise ValueError(f"weight_dtype {weight_dtype!r}: expected one of {sorted(map(str, _WEIGHT_DTYPES))}")
         if weight_dtype is not None and devices is not None and len(devices) > 1:
             raise NotImplementedError("bf16 weight storage on a multi-device model: not implemented")
+        if ragged_split is not None and devices is not None and len(devices) > 1:
+            raise NotImplementedError("ragged batches on a multi-device model: not implemented")
         keep = keep_host_weights
         pool = None
         if isinstance(model_path, Mapping):
@@ -333,6 +341,8 @@ class Llama:
             tgt = self._ctx
         if weight_dtype is not None:
             self._ctx.set_weight_bf16(_WEIGHT_DTYPES[weight_dtype])
+        if ragged_split is not None:
+            self._ctx.set_ragged_attn_split(1, int(ragged_split))
         self._target = tgt
         emb = weight.get("model.embed_tokens.weight")
         tgt.upload(0, l3hip.W_EMBED, emb)
@@ -493,7 +503,11 @@ class Llama:
         included) — ``max_new_tokens - len(prompts[b])`` ids, or fewer when the row emitted one of
         ``stop_ids``, which ends the row and stays its last id.  After ``set_sampling`` the ids
         are sampled with the uniforms of (seed, row, position), so rows of equal length give
-        ``generate_all``'s ids.  Not for a model on more than one device."""
+        ``generate_all``'s ids.  ``max_new_tokens`` may be anything up to ``max_seq_len``: where
+        the single-pass decode attention's scores no longer fit its LDS (past about 2 800 positions
+        at four query heads per KV head) the split-KV kernels run instead (DESIGN.md "Split-KV
+        decode attention"; ``context.set_ragged_attn_split`` forces them or sets the chunk).  Not
+        for a model on more than one device."""
         ids, lens = self._ragged(prompts)
         out, n = self._ctx.ragged_generate(ids, lens, int(max_new_tokens), stop_ids)
         return [out[b, :n[b]].copy() for b in range(len(n))]
