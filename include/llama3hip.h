@@ -306,6 +306,38 @@ int l3_set_ragged_attn_split(l3_ctx* ctx, int32_t mode, int32_t chunk);
 int l3_ragged_attn_info(l3_ctx* ctx, int32_t* mode, int32_t* chunk_in_force, int64_t* split_launches,
                         int64_t* workspace_bytes);
 
+/* ---- ragged continuation (extension; DESIGN.md "Ragged continuation") ------ */
+/* Several new tokens per row, each row at its own offset: row b's lens[b] >= 1 tokens (ids_host
+ * [B, Lmax] int64, right-padded, pads ignored) run at positions [starts[b], starts[b] + lens[b])
+ * and attend to cache row b as it stood before the call (llama3.py:285-308 with
+ * start_pos = starts[b], on that row alone).  logits_host [B, VS] fp32: row b the logits of its
+ * last new token.  Afterwards slots [starts[b], starts[b] + lens[b]) hold the new K / V; no other
+ * slot of the cache has changed (pads write nothing, and nothing is cleared).  Every block runs on
+ * every row; the QKV projection keeps the fp32 kernels (l3_set_gemm_x6 applies to the others).
+ * Errors, reported before anything is allocated or launched: a null argument, B > max_batch_size,
+ * a lens[b] outside [1, Lmax], starts[b] < 0, starts[b] + lens[b] > max_seq_len, a token id
+ * outside [-VS, VS) at a real position, n_heads / n_kv_heads > 8 or a head size other than 16, 32,
+ * 48, 64, 96, 128, a member of a multi-device l3_group; and a chunk workspace (B * Lmax raw QKV
+ * rows) that cannot be allocated. */
+int l3_ragged_extend_host(l3_ctx* ctx, const int64_t* ids_host, const int32_t* lens, const int32_t* starts,
+                          int32_t B, int32_t Lmax, float* logits_host);
+/* l3_ragged_generate_host continued from per-row offsets: the extend above, then the same decode
+ * loop with T_b = starts[b] + lens[b] in the prompt length's place — row b's first token from
+ * position T_b - 1, its decode step i >= 1 at T_b + i, slot T_b never written,
+ * max(0, max_new_tokens - T_b) tokens unless it stops earlier, cap = max_new_tokens - min(T_b).
+ * Before the first decode step slot T_b of every row with a budget is zeroed in every layer, so
+ * the ids do not depend on what an earlier call left past the row's frontier.  Sampling draws the
+ * uniform of (seed, b, position); the single-pass or split-KV attention is chosen as there.
+ * Errors as for both calls above.  When no row has a token to emit nothing runs. */
+int l3_ragged_generate_from_host(l3_ctx* ctx, const int64_t* ids_host, const int32_t* lens, const int32_t* starts,
+                                 int32_t B, int32_t Lmax, int32_t max_new_tokens, const int64_t* stop_ids,
+                                 int32_t n_stop, int64_t* out_ids_host, int32_t* out_lens);
+/* The fork of a cache row: slots [0, n_slots) of K and V in every layer are copied from cache row
+ * src_row to each of dst_rows [n_dst] (a shared prefix prefilled once).  Errors: a row outside
+ * [0, max_batch_size), src_row among dst_rows, n_dst > max_batch_size, n_slots outside
+ * [0, max_seq_len], a member of a multi-device l3_group. */
+int l3_cache_copy_rows(l3_ctx* ctx, int32_t src_row, const int32_t* dst_rows, int32_t n_dst, int32_t n_slots);
+
 /* ---- one block (replaces TransformerBlock.__call__, llama3.py:239-261) --- */
 /* x [B, L, D] fp32 host -> out [B, L, D]; uses and updates layer's KV cache. */
 int l3_layer_forward_host(l3_ctx* ctx, int32_t layer, const float* x_host, int32_t B,
@@ -353,6 +385,16 @@ int l3_op_attn_decode_ragged_host(l3_ctx* ctx, const float* qkv, float* cache_k,
                                   const float* rope_cos, const float* rope_sin, const int32_t* pos,
                                   const int32_t* finished, int32_t B, int32_t H, int32_t KVH, int32_t HD,
                                   int32_t Smax, int32_t s_cap, int32_t split, float* out);
+/* The two launches of a ragged extend (l3_ragged_extend_host's attention) on plain arrays: qkv
+ * [B, Lq, (H + 2 KVH) * HD] the raw [q | k | v] rows of the right-padded chunk, cache_k / cache_v
+ * [B, KVH, Smax, HD] (copied in, and back out with slots [starts[b], starts[b] + lens[b]) of row b
+ * written: RoPE'd k, v as given), rope_cos / rope_sin [Smax, HD/2], starts / lens [B] int32 with
+ * 0 <= lens[b] <= Lq, starts[b] < Smax and starts[b] + lens[b] <= Smax, out [B, Lq, H * HD]: new
+ * token t of row b over the keys [0, starts[b] + t]; pad rows zero. */
+int l3_op_attn_extend_ragged_host(l3_ctx* ctx, const float* qkv, float* cache_k, float* cache_v,
+                                  const float* rope_cos, const float* rope_sin, const int32_t* starts,
+                                  const int32_t* lens, int32_t B, int32_t Lq, int32_t H, int32_t KVH,
+                                  int32_t HD, int32_t Smax, float* out);
 /* FeedForward.__call__ (llama3.py:97-103): x [rows, D], W as stored. */
 int l3_op_ffn_host(l3_ctx* ctx, const float* x, int64_t rows, int32_t dim, int32_t hidden,
                    const float* w_gate, const float* w_up, const float* w_down, float* y);

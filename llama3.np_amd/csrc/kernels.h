@@ -460,6 +460,31 @@ hipError_t launch_ragged_uniform(const SampleParams* prm, const int32_t* pos, fl
 hipError_t launch_ragged_advance(const RaggedState& st, const int32_t* tok, int B, int n_ids, hipStream_t s);
 hipError_t dcheck_collect_ragged(unsigned* out);
 
+// Ragged continuation (ragged_extend.hip; DESIGN.md "Ragged continuation"): row b's lens[b] new
+// tokens sit at positions [starts[b], starts[b] + lens[b]) and attend to that row's cache
+struct ExtendAttnArgs {
+    const float* qkv;      // [B, Lq, (H + 2 KVH) * HD] raw [q | k | v] rows (no RoPE, no scale); pads never read
+    float* cache_k;        // [maxB, KVH, Smax, HD]; slots [starts[b], starts[b] + lens[b]) of row b are written
+    float* cache_v;
+    float* out;            // [B, Lq, H * HD]; pad rows get zeros
+    const float* rope_cos; const float* rope_sin;  // [Smax, HD/2]
+    const int32_t* starts; // [B]
+    const int32_t* lens;   // [B], each in [0, Lq] with starts[b] + lens[b] <= Smax
+    int B, Lq, H, KVH, HD, Smax;
+    float q_scale;         // log2(e) / sqrt(HD)
+};
+// two launches on s: the append on grid (ceil(Lq / 16), KVH, B), then the attention on
+// (ceil(Lq / (64 / n_rep)), KVH, B); head shapes: attn_decode_ragged_shape_ok
+hipError_t launch_attn_extend_ragged(const ExtendAttnArgs& a, hipStream_t s);
+// cache[dst[i]][h][0 .. n_slots) = cache[src][h][0 .. n_slots) for i < n_dst, h < KVH, in both
+// caches (dst: device memory; n_rows: rows of the caches)
+hipError_t launch_cache_copy_rows(float* cache_k, float* cache_v, int src, const int32_t* dst, int n_dst, int KVH,
+                                  int Smax, int HD, int n_slots, int n_rows, hipStream_t s);
+// cache[b][h][len[b]] = 0 for b < B with budget[b] > 0, h < KVH, in both caches
+hipError_t launch_ragged_zero_slot(float* cache_k, float* cache_v, const int32_t* len, const int32_t* budget, int B,
+                                   int KVH, int Smax, int HD, hipStream_t s);
+hipError_t dcheck_collect_extend(unsigned* out);
+
 // Persistent batch-1 decode step (decode_persist.hip): one launch runs a whole greedy step —
 // every layer, the lm_head and the argmax — with in-launch hand-offs between the stages
 struct DecodePersistArgs {

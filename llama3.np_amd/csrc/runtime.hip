@@ -268,9 +268,10 @@ struct l3_ctx {
     int64_t score_rows_cap = 0;
     std::vector<int32_t> score_tgt_host;        // int32 staging of the int64 host targets
     // ragged batches (l3_ragged_*; ragged.hip): per-row device state [RAG_WORDS][max_batch_size]
-    // int32 (pos, cur_id, finished, n_out, len, budget, lm_head rows, token) + the live word, the
-    // step's raw QKV rows and sampling uniforms, the output ids and the stop list (grown on demand)
-    static constexpr int RAG_WORDS = 8;
+    // int32 (pos, cur_id, finished, n_out, len, budget, lm_head rows, token, and a continuation's
+    // chunk starts and lengths) + the live word, the step's raw QKV rows and sampling uniforms, the
+    // output ids and the stop list (grown on demand)
+    static constexpr int RAG_WORDS = 10;
     int32_t* rag_state = nullptr;
     float* rag_qkv = nullptr;                   // [max_batch_size, qkvn]
     float* rag_u = nullptr;                     // [max_batch_size]
@@ -290,6 +291,10 @@ struct l3_ctx {
     float* rag_split_ws = nullptr;
     int64_t rag_split_ws_n = 0;                 // floats
     int64_t rag_split_launches = 0;             // split-kernel launches since l3_create (stats)
+    // ragged continuation (l3_ragged_extend_host; ragged_extend.hip): the chunk's raw QKV rows
+    // [B * Lmax, qkvn], allocated on first use and grown as needed
+    float* rag_ext_qkv = nullptr;
+    int64_t rag_ext_qkv_n = 0;                  // floats
 };
 
 static bool sampling_on(const l3_ctx* c) { return c->samp.temperature > 0.f; }
@@ -407,7 +412,7 @@ extern "C" const char* l3_last_error(void) { return g_err.c_str(); }
 
 extern "C" int l3_version(int32_t* major, int32_t* minor) {
     if (major) *major = 0;
-    if (minor) *minor = 16;
+    if (minor) *minor = 17;
     return 0;
 }
 
@@ -565,7 +570,7 @@ extern "C" int l3_destroy(l3_ctx* c) {
     dfree(c->dec_ids); dfree(c->dec_state); dfree(c->kv_bak); dfree(c->samp_dev);
     dfree(c->score_ws); dfree(c->score_rows);
     dfree(c->rag_state); dfree(c->rag_qkv); dfree(c->rag_u); dfree(c->rag_out); dfree(c->rag_stop);
-    dfree(c->rag_split_ws);
+    dfree(c->rag_split_ws); dfree(c->rag_ext_qkv);
     if (c->dec_host) (void)hipHostFree(c->dec_host);
     for (auto& q : c->spec_q) { (void)hipEventDestroy(q.ev0); (void)hipEventDestroy(q.ev1); (void)hipEventDestroy(q.ev); }
     for (hipEvent_t e : c->spec_free) (void)hipEventDestroy(e);
@@ -2082,8 +2087,10 @@ extern "C" int l3_greedy_generate_values_host(l3_ctx* c, const int64_t* ids_host
 // follow a row's real tokens, so every real position is computed as if the row ran alone) with the
 // lm_head reading each row's own last position and the pads' K / V slots cleared afterwards; the
 // decode steps keep every row's position, id and finished flag on the device (ragged.hip).
-enum RagWord : int { RAG_POS = 0, RAG_CUR, RAG_FIN, RAG_NOUT, RAG_LEN, RAG_BUDGET, RAG_ROWS, RAG_TOK };
-static_assert(RAG_TOK + 1 == l3_ctx::RAG_WORDS, "one array of max_batch_size words per RagWord");
+enum RagWord : int {
+    RAG_POS = 0, RAG_CUR, RAG_FIN, RAG_NOUT, RAG_LEN, RAG_BUDGET, RAG_ROWS, RAG_TOK, RAG_EXT_START, RAG_EXT_LEN
+};
+static_assert(RAG_EXT_LEN + 1 == l3_ctx::RAG_WORDS, "one array of max_batch_size words per RagWord");
 
 static int32_t* rag_word(l3_ctx* c, int w) { return c->rag_state + (int64_t)w * c->d.max_batch_size; }
 
@@ -2287,20 +2294,149 @@ static int ragged_choose(l3_ctx* c, const RaggedState& st, int B) {
     return 0;
 }
 
-extern "C" int l3_ragged_generate_host(l3_ctx* c, const int64_t* ids_host, const int32_t* lens, int32_t B,
-                                       int32_t Lmax, int32_t max_new_tokens, const int64_t* stop_ids,
-                                       int32_t n_stop, int64_t* out_ids_host, int32_t* out_lens) {
-    CHECK_CTX(c);
-    const char* who = "l3_ragged_generate_host";
-    if (!out_lens || n_stop < 0 || (n_stop > 0 && !stop_ids)) return fail("%s: null argument", who);
+// ---------------------------------------------------------------------------------------
+// Ragged continuation (DESIGN.md "Ragged continuation"): row b's lens[b] new tokens run at
+// positions [starts[b], starts[b] + lens[b]) and attend to the row's cache as it stands
+// (llama3.py:285-308 with start_pos = starts[b], one row at a time).
+static int ragged_shape_check(const l3_ctx* c, const char* who) {
+    if (!attn_decode_ragged_shape_ok(c->d.n_heads, c->d.n_kv_heads, c->HD))
+        return fail("%s: the ragged attention takes at most %d query heads per KV head and head sizes 16, 32, 48, "
+                    "64, 96, 128 (%d heads per KV head, head size %d)", who, RAGGED_MAX_REP,
+                    c->d.n_heads / c->d.n_kv_heads, c->HD);
+    return 0;
+}
+
+// everything an extend can be refused for, before anything is allocated or launched
+static int ragged_extend_check(l3_ctx* c, const char* who, const int64_t* ids_host, const int32_t* lens,
+                               const int32_t* starts, int B, int Lmax) {
+    if (!starts) return fail("%s: null argument", who);
     if (ragged_check(c, who, ids_host, lens, B, Lmax)) return 1;
+    for (int b = 0; b < B; ++b) {
+        if (starts[b] < 0) return fail("%s: starts[%d] = %d is negative", who, b, starts[b]);
+        if ((int64_t)starts[b] + lens[b] > c->d.max_seq_len)
+            return fail("%s: row %d: positions [%d, %lld) exceed max_seq_len %d", who, b, starts[b],
+                        (long long)starts[b] + lens[b], c->d.max_seq_len);
+    }
+    return ragged_shape_check(c, who);
+}
+
+// the chunk's raw QKV rows: allocated on first use, grown as needed, freed with the context; a
+// refused allocation is reported before any launch
+static int ragged_extend_ws(l3_ctx* c, const char* who, int64_t rows) {
+    const int64_t n = rows * c->qkvn;
+    if (n <= c->rag_ext_qkv_n) return 0;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    dfree(c->rag_ext_qkv);
+    c->rag_ext_qkv = nullptr;
+    c->rag_ext_qkv_n = 0;
+    if (hipMalloc(&c->rag_ext_qkv, (size_t)n * 4) != hipSuccess) {
+        (void)hipGetLastError();  // clear the sticky error: the next launch check must not see it
+        c->rag_ext_qkv = nullptr;
+        return fail("%s: the raw QKV rows of the chunk (%lld bytes: %lld rows x %d) could not be allocated", who,
+                    (long long)n * 4, (long long)rows, c->qkvn);
+    }
+    c->rag_ext_qkv_n = n;
+    return 0;
+}
+
+// The extend on the padded chunk [B, Lmax]: the per-row state uploaded (T_b = starts[b] + lens[b]
+// in the prompt length's place, so the decode loop continues from it), then per layer the raw QKV
+// rows (layer 0 from the embedding rows; pads a valid id), the append and the attention
+// (ragged_extend.hip), O-proj, gate|up and down at M = B * Lmax; row b's logits from its chunk
+// position lens[b] - 1 into c->logits.  No slot outside [starts[b], T_b) is written.
+// max_new_tokens: the generate loop's (0: an extend only).
+static int ragged_extend_run(l3_ctx* c, const int64_t* ids_host, const int32_t* lens, const int32_t* starts, int B,
+                             int Lmax, int max_new_tokens) {
+    const int64_t mb = c->d.max_batch_size;
+    c->rag_ids_host.assign((size_t)B * Lmax, 0);  // pads become a valid id
+    c->rag_host.assign((size_t)(l3_ctx::RAG_WORDS * mb + 4), 0);
+    for (int b = 0; b < B; ++b) {
+        for (int t = 0; t < lens[b]; ++t) c->rag_ids_host[(size_t)b * Lmax + t] = ids_host[(int64_t)b * Lmax + t];
+        int32_t* h = c->rag_host.data() + b;
+        const int T = starts[b] + lens[b];
+        h[RAG_POS * mb] = T - 1;  // the position the first token is chosen (and drawn) at
+        h[RAG_LEN * mb] = T;
+        h[RAG_BUDGET * mb] = max_new_tokens - T;
+        h[RAG_FIN * mb] = max_new_tokens - T <= 0;
+        h[RAG_ROWS * mb] = b * Lmax + lens[b] - 1;
+        h[RAG_EXT_START * mb] = starts[b];
+        h[RAG_EXT_LEN * mb] = lens[b];
+    }
+    if (upload_ids(c, c->rag_ids_host.data(), (int64_t)B * Lmax)) return 1;
+    HIP_TRY(hipMemcpyAsync(c->rag_state, c->rag_host.data(), c->rag_host.size() * 4, hipMemcpyHostToDevice, c->stream));
+    const int D = c->d.dim, FD = c->d.hidden_dim, T = B * Lmax;
+    hipStream_t s = c->stream;
+    for (size_t li = 0; li < c->layers.size(); ++li) {
+        Layer& Ly = c->layers[li];
+        GemmArgs g{};  // rmsnorm -> QKV, raw
+        g.eps = c->d.norm_eps;
+        g.A = c->h; g.lda = D; g.W = Ly.wqkv; g.C = c->rag_ext_qkv; g.ldc = c->qkvn;
+        g.M = T; g.N = c->qkvn; g.K = D; g.norm = true;
+        g.Wb = Ly.wqkvb; g.norm_w = Ly.wqkvb ? Ly.n_attn : nullptr;
+        g.ws = c->skws; g.ws_cap = c->skws_cap;
+        if (li == 0) { g.A = c->emb; g.a_rows = c->ids; }
+        if (timed(c, L3_K_QKV, [&] { return gemm(c, EPI_STORE, g, s); })) return 1;
+        ExtendAttnArgs a{};
+        a.qkv = c->rag_ext_qkv; a.cache_k = Ly.cache_k; a.cache_v = Ly.cache_v; a.out = c->attn;
+        a.rope_cos = c->rope_cos; a.rope_sin = c->rope_sin;
+        a.starts = rag_word(c, RAG_EXT_START); a.lens = rag_word(c, RAG_EXT_LEN);
+        a.B = B; a.Lq = Lmax; a.H = c->d.n_heads; a.KVH = c->d.n_kv_heads; a.HD = c->HD; a.Smax = c->d.max_seq_len;
+        a.q_scale = (float)(1.4426950408889634 / std::sqrt((double)c->HD));
+        if (timed(c, L3_K_ATTN, [&] { return launch_attn_extend_ragged(a, s); })) return 1;
+        GemmArgs o{};  // O-proj + residual (layer 0: h = emb[ids] + attn . Wo^T)
+        o.A = c->attn; o.lda = c->qdim; o.W = Ly.wo; o.W3 = Ly.wo3; o.Wb = Ly.wob; o.C = c->h; o.ldc = D;
+        o.M = T; o.N = D; o.K = c->qdim; o.norm = false;
+        o.ws = c->skws; o.ws_cap = c->skws_cap;
+        if (li == 0) { o.res_src = c->emb; o.res_rows = c->ids; }
+        if (timed(c, L3_K_OPROJ, [&] { return gemm(c, EPI_RESID, o, s); })) return 1;
+        GemmArgs gu{};  // rmsnorm -> gate|up -> SwiGLU
+        gu.A = c->h; gu.lda = D; gu.W = Ly.wgu; gu.W3 = Ly.wgu3; gu.C = c->hid; gu.ldc = FD;
+        gu.M = T; gu.N = 2 * FD; gu.K = D; gu.norm = true; gu.eps = c->d.norm_eps;
+        gu.Wb = Ly.wgub; gu.norm_w = Ly.wgub ? Ly.n_ffn : nullptr;
+        GemmArgs dn{};  // down + residual
+        dn.A = c->hid; dn.lda = FD; dn.W = Ly.wd; dn.W3 = Ly.wd3; dn.Wb = Ly.wdb; dn.C = c->h; dn.ldc = D;
+        dn.M = T; dn.N = D; dn.K = FD; dn.norm = false;
+        gu.ws = dn.ws = c->skws; gu.ws_cap = dn.ws_cap = c->skws_cap;
+        if (timed(c, L3_K_GATEUP, [&] { return gemm(c, EPI_SWIGLU, gu, s); })) return 1;
+        if (timed(c, L3_K_DOWN, [&] { return gemm(c, EPI_RESID, dn, s); })) return 1;
+    }
+    GemmArgs lm = lm_head_args(c, B, 1, c->logits, 0);  // A row b = h row b * Lmax + lens[b] - 1
+    lm.a_rows = rag_word(c, RAG_ROWS);
+    return timed(c, L3_K_LMHEAD, [&] { return gemm(c, EPI_STORE, lm, s); });
+}
+
+extern "C" int l3_ragged_extend_host(l3_ctx* c, const int64_t* ids_host, const int32_t* lens, const int32_t* starts,
+                                     int32_t B, int32_t Lmax, float* logits_host) {
+    CHECK_CTX(c);
+    const char* who = "l3_ragged_extend_host";
+    if (!logits_host) return fail("%s: null argument", who);
+    if (ragged_extend_check(c, who, ids_host, lens, starts, B, Lmax)) return 1;
+    if (set_dev(c) || spec_resolve(c)) return 1;
+    if (ragged_extend_ws(c, who, (int64_t)B * Lmax) || ensure_ws(c, B, Lmax) || ragged_bufs(c)) return 1;
+    if (ragged_extend_run(c, ids_host, lens, starts, B, Lmax, 0)) return 1;
+    HIP_TRY(hipMemcpyAsync(logits_host, c->logits, (size_t)B * c->d.vocab_size * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// The generate loop of l3_ragged_generate_host (starts null: the prefill at position 0, its code
+// path as it always was) and of l3_ragged_generate_from_host (the extend, T_b = starts[b] + lens[b]
+// in the prompt length's place)
+static int ragged_generate(l3_ctx* c, const char* who, const int64_t* ids_host, const int32_t* lens,
+                           const int32_t* starts, int32_t B, int32_t Lmax, int32_t max_new_tokens,
+                           const int64_t* stop_ids, int32_t n_stop, int64_t* out_ids_host, int32_t* out_lens) {
+    if (!out_lens || n_stop < 0 || (n_stop > 0 && !stop_ids)) return fail("%s: null argument", who);
+    if (starts ? ragged_extend_check(c, who, ids_host, lens, starts, B, Lmax)
+               : ragged_check(c, who, ids_host, lens, B, Lmax))
+        return 1;
     // the last decode step runs at position max_new_tokens - 1, which must be a cache slot
     // (the reference fails there with a broadcast error, llama3.py:184)
     if (max_new_tokens > c->d.max_seq_len)
         return fail("generate: last decode position %d exceeds max_seq_len %d", max_new_tokens - 1, c->d.max_seq_len);
-    int min_len = lens[0];
+    int min_len = lens[0] + (starts ? starts[0] : 0);
     for (int b = 0; b < B; ++b) {
-        min_len = lens[b] < min_len ? lens[b] : min_len;
+        const int T = lens[b] + (starts ? starts[b] : 0);
+        min_len = T < min_len ? T : min_len;
         out_lens[b] = 0;
     }
     const int cap = max_new_tokens - min_len;
@@ -2318,6 +2454,7 @@ extern "C" int l3_ragged_generate_host(l3_ctx* c, const int64_t* ids_host, const
     if (split && chunk == 0) return fail("%s: no split-KV chunk length fits the attention's LDS budget", who);
     if (set_dev(c) || spec_resolve(c)) return 1;
     if (split && ragged_split_ws(c, who, attn_decode_split_n(s_cap, chunk))) return 1;
+    if (starts && ragged_extend_ws(c, who, (int64_t)B * Lmax)) return 1;
     if (ensure_ws(c, B, Lmax) || ragged_bufs(c)) return 1;
     const int64_t n_out_ids = (int64_t)B * cap;
     if (n_out_ids > c->rag_out_n) {
@@ -2344,7 +2481,16 @@ extern "C" int l3_ragged_generate_host(l3_ctx* c, const int64_t* ids_host, const
         HIP_TRY(hipMemcpy(c->rag_stop, stops.data(), stops.size() * 4, hipMemcpyHostToDevice));
     }
     HIP_TRY(hipMemsetAsync(c->rag_out, 0xFF, (size_t)n_out_ids * 4, c->stream));  // -1
-    if (ragged_prefill(c, ids_host, lens, B, Lmax, max_new_tokens)) return 1;
+    if (!starts) {
+        if (ragged_prefill(c, ids_host, lens, B, Lmax, max_new_tokens)) return 1;
+    } else {
+        if (ragged_extend_run(c, ids_host, lens, starts, B, Lmax, max_new_tokens)) return 1;
+        // slot T_b, which the loop never writes and every later step attends: a row run alone on a
+        // cache that is zero past its frontier finds zero there, whatever an earlier call left
+        for (auto& Ly : c->layers)
+            HIP_TRY(launch_ragged_zero_slot(Ly.cache_k, Ly.cache_v, rag_word(c, RAG_LEN), rag_word(c, RAG_BUDGET), B,
+                                            c->d.n_kv_heads, c->d.max_seq_len, c->HD, c->stream));
+    }
     RaggedState st{};
     st.pos = rag_word(c, RAG_POS); st.cur_id = rag_word(c, RAG_CUR); st.finished = rag_word(c, RAG_FIN);
     st.n_out = rag_word(c, RAG_NOUT); st.len = rag_word(c, RAG_LEN); st.budget = rag_word(c, RAG_BUDGET);
@@ -2369,6 +2515,25 @@ extern "C" int l3_ragged_generate_host(l3_ctx* c, const int64_t* ids_host, const
     for (int64_t i = 0; i < n_out_ids; ++i) out_ids_host[i] = all[(size_t)i];
     for (int b = 0; b < B; ++b) out_lens[b] = n_out[(size_t)b];
     return 0;
+}
+
+extern "C" int l3_ragged_generate_host(l3_ctx* c, const int64_t* ids_host, const int32_t* lens, int32_t B,
+                                       int32_t Lmax, int32_t max_new_tokens, const int64_t* stop_ids,
+                                       int32_t n_stop, int64_t* out_ids_host, int32_t* out_lens) {
+    CHECK_CTX(c);
+    return ragged_generate(c, "l3_ragged_generate_host", ids_host, lens, nullptr, B, Lmax, max_new_tokens, stop_ids,
+                           n_stop, out_ids_host, out_lens);
+}
+
+extern "C" int l3_ragged_generate_from_host(l3_ctx* c, const int64_t* ids_host, const int32_t* lens,
+                                            const int32_t* starts, int32_t B, int32_t Lmax, int32_t max_new_tokens,
+                                            const int64_t* stop_ids, int32_t n_stop, int64_t* out_ids_host,
+                                            int32_t* out_lens) {
+    CHECK_CTX(c);
+    const char* who = "l3_ragged_generate_from_host";
+    if (!starts) return fail("%s: null argument", who);
+    return ragged_generate(c, who, ids_host, lens, starts, B, Lmax, max_new_tokens, stop_ids, n_stop, out_ids_host,
+                           out_lens);
 }
 
 extern "C" int l3_layer_forward_host(l3_ctx* c, int32_t layer, const float* x_host, int32_t B,
@@ -2612,6 +2777,94 @@ extern "C" int l3_op_attn_decode_ragged_host(l3_ctx* c, const float* qkv, float*
     D2H(cache_k, dk, nc);
     D2H(cache_v, dv, nc);
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// The two launches of a ragged extend on plain arrays (ragged_extend.hip): the append of the new
+// keys / values, then the attention.  cache_k / cache_v [B, KVH, Smax, HD] are copied in and, with
+// slots [starts[b], starts[b] + lens[b]) written, back out; lens[b] may be 0 (an all-pad row).
+extern "C" int l3_op_attn_extend_ragged_host(l3_ctx* c, const float* qkv, float* cache_k, float* cache_v,
+                                             const float* rope_cos, const float* rope_sin, const int32_t* starts,
+                                             const int32_t* lens, int32_t B, int32_t Lq, int32_t H, int32_t KVH,
+                                             int32_t HD, int32_t Smax, float* out) {
+    CHECK_CTX(c);
+    const char* who = "l3_op_attn_extend_ragged";
+    if (!qkv || !cache_k || !cache_v || !rope_cos || !rope_sin || !starts || !lens || !out)
+        return fail("%s: null argument", who);
+    if (B < 1 || B > 65535 || Lq < 1 || Smax < 1)
+        return fail("%s: bad shape (B %d, Lq %d, Smax %d)", who, B, Lq, Smax);
+    if (!attn_decode_ragged_shape_ok(H, KVH, HD))
+        return fail("%s: the ragged attention takes at most %d query heads per KV head and head sizes 16, 32, 48, "
+                    "64, 96, 128 (H %d, KVH %d, head size %d)", who, RAGGED_MAX_REP, H, KVH, HD);
+    for (int b = 0; b < B; ++b) {
+        if (lens[b] < 0 || lens[b] > Lq) return fail("%s: lens[%d] = %d outside [0, %d]", who, b, lens[b], Lq);
+        if (starts[b] < 0) return fail("%s: starts[%d] = %d is negative", who, b, starts[b]);
+        if ((int64_t)starts[b] + lens[b] > Smax || starts[b] >= Smax)
+            return fail("%s: row %d: positions [%d, %lld) exceed Smax %d", who, b, starts[b],
+                        (long long)starts[b] + lens[b], Smax);
+    }
+    if (set_dev(c)) return 1;
+    const int64_t nq = (int64_t)B * Lq * (H + 2 * KVH) * HD, nc = (int64_t)B * KVH * Smax * HD;
+    const int64_t nt = (int64_t)Smax * (HD / 2), no = (int64_t)B * Lq * H * HD;
+    Scratch S{c};
+    SCRATCH(dq, nq);
+    SCRATCH(dk, nc);
+    SCRATCH(dv, nc);
+    SCRATCH(dc, nt);
+    SCRATCH(ds, nt);
+    SCRATCH(dst, B);
+    SCRATCH(dl, B);
+    SCRATCH(dout, no);
+    H2D(dq, qkv, nq);
+    H2D(dk, cache_k, nc);
+    H2D(dv, cache_v, nc);
+    H2D(dc, rope_cos, nt);
+    H2D(ds, rope_sin, nt);
+    H2D(dst, starts, B);
+    H2D(dl, lens, B);
+    ExtendAttnArgs a{};
+    a.qkv = dq; a.cache_k = dk; a.cache_v = dv; a.out = dout; a.rope_cos = dc; a.rope_sin = ds;
+    a.starts = reinterpret_cast<const int32_t*>(dst); a.lens = reinterpret_cast<const int32_t*>(dl);
+    a.B = B; a.Lq = Lq; a.H = H; a.KVH = KVH; a.HD = HD; a.Smax = Smax;
+    a.q_scale = (float)(1.4426950408889634 / std::sqrt((double)HD));
+    if (timed(c, L3_K_ATTN, [&] { return launch_attn_extend_ragged(a, c->stream); })) return 1;
+    D2H(out, dout, no);
+    D2H(cache_k, dk, nc);
+    D2H(cache_v, dv, nc);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// The fork of a cache row (DESIGN.md "Ragged continuation"): slots [0, n_slots) of K and V in every
+// layer from row src_row to each row of dst_rows — one small copy kernel per layer on the
+// context's stream (ragged_extend.hip cache_copy_rows_kernel)
+extern "C" int l3_cache_copy_rows(l3_ctx* c, int32_t src_row, const int32_t* dst_rows, int32_t n_dst,
+                                  int32_t n_slots) {
+    CHECK_CTX(c);
+    const char* who = "l3_cache_copy_rows";
+    if (n_dst < 0 || (n_dst > 0 && !dst_rows)) return fail("%s: null argument", who);
+    if (need_model(c)) return 1;
+    if (c->group && group_members(c->group) > 1)
+        return fail("%s: this context is a member of a multi-device l3_group (not supported)", who);
+    const int mb = c->d.max_batch_size;
+    if (src_row < 0 || src_row >= mb) return fail("%s: src_row %d outside [0, %d)", who, src_row, mb);
+    if (n_dst > mb) return fail("%s: n_dst %d exceeds max_batch_size %d", who, n_dst, mb);
+    for (int i = 0; i < n_dst; ++i) {
+        if (dst_rows[i] < 0 || dst_rows[i] >= mb)
+            return fail("%s: dst_rows[%d] = %d outside [0, %d)", who, i, dst_rows[i], mb);
+        if (dst_rows[i] == src_row) return fail("%s: dst_rows[%d] is src_row %d", who, i, src_row);
+    }
+    if (n_slots < 0 || n_slots > c->d.max_seq_len)
+        return fail("%s: n_slots %d outside [0, %d]", who, n_slots, c->d.max_seq_len);
+    if (set_dev(c) || spec_resolve(c)) return 1;
+    if (n_dst == 0 || n_slots == 0) return 0;
+    if (ragged_bufs(c)) return 1;
+    int32_t* dst_dev = rag_word(c, RAG_TOK);  // free between calls: a step's token choice writes it
+    HIP_TRY(hipMemcpyAsync(dst_dev, dst_rows, (size_t)n_dst * 4, hipMemcpyHostToDevice, c->stream));
+    for (auto& Ly : c->layers)
+        HIP_TRY(launch_cache_copy_rows(Ly.cache_k, Ly.cache_v, src_row, dst_dev, n_dst, c->d.n_kv_heads,
+                                       c->d.max_seq_len, c->HD, n_slots, mb, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // dst_rows is the caller's: read before the return
     return 0;
 }
 
@@ -2954,6 +3207,7 @@ extern "C" int l3_device_check_counts(l3_ctx* c, uint32_t* counts, int32_t* enab
     HIP_TRY(dcheck_collect_score(n));
     HIP_TRY(dcheck_collect_persist(n));
     HIP_TRY(dcheck_collect_ragged(n));
+    HIP_TRY(dcheck_collect_extend(n));
     for (int i = 0; i < CHK_N; ++i) counts[i] = n[i];
     return 0;
 }

@@ -72,6 +72,11 @@ _SIGNATURES = {
     "l3_ragged_attn_info": (ctypes.c_int, [_P, _P, _P, _P, _P]),
     "l3_op_attn_decode_ragged_host": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32,
                                                      _I32, _I32, _P]),
+    "l3_ragged_extend_host": (ctypes.c_int, [_P, _P, _P, _P, _I32, _I32, _P]),
+    "l3_ragged_generate_from_host": (ctypes.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _P, _I32, _P, _P]),
+    "l3_cache_copy_rows": (ctypes.c_int, [_P, _I32, _P, _I32, _I32]),
+    "l3_op_attn_extend_ragged_host": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32,
+                                                     _I32, _P]),
     "l3_attention_forward_host": (ctypes.c_int, [_P, _I32, _P, _I32, _I32, _I32, _P]),
     "l3_op_softmax_host": (ctypes.c_int, [_P, _P, _I64, _I64, _P]),
     "l3_op_argmax_host": (ctypes.c_int, [_P, _P, _I64, _I64, _P]),
@@ -398,22 +403,86 @@ class Context:
         check(lib().l3_ragged_forward_host(self._h, ptr(ids), ptr(lens), B, Lmax, ptr(out)))
         return out
 
-    def ragged_generate(self, ids: np.ndarray, lens, max_new_tokens: int, stop_ids=()):
+    @staticmethod
+    def _ragged_starts(starts, B):
+        starts = np.ascontiguousarray(starts, dtype=np.int32)
+        if starts.shape != (B,):
+            raise ValueError(f"starts {starts.shape} must be [{B}]")
+        return starts
+
+    def ragged_extend(self, ids: np.ndarray, lens, starts) -> np.ndarray:
+        """Several new tokens per row, each row at its own offset (l3_ragged_extend_host): row b's
+        ``lens[b]`` tokens of ``ids`` [B, Lmax] (right-padded, pads ignored) run at positions
+        ``[starts[b], starts[b] + lens[b])`` over the row's cache as it stands; float32 [B, VS],
+        row b the logits of its last new token.  No other cache slot changes."""
+        ids, lens = self._ragged_args(ids, lens)
+        B, Lmax = ids.shape
+        starts = self._ragged_starts(starts, B)
+        out = pinned.empty((B, self.dims.vocab_size), np.float32)
+        check(lib().l3_ragged_extend_host(self._h, ptr(ids), ptr(lens), ptr(starts), B, Lmax, ptr(out)))
+        return out
+
+    def ragged_generate(self, ids: np.ndarray, lens, max_new_tokens: int, stop_ids=(), starts=None):
         """The device-side decode loop over rows of different lengths (l3_ragged_generate_host):
         (out int64 [B, max_new_tokens - min(lens)], out_lens int32 [B]); row b holds
         ``out_lens[b]`` tokens — at most ``max_new_tokens - lens[b]``, fewer when it emitted one of
         ``stop_ids`` (kept as its last token) — and -1 after them.  Sampled when ``set_sampling``
-        is on, with the uniforms of (seed, row, position)."""
+        is on, with the uniforms of (seed, row, position).  With ``starts`` [B]
+        (l3_ragged_generate_from_host) the rows continue from their caches: ``ids`` run at
+        ``starts[b]`` on, and ``starts[b] + lens[b]`` stands in the length's place everywhere.
+        When no row of the batch has a token to emit (``max_new_tokens <= starts[b] + lens[b]`` for
+        every b) the call runs nothing, as without ``starts``: the new tokens are NOT appended to
+        the caches then — use ``ragged_extend`` to append without generating."""
         ids, lens = self._ragged_args(ids, lens)
         B, Lmax = ids.shape
         stops = np.ascontiguousarray(list(stop_ids), dtype=np.int64).reshape(-1)
-        cap = max(0, int(max_new_tokens) - int(lens.min())) if B else 0
+        if starts is not None:
+            starts = self._ragged_starts(starts, B)
+        total = lens if starts is None else lens.astype(np.int64) + starts
+        cap = max(0, int(max_new_tokens) - int(total.min())) if B else 0
         out = np.full((B, cap), -1, np.int64)
         out_lens = np.zeros(B, np.int32)
-        check(lib().l3_ragged_generate_host(self._h, ptr(ids), ptr(lens), B, Lmax, int(max_new_tokens),
-                                            ptr(stops) if stops.size else None, int(stops.size),
-                                            ptr(out), ptr(out_lens)))
+        tail = (B, Lmax, int(max_new_tokens), ptr(stops) if stops.size else None, int(stops.size), ptr(out),
+                ptr(out_lens))
+        if starts is None:
+            check(lib().l3_ragged_generate_host(self._h, ptr(ids), ptr(lens), *tail))
+        else:
+            check(lib().l3_ragged_generate_from_host(self._h, ptr(ids), ptr(lens), ptr(starts), *tail))
         return out, out_lens
+
+    def cache_copy_rows(self, src: int, dst_rows, n_slots: int) -> None:
+        """The fork of a cache row (l3_cache_copy_rows): slots ``[0, n_slots)`` of K and V in every
+        layer from row ``src`` to each row of ``dst_rows``."""
+        dst = np.ascontiguousarray(list(dst_rows), dtype=np.int32).reshape(-1)
+        check(lib().l3_cache_copy_rows(self._h, int(src), ptr(dst) if dst.size else None, int(dst.size), int(n_slots)))
+
+    def op_attn_extend_ragged(self, qkv, cache_k, cache_v, rope_cos, rope_sin, starts, lens, n_heads: int):
+        """The two launches of a ragged extend on plain arrays (l3_op_attn_extend_ragged_host):
+        ``qkv`` [B, Lq, (H + 2 KVH) * HD] raw rows, ``cache_k`` / ``cache_v`` [B, KVH, Smax, HD],
+        ``rope_cos`` / ``rope_sin`` [Smax, HD/2], ``starts`` / ``lens`` [B].  Returns
+        (out [B, Lq, H * HD], cache_k, cache_v) — the caches are copies with slots
+        ``[starts[b], starts[b] + lens[b])`` written."""
+        ck = np.array(cache_k, dtype=np.float32, order="C")
+        cv = np.array(cache_v, dtype=np.float32, order="C")
+        if ck.ndim != 4 or cv.shape != ck.shape:
+            raise ValueError(f"cache_k {ck.shape} / cache_v {cv.shape} must be [B, KVH, Smax, HD]")
+        B, KVH, Smax, HD = ck.shape
+        H = int(n_heads)
+        qkv = np.ascontiguousarray(qkv, dtype=np.float32)
+        c = np.ascontiguousarray(rope_cos, dtype=np.float32)
+        s = np.ascontiguousarray(rope_sin, dtype=np.float32)
+        starts = np.ascontiguousarray(starts, dtype=np.int32)
+        lens = np.ascontiguousarray(lens, dtype=np.int32)
+        if qkv.ndim != 3 or qkv.shape[0] != B or qkv.shape[2] != (H + 2 * KVH) * HD or c.shape != (Smax, HD // 2) \
+                or s.shape != c.shape:
+            raise ValueError(f"qkv {qkv.shape} / rope tables {c.shape} do not match the caches {ck.shape}")
+        if starts.shape != (B,) or lens.shape != (B,):
+            raise ValueError(f"starts {starts.shape} and lens {lens.shape} must be [{B}]")
+        Lq = qkv.shape[1]
+        out = np.empty((B, Lq, H * HD), np.float32)
+        check(lib().l3_op_attn_extend_ragged_host(self._h, ptr(qkv), ptr(ck), ptr(cv), ptr(c), ptr(s), ptr(starts),
+                                                  ptr(lens), B, Lq, H, KVH, HD, Smax, ptr(out)))
+        return out, ck, cv
 
     def set_ragged_attn_split(self, mode: int, chunk: int = 0) -> None:
         """Extension (l3_set_ragged_attn_split): the split-KV decode attention of the ragged

@@ -496,7 +496,26 @@ class Llama:
         ids, lens = self._ragged(prompts)
         return self._ctx.ragged_forward(ids, lens)[:, None, :]
 
-    def generate_ragged(self, prompts, max_new_tokens: int, stop_ids=()):
+    def extend_ragged(self, chunks, start_pos) -> np.ndarray:
+        """Extension (DESIGN.md "Ragged continuation"): ``__call__`` for rows that continue at
+        different positions, in one batch: ``chunks[b]`` (new tokens of row b) runs at positions
+        ``start_pos[b]`` on and attends to cache row b as it stands.  Returns float32
+        ``[B, 1, VS]``: row b holds the logits of its last new token, as
+        ``model(chunks[b][None], start_pos[b])`` gives on that row alone.  Only the slots
+        ``[start_pos[b], start_pos[b] + len(chunks[b]))`` of the cache change.  Not for a model on
+        more than one device."""
+        ids, lens = self._ragged(chunks)
+        return self._ctx.ragged_extend(ids, lens, start_pos)[:, None, :]
+
+    def fork_cache(self, src_row: int, dst_rows, n_slots: int) -> None:
+        """Extension (DESIGN.md "Ragged continuation"): cache slots ``[0, n_slots)`` of batch row
+        ``src_row`` copied to each row of ``dst_rows`` in every layer, so a prefix prefilled once
+        serves many rows.  Not for a model on more than one device."""
+        if self._group is not None and self._group.n > 1:
+            raise NotImplementedError("ragged batches on a multi-device model: not implemented")
+        self._ctx.cache_copy_rows(src_row, dst_rows, n_slots)
+
+    def generate_ragged(self, prompts, max_new_tokens: int, stop_ids=(), start_pos=None, prefix=None):
         """Extension (DESIGN.md "Ragged batches"): ``generate_all`` for prompts of different
         lengths, as one device-side loop.  Returns one int64 array per row: what ``generate``
         yields for that row alone on a zeroed cache (the reference's schedule, decode hole
@@ -507,9 +526,28 @@ class Llama:
         the single-pass decode attention's scores no longer fit its LDS (past about 2 800 positions
         at four query heads per KV head) the split-KV kernels run instead (DESIGN.md "Split-KV
         decode attention"; ``context.set_ragged_attn_split`` forces them or sets the chunk).  Not
-        for a model on more than one device."""
+        for a model on more than one device.
+
+        Continuation (DESIGN.md "Ragged continuation"): with ``start_pos`` (one int per row) row b's
+        ``prompts[b]`` are new tokens at positions ``start_pos[b]`` on, attending to cache row b
+        as earlier calls left it, and the row yields what ``generate`` yields for its whole history
+        plus ``prompts[b]`` — ``max_new_tokens - start_pos[b] - len(prompts[b])`` ids.  With
+        ``prefix`` (a sequence of ids every row begins with; not together with ``start_pos``) the
+        prefix is prefilled once on row 0, its cache slots are forked to the other rows, and the
+        rows generate from ``start_pos = len(prefix)``: the ids of ``prefix + prompts[b]``.
+        A call in which no row has a token left to emit runs nothing and leaves the caches as they
+        were (``prompts`` are not appended; with ``prefix`` only the prefix is): to append without
+        generating, call ``extend_ragged``."""
         ids, lens = self._ragged(prompts)
-        out, n = self._ctx.ragged_generate(ids, lens, int(max_new_tokens), stop_ids)
+        if prefix is not None:
+            if start_pos is not None:
+                raise ValueError("pass start_pos or prefix, not both")
+            pre = np.asarray(prefix, dtype=np.int64).reshape(-1)
+            if pre.size:
+                self(pre[None], 0)
+                self.fork_cache(0, range(1, len(lens)), pre.size)
+            start_pos = [pre.size] * len(lens)
+        out, n = self._ctx.ragged_generate(ids, lens, int(max_new_tokens), stop_ids, starts=start_pos)
         return [out[b, :n[b]].copy() for b in range(len(n))]
 
 
