@@ -338,6 +338,53 @@ int l3_ragged_generate_from_host(l3_ctx* ctx, const int64_t* ids_host, const int
  * [0, max_seq_len], a member of a multi-device l3_group. */
 int l3_cache_copy_rows(l3_ctx* ctx, int32_t src_row, const int32_t* dst_rows, int32_t n_dst, int32_t n_slots);
 
+/* ---- speculative decoding with lookup drafts (extension; DESIGN.md "Speculative decoding") ---- */
+/* l3_ragged_generate_host (starts NULL) or l3_ragged_generate_from_host (starts given) with the
+ * decode steps replaced by speculative iterations: the same arguments give the same out_ids_host,
+ * out_lens and cap, greedy or sampled.  The prefill, each row's first token and (with starts) the
+ * zeroing of slot T_b are that call's.  Then, for every unfinished row b that has emitted m >= 1
+ * of its R_b = max_new_tokens - T_b tokens, an iteration
+ *   - drafts: with S = lookup_b ++ (the row's ids_host tokens) ++ (its emitted tokens) of length E,
+ *     for n = min(ngram_max, E - 1) down to ngram_min it looks for the largest j in [0, E - n - 1]
+ *     with S[j : j + n] == S[E - n : E]; at the first n that has one the draft is
+ *     S[j + n : min(j + n + k, E)] with k = min(draft_len, R_b - m - 1), otherwise it is empty;
+ *   - runs the chunk [last emitted token, draft...] (1 + d tokens) as one extend at positions
+ *     T_b + m onward (the reference's schedule: slot T_b is never written);
+ *   - picks the token of every chunk position from that position's logits by the ordinary rule:
+ *     l3_op_argmax_host's, or with sampling on l3_set_sampling's with the uniform of (seed, b,
+ *     position);
+ *   - accepts the longest prefix of the draft whose tokens equal those picks, emits the picks of
+ *     the accepted positions and of the one after them, cut after the first stop id (which ends
+ *     the row and stays its last id), and moves the row on by the number emitted.
+ * lookup_host [B, Lk] int64 with lookup_lens [B] in [0, Lk] is an optional reference text per row
+ * (a previous answer, a document being edited); NULL: none, lookup_lens and Lk are not read.
+ * draft_len in [0, 15] (0: plain decoding through the chunk path), 1 <= ngram_min <= ngram_max <= 8.
+ * row_steps / drafted / accepted [B] int32, each may be NULL: the iterations in which the row ran
+ * a chunk, the draft tokens it ran, and those accepted (counted before the stop-id cut).
+ * K / V of rejected draft positions stay in the cache past the accepted frontier, and no later
+ * chunk attends a slot before writing it; after the call the slots past a row's last emitted
+ * position hold unspecified values.  The "rows still running" word is read after every iteration
+ * from the first one at which the longest row can have spent its budget (with stop ids also every
+ * 4th iteration before that); at most cap - 1 iterations run.
+ * Errors, all reported before anything is launched: everything both generate calls refuse;
+ * draft_len, ngram_min or ngram_max out of range (checked before the context), Lk < 0, a
+ * lookup_lens[b] outside [0, Lk], a lookup id outside [0, VS) within lookup_lens[b]; a workspace
+ * (B * (1 + draft_len) logits rows, the raw QKV rows of the chunks) that cannot be allocated. */
+int l3_ragged_generate_spec_host(l3_ctx* ctx, const int64_t* ids_host, const int32_t* lens, const int32_t* starts,
+                                 int32_t B, int32_t Lmax, int32_t max_new_tokens, const int64_t* stop_ids,
+                                 int32_t n_stop, const int64_t* lookup_host, const int32_t* lookup_lens,
+                                 int32_t Lk, int32_t draft_len, int32_t ngram_max, int32_t ngram_min,
+                                 int64_t* out_ids_host, int32_t* out_lens, int32_t* row_steps, int32_t* drafted,
+                                 int32_t* accepted);
+/* The verification of caller-supplied chunks: l3_ragged_extend_host (same cache effect, same
+ * errors) that returns, instead of the last logits, the token picked at every real chunk position
+ * by the rule above — chosen_host [B, Lmax] int64, -1 at pads — and n_accept [B] int32: the
+ * largest a <= lens[b] - 1 with ids[b][t + 1] == chosen[b][t] for all t < a.  What a caller who
+ * drafts some other way (a small second model) builds on.  A logits workspace of B * Lmax rows
+ * that cannot be allocated is refused before anything is launched. */
+int l3_ragged_verify_host(l3_ctx* ctx, const int64_t* ids_host, const int32_t* lens, const int32_t* starts,
+                          int32_t B, int32_t Lmax, int64_t* chosen_host, int32_t* n_accept);
+
 /* ---- one block (replaces TransformerBlock.__call__, llama3.py:239-261) --- */
 /* x [B, L, D] fp32 host -> out [B, L, D]; uses and updates layer's KV cache. */
 int l3_layer_forward_host(l3_ctx* ctx, int32_t layer, const float* x_host, int32_t B,
@@ -357,6 +404,13 @@ int l3_op_softmax_host(l3_ctx* ctx, const float* x, int64_t rows, int64_t n, flo
 /* argmax over the last axis with np.argmax's tie-break: first index of the maximum, the first
  * NaN if any (llama3.py:320); rows x n -> rows int32. */
 int l3_op_argmax_host(l3_ctx* ctx, const float* x, int64_t rows, int64_t n, int32_t* out);
+/* The drafting rule of l3_ragged_generate_spec_host on plain arrays: row b's sequence is
+ * seq[b][0 .. seq_lens[b]) (seq [B, Smax] int32, 0 <= seq_lens[b] <= Smax) and its draft limit
+ * k[b] in [0, draft_len]; out [B, draft_len] int32 receives the draft, -1 past its out_n[b]
+ * tokens.  Exact: token against token, no hashes.  Works on an op-only context. */
+int l3_op_spec_draft_host(l3_ctx* ctx, const int32_t* seq, const int32_t* seq_lens, const int32_t* k, int32_t B,
+                          int32_t Smax, int32_t draft_len, int32_t ngram_max, int32_t ngram_min, int32_t* out,
+                          int32_t* out_n);
 /* One sampled token per row by the rule of l3_set_sampling (temperature 0: the argmax);
  * logits rows x n -> rows int32.  u [rows] holds each row's uniform in [0, 1), or is NULL: row r
  * then draws l3_sample_uniform(seed, row0 + r, pos). */

@@ -12,7 +12,8 @@ namespace l3 {
 //                L3_LM_AMAX (1), L3_DECODE_FOLD_ARGMAX (1), L3_DECODE_SPECULATE (1), L3_DECODE_GRAPH_STEPS (8),
 //                L3_DECODE_GRAPH (1), L3_COMM_MODE (1), L3_COMM_PRIORITY (1), L3_GROUP_MULTI_PATH (0),
 //                L3_DECODE_PERSIST (1 persistent step; 0 graph), L3_DECODE_ROWS_AMAX (1),
-//                L3_EMBED_QKV (1 layer-0 QKV of a prefill from the table; 0 its GEMM)
+//                L3_EMBED_QKV (1 layer-0 QKV of a prefill from the table; 0 its GEMM),
+//                L3_SPEC_SKINNY (1 speculative chunks of 2 .. 8 rows on the skinny MFMA kernel; 0 launch_gemm's choice)
 //   test knobs   L3_DECODE_PERSIST_MAX_CUS (cap the CUs the persistent step sees), L3_DECODE_PERSIST_FAULT
 //                (a workgroup gives up in the step at that position; L3_DECODE_PERSIST_FAULT_WG which),
 //                L3_GROUP_VIRTUAL (a group's members may share one device; D2D copies for the gather),
@@ -484,6 +485,48 @@ hipError_t launch_cache_copy_rows(float* cache_k, float* cache_v, int src, const
 hipError_t launch_ragged_zero_slot(float* cache_k, float* cache_v, const int32_t* len, const int32_t* budget, int B,
                                    int KVH, int Smax, int HD, hipStream_t s);
 hipError_t dcheck_collect_extend(unsigned* out);
+
+// Speculative decoding with lookup drafts (spec.hip; DESIGN.md "Speculative decoding")
+constexpr int SPEC_MAX_DRAFT = 15;  // draft tokens per chunk: the chunk is 1 + draft_len <= 16 rows
+constexpr int SPEC_MAX_NGRAM = 8;   // longest suffix the lookup matches
+struct SpecDraftArgs {
+    const int32_t* seq;        // [B, seq_stride] row b: S_b = lookup ++ prompt ++ emitted
+    int64_t seq_stride;
+    const int32_t* seq_len;    // [B] E_b <= seq_stride
+    int draft_len, ngram_max, ngram_min;
+    int n_ids;                 // vocabulary size (loop form: ids outside it are counted and replaced)
+    // op form (out set): the draft alone
+    const int32_t* k;          // [B] the row's draft limit
+    int32_t* out;              // [B, draft_len], -1 past the draft
+    int32_t* out_n;            // [B]
+    // loop form (ids set): the chunk the extend reads
+    int32_t* ids;              // [B, 1 + draft_len]: [cur, draft..., pads 0]
+    int32_t* ext_start;        // [B] ExtendAttnArgs::starts
+    int32_t* ext_len;          // [B] ExtendAttnArgs::lens: 1 + d, 0 for a finished row
+    const int32_t* pos; const int32_t* cur; int32_t* finished;  // RaggedState's
+    const int32_t* n_out; const int32_t* budget;
+    int Smax;
+};
+struct SpecAcceptArgs {
+    RaggedState st;
+    const int32_t* ids;        // [B, Lq] the chunks (SpecDraftArgs::ids)
+    const int32_t* chosen;     // [B, Lq] the token choice at every chunk position
+    const int32_t* ext_len;    // [B]
+    int Lq;
+    int32_t* seq; int64_t seq_stride; int32_t* seq_len;  // S, appended to
+    int32_t* counters;         // [3][B]: iterations with a chunk, draft tokens, accepted draft tokens
+    int B, n_ids;
+};
+// one workgroup per row
+hipError_t launch_spec_draft(const SpecDraftArgs& a, int B, hipStream_t s);
+// S_b += the row's first token (after the prefill's ragged_advance)
+hipError_t launch_spec_seed(const SpecAcceptArgs& a, hipStream_t s);
+// acceptance, emission, stop / budget, advance; live[0] = rows still running
+hipError_t launch_spec_accept(const SpecAcceptArgs& a, hipStream_t s);
+// u[b * Lq + t] = the sampling uniform of (seed, b, start[b] + t)
+hipError_t launch_spec_uniform(const SampleParams* prm, const int32_t* start, float* u, int B, int Lq,
+                               hipStream_t s);
+hipError_t dcheck_collect_spec(unsigned* out);
 
 // Persistent batch-1 decode step (decode_persist.hip): one launch runs a whole greedy step —
 // every layer, the lm_head and the argmax — with in-launch hand-offs between the stages

@@ -295,6 +295,12 @@ struct l3_ctx {
     // [B * Lmax, qkvn], allocated on first use and grown as needed
     float* rag_ext_qkv = nullptr;
     int64_t rag_ext_qkv_n = 0;                  // floats
+    // speculative decoding (l3_ragged_generate_spec_host, l3_ragged_verify_host; spec.hip): one
+    // workspace — the logits of every chunk row [rows, VS], their token choices and uniforms, and
+    // the loop's sequences S, lengths and counters — allocated on first use and grown as needed
+    char* draft_ws = nullptr;
+    int64_t draft_ws_n = 0;                     // bytes
+    std::vector<int32_t> draft_host;            // host staging of the sequences (kept until the call's sync)
 };
 
 static bool sampling_on(const l3_ctx* c) { return c->samp.temperature > 0.f; }
@@ -412,7 +418,7 @@ extern "C" const char* l3_last_error(void) { return g_err.c_str(); }
 
 extern "C" int l3_version(int32_t* major, int32_t* minor) {
     if (major) *major = 0;
-    if (minor) *minor = 17;
+    if (minor) *minor = 18;
     return 0;
 }
 
@@ -570,7 +576,7 @@ extern "C" int l3_destroy(l3_ctx* c) {
     dfree(c->dec_ids); dfree(c->dec_state); dfree(c->kv_bak); dfree(c->samp_dev);
     dfree(c->score_ws); dfree(c->score_rows);
     dfree(c->rag_state); dfree(c->rag_qkv); dfree(c->rag_u); dfree(c->rag_out); dfree(c->rag_stop);
-    dfree(c->rag_split_ws); dfree(c->rag_ext_qkv);
+    dfree(c->rag_split_ws); dfree(c->rag_ext_qkv); dfree(c->draft_ws);
     if (c->dec_host) (void)hipHostFree(c->dec_host);
     for (auto& q : c->spec_q) { (void)hipEventDestroy(q.ev0); (void)hipEventDestroy(q.ev1); (void)hipEventDestroy(q.ev); }
     for (hipEvent_t e : c->spec_free) (void)hipEventDestroy(e);
@@ -2344,9 +2350,12 @@ static int ragged_extend_ws(l3_ctx* c, const char* who, int64_t rows) {
 // rows (layer 0 from the embedding rows; pads a valid id), the append and the attention
 // (ragged_extend.hip), O-proj, gate|up and down at M = B * Lmax; row b's logits from its chunk
 // position lens[b] - 1 into c->logits.  No slot outside [starts[b], T_b) is written.
-// max_new_tokens: the generate loop's (0: an extend only).
+// max_new_tokens: the generate loop's (0: an extend only).  last_logits false: no lm_head (the
+// caller reads c->h itself).
+static int ragged_extend_layers(l3_ctx* c, int B, int Lmax, bool skinny = false);
+
 static int ragged_extend_run(l3_ctx* c, const int64_t* ids_host, const int32_t* lens, const int32_t* starts, int B,
-                             int Lmax, int max_new_tokens) {
+                             int Lmax, int max_new_tokens, bool last_logits = true) {
     const int64_t mb = c->d.max_batch_size;
     c->rag_ids_host.assign((size_t)B * Lmax, 0);  // pads become a valid id
     c->rag_host.assign((size_t)(l3_ctx::RAG_WORDS * mb + 4), 0);
@@ -2364,6 +2373,18 @@ static int ragged_extend_run(l3_ctx* c, const int64_t* ids_host, const int32_t* 
     }
     if (upload_ids(c, c->rag_ids_host.data(), (int64_t)B * Lmax)) return 1;
     HIP_TRY(hipMemcpyAsync(c->rag_state, c->rag_host.data(), c->rag_host.size() * 4, hipMemcpyHostToDevice, c->stream));
+    if (ragged_extend_layers(c, B, Lmax)) return 1;
+    if (!last_logits) return 0;
+    GemmArgs lm = lm_head_args(c, B, 1, c->logits, 0);  // A row b = h row b * Lmax + lens[b] - 1
+    lm.a_rows = rag_word(c, RAG_ROWS);
+    return timed(c, L3_K_LMHEAD, [&] { return gemm(c, EPI_STORE, lm, c->stream); });
+}
+
+// The layers of an extend from device-resident state: the chunk's ids in c->ids [B, Lmax] (pads a
+// valid id), its starts and lengths in RAG_EXT_START / RAG_EXT_LEN; leaves the residual stream
+// of every chunk row in c->h [B * Lmax, D].  skinny (the speculative iterations' short chunks): the
+// four projections on the skinny MFMA kernel whatever their M
+static int ragged_extend_layers(l3_ctx* c, int B, int Lmax, bool skinny) {
     const int D = c->d.dim, FD = c->d.hidden_dim, T = B * Lmax;
     hipStream_t s = c->stream;
     for (size_t li = 0; li < c->layers.size(); ++li) {
@@ -2375,6 +2396,7 @@ static int ragged_extend_run(l3_ctx* c, const int64_t* ids_host, const int32_t* 
         g.Wb = Ly.wqkvb; g.norm_w = Ly.wqkvb ? Ly.n_attn : nullptr;
         g.ws = c->skws; g.ws_cap = c->skws_cap;
         if (li == 0) { g.A = c->emb; g.a_rows = c->ids; }
+        g.force_skinny = skinny;
         if (timed(c, L3_K_QKV, [&] { return gemm(c, EPI_STORE, g, s); })) return 1;
         ExtendAttnArgs a{};
         a.qkv = c->rag_ext_qkv; a.cache_k = Ly.cache_k; a.cache_v = Ly.cache_v; a.out = c->attn;
@@ -2388,6 +2410,7 @@ static int ragged_extend_run(l3_ctx* c, const int64_t* ids_host, const int32_t* 
         o.M = T; o.N = D; o.K = c->qdim; o.norm = false;
         o.ws = c->skws; o.ws_cap = c->skws_cap;
         if (li == 0) { o.res_src = c->emb; o.res_rows = c->ids; }
+        o.force_skinny = skinny;
         if (timed(c, L3_K_OPROJ, [&] { return gemm(c, EPI_RESID, o, s); })) return 1;
         GemmArgs gu{};  // rmsnorm -> gate|up -> SwiGLU
         gu.A = c->h; gu.lda = D; gu.W = Ly.wgu; gu.W3 = Ly.wgu3; gu.C = c->hid; gu.ldc = FD;
@@ -2397,12 +2420,11 @@ static int ragged_extend_run(l3_ctx* c, const int64_t* ids_host, const int32_t* 
         dn.A = c->hid; dn.lda = FD; dn.W = Ly.wd; dn.W3 = Ly.wd3; dn.Wb = Ly.wdb; dn.C = c->h; dn.ldc = D;
         dn.M = T; dn.N = D; dn.K = FD; dn.norm = false;
         gu.ws = dn.ws = c->skws; gu.ws_cap = dn.ws_cap = c->skws_cap;
+        gu.force_skinny = dn.force_skinny = skinny;
         if (timed(c, L3_K_GATEUP, [&] { return gemm(c, EPI_SWIGLU, gu, s); })) return 1;
         if (timed(c, L3_K_DOWN, [&] { return gemm(c, EPI_RESID, dn, s); })) return 1;
     }
-    GemmArgs lm = lm_head_args(c, B, 1, c->logits, 0);  // A row b = h row b * Lmax + lens[b] - 1
-    lm.a_rows = rag_word(c, RAG_ROWS);
-    return timed(c, L3_K_LMHEAD, [&] { return gemm(c, EPI_STORE, lm, s); });
+    return 0;
 }
 
 extern "C" int l3_ragged_extend_host(l3_ctx* c, const int64_t* ids_host, const int32_t* lens, const int32_t* starts,
@@ -2421,14 +2443,38 @@ extern "C" int l3_ragged_extend_host(l3_ctx* c, const int64_t* ids_host, const i
 
 // The generate loop of l3_ragged_generate_host (starts null: the prefill at position 0, its code
 // path as it always was) and of l3_ragged_generate_from_host (the extend, T_b = starts[b] + lens[b]
-// in the prompt length's place)
+// in the prompt length's place).  sp set: l3_ragged_generate_spec_host — the same prefill and first
+// token, then the speculative iterations (draft_loop) in the decode steps' place.
+struct DraftOpts {
+    const int64_t* lookup;        // [B, Lk] (null: no lookup)
+    const int32_t* lookup_lens;   // [B]
+    int Lk, draft_len, ngram_max, ngram_min;
+    int32_t *row_steps, *drafted, *accepted;  // [B] each, any may be null
+};
+static int draft_ws_ensure(l3_ctx* c, const char* who, int64_t rows, int64_t seq_words, int B);
+static int draft_loop(l3_ctx* c, const DraftOpts& sp, const RaggedState& st, const int64_t* ids_host,
+                     const int32_t* lens, const int32_t* starts, int B, int Lmax, int max_new_tokens);
+
 static int ragged_generate(l3_ctx* c, const char* who, const int64_t* ids_host, const int32_t* lens,
                            const int32_t* starts, int32_t B, int32_t Lmax, int32_t max_new_tokens,
-                           const int64_t* stop_ids, int32_t n_stop, int64_t* out_ids_host, int32_t* out_lens) {
+                           const int64_t* stop_ids, int32_t n_stop, int64_t* out_ids_host, int32_t* out_lens,
+                           const DraftOpts* sp = nullptr) {
     if (!out_lens || n_stop < 0 || (n_stop > 0 && !stop_ids)) return fail("%s: null argument", who);
+    if (sp && sp->lookup && !sp->lookup_lens) return fail("%s: null argument", who);
     if (starts ? ragged_extend_check(c, who, ids_host, lens, starts, B, Lmax)
                : ragged_check(c, who, ids_host, lens, B, Lmax))
         return 1;
+    if (sp && sp->lookup)
+        for (int b = 0; b < B; ++b) {
+            if (sp->lookup_lens[b] < 0 || sp->lookup_lens[b] > sp->Lk)
+                return fail("%s: lookup_lens[%d] = %d outside [0, %d]", who, b, sp->lookup_lens[b], sp->Lk);
+            for (int t = 0; t < sp->lookup_lens[b]; ++t) {
+                const int64_t id = sp->lookup[(int64_t)b * sp->Lk + t];
+                if (id < 0 || id >= c->d.vocab_size)
+                    return fail("%s: lookup id %lld (row %d, index %d) outside [0, %d)", who, (long long)id, b, t,
+                                c->d.vocab_size);
+            }
+        }
     // the last decode step runs at position max_new_tokens - 1, which must be a cache slot
     // (the reference fails there with a broadcast error, llama3.py:184)
     if (max_new_tokens > c->d.max_seq_len)
@@ -2438,6 +2484,9 @@ static int ragged_generate(l3_ctx* c, const char* who, const int64_t* ids_host, 
         const int T = lens[b] + (starts ? starts[b] : 0);
         min_len = T < min_len ? T : min_len;
         out_lens[b] = 0;
+        if (sp && sp->row_steps) sp->row_steps[b] = 0;
+        if (sp && sp->drafted) sp->drafted[b] = 0;
+        if (sp && sp->accepted) sp->accepted[b] = 0;
     }
     const int cap = max_new_tokens - min_len;
     if (cap <= 0) return 0;  // no row has a token to emit
@@ -2449,13 +2498,18 @@ static int ragged_generate(l3_ctx* c, const char* who, const int64_t* ids_host, 
                     c->d.n_heads / c->d.n_kv_heads, c->HD);
     // the attention kernel, once per call: the single-pass one wherever its LDS fits (auto mode:
     // same kernel, same bits as before the split form existed), the split-KV one otherwise or always
-    const bool split = c->rag_split_mode == 1 || !attn_decode_ragged_ok(c->d.n_heads, c->d.n_kv_heads, c->HD, s_cap);
+    // (the speculative iterations run the extend's attention, which has no context-length limit)
+    const bool split = !sp && (c->rag_split_mode == 1 ||
+                               !attn_decode_ragged_ok(c->d.n_heads, c->d.n_kv_heads, c->HD, s_cap));
     const int chunk = split ? ragged_chunk(c) : 0;
     if (split && chunk == 0) return fail("%s: no split-KV chunk length fits the attention's LDS budget", who);
     if (set_dev(c) || spec_resolve(c)) return 1;
     if (split && ragged_split_ws(c, who, attn_decode_split_n(s_cap, chunk))) return 1;
-    if (starts && ragged_extend_ws(c, who, (int64_t)B * Lmax)) return 1;
-    if (ensure_ws(c, B, Lmax) || ragged_bufs(c)) return 1;
+    const int Lq = sp ? 1 + sp->draft_len : 0;  // rows of a speculative chunk
+    const int Lrows = starts && Lmax > Lq ? Lmax : Lq;
+    if (Lrows && ragged_extend_ws(c, who, (int64_t)B * Lrows)) return 1;
+    if (sp && draft_ws_ensure(c, who, (int64_t)B * Lq, (int64_t)B * ((sp->lookup ? sp->Lk : 0) + Lmax + cap), B)) return 1;
+    if (ensure_ws(c, B, Lmax > Lq ? Lmax : Lq) || ragged_bufs(c)) return 1;
     const int64_t n_out_ids = (int64_t)B * cap;
     if (n_out_ids > c->rag_out_n) {
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2498,7 +2552,8 @@ static int ragged_generate(l3_ctx* c, const char* who, const int64_t* ids_host, 
     st.stop = c->rag_stop; st.n_stop = (int)stops.size();
     st.live = c->rag_state + (int64_t)l3_ctx::RAG_WORDS * c->d.max_batch_size;
     if (ragged_choose(c, st, B)) return 1;  // each row's first token, from its position lens[b] - 1
-    for (int i = 1; i < cap; ++i) {
+    if (sp && draft_loop(c, *sp, st, ids_host, lens, starts, B, Lmax, max_new_tokens)) return 1;
+    for (int i = 1; !sp && i < cap; ++i) {
         if (ragged_step(c, B, s_cap, chunk) || ragged_choose(c, st, B)) return 1;
         // with stop ids the rows may all be finished early: a 4-byte read every 8 steps
         if (st.n_stop > 0 && i % 8 == 0 && i + 1 < cap) {
@@ -2534,6 +2589,207 @@ extern "C" int l3_ragged_generate_from_host(l3_ctx* c, const int64_t* ids_host, 
     if (!starts) return fail("%s: null argument", who);
     return ragged_generate(c, who, ids_host, lens, starts, B, Lmax, max_new_tokens, stop_ids, n_stop, out_ids_host,
                            out_lens);
+}
+
+// ---------------------------------------------------------------------------------------
+// Speculative decoding with lookup drafts (DESIGN.md "Speculative decoding"; spec.hip): after the
+// prefill and each row's first token, an iteration drafts up to draft_len tokens per row by n-gram
+// lookup in the row's own sequence, runs the chunk [last token, draft...] as one ragged extend,
+// chooses a token from every chunk position's logits by the ordinary rule and keeps the draft's
+// longest prefix that equals those choices: the ids are l3_ragged_generate_host's.
+static int draft_range_check(const char* who, int draft_len, int ngram_max, int ngram_min) {
+    if (draft_len < 0 || draft_len > SPEC_MAX_DRAFT)
+        return fail("%s: draft_len %d outside [0, %d]", who, draft_len, SPEC_MAX_DRAFT);
+    if (ngram_min < 1 || ngram_min > ngram_max || ngram_max > SPEC_MAX_NGRAM)
+        return fail("%s: ngram_min %d, ngram_max %d (1 <= ngram_min <= ngram_max <= %d)", who, ngram_min, ngram_max,
+                    SPEC_MAX_NGRAM);
+    return 0;
+}
+
+// the workspace's parts for `rows` chunk rows, B batch rows and seq_words words of sequences
+struct DraftWs {
+    float* logits;      // [rows, VS]
+    int32_t* chosen;    // [rows]
+    float* u;           // [rows]
+    int32_t* seq_len;   // [B]
+    int32_t* counters;  // [3][B]
+    int32_t* seq;       // [seq_words]
+};
+static int64_t draft_ws_carve(const l3_ctx* c, char* base, int64_t rows, int64_t seq_words, int B, DraftWs* w) {
+    auto up = [](int64_t n) { return (n + 15) & ~(int64_t)15; };
+    int64_t off = 0;
+    auto take = [&](int64_t bytes) {
+        char* p = base + off;
+        off += up(bytes);
+        return p;
+    };
+    DraftWs t;
+    t.logits = (float*)take(rows * c->d.vocab_size * 4);
+    t.chosen = (int32_t*)take(rows * 4);
+    t.u = (float*)take(rows * 4);
+    t.seq_len = (int32_t*)take((int64_t)B * 4);
+    t.counters = (int32_t*)take((int64_t)3 * B * 4);
+    t.seq = (int32_t*)take(seq_words * 4);
+    if (w) *w = t;
+    return off;
+}
+
+// allocated on first use, grown as needed, freed with the context; a refused allocation is reported
+// before any launch
+static int draft_ws_ensure(l3_ctx* c, const char* who, int64_t rows, int64_t seq_words, int B) {
+    const int64_t n = draft_ws_carve(c, nullptr, rows, seq_words, B, nullptr);
+    if (n <= c->draft_ws_n) return 0;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    dfree(c->draft_ws);
+    c->draft_ws = nullptr;
+    c->draft_ws_n = 0;
+    if (hipMalloc(&c->draft_ws, (size_t)n) != hipSuccess) {
+        (void)hipGetLastError();  // clear the sticky error: the next launch check must not see it
+        c->draft_ws = nullptr;
+        return fail("%s: the speculative workspace (%lld bytes: %lld chunk rows x %d logits) could not be allocated",
+                    who, (long long)n, (long long)rows, c->d.vocab_size);
+    }
+    c->draft_ws_n = n;
+    return 0;
+}
+
+// the lm_head on every chunk row of c->h [B * Lq, D], then each row's token by the ordinary rule:
+// the argmax, or with sampling on the draw of (seed, b, start[b] + t)
+static int draft_choose(l3_ctx* c, const DraftWs& w, int B, int Lq, bool skinny = false) {
+    const int T = B * Lq, VS = c->d.vocab_size;
+    hipStream_t s = c->stream;
+    GemmArgs lm = lm_head_args(c, T, 1, w.logits, 0);
+    lm.force_skinny = skinny;
+    if (timed(c, L3_K_LMHEAD, [&] { return gemm(c, EPI_STORE, lm, s); })) return 1;
+    return timed(c, L3_K_ARGMAX, [&] {
+        if (!sampling_on(c)) return launch_argmax(w.logits, T, VS, w.chosen, s);
+        const hipError_t e = launch_spec_uniform(c->samp_dev, rag_word(c, RAG_EXT_START), w.u, B, Lq, s);
+        if (e != hipSuccess) return e;
+        return launch_sample(w.logits, T, VS, w.chosen, c->samp_dev, w.u, 0, 0, s);
+    });
+}
+
+// The iterations after each row's first token.  Queued eagerly; the 4-byte "rows still running"
+// word is read after every iteration from the first one at which the longest row can have spent
+// its budget (an iteration emits at most 1 + draft_len tokens per row), and with stop ids also
+// after every 4th iteration before that.  At most cap - 1 iterations: a live row emits at least one
+// token in each.
+static int draft_loop(l3_ctx* c, const DraftOpts& sp, const RaggedState& st, const int64_t* ids_host,
+                      const int32_t* lens, const int32_t* starts, int B, int Lmax, int max_new_tokens) {
+    const int VS = c->d.vocab_size, Lq = 1 + sp.draft_len, Lk = sp.lookup ? sp.Lk : 0;
+    const int64_t stride = (int64_t)Lk + Lmax + st.cap;
+    hipStream_t s = c->stream;
+    DraftWs w;
+    draft_ws_carve(c, c->draft_ws, (int64_t)B * Lq, (int64_t)B * stride, B, &w);
+    // S_b = lookup_b ++ prompt_b, as plain ids (a negative prompt id wrapped as the embedding wraps it)
+    c->draft_host.assign((size_t)(B * stride + B), 0);
+    int32_t* E = c->draft_host.data() + B * stride;
+    int rmax = 0;
+    for (int b = 0; b < B; ++b) {
+        int32_t* row = c->draft_host.data() + b * stride;
+        int n = 0;
+        for (int t = 0; sp.lookup && t < sp.lookup_lens[b]; ++t) row[n++] = (int32_t)sp.lookup[(int64_t)b * Lk + t];
+        for (int t = 0; t < lens[b]; ++t) {
+            const int64_t id = ids_host[(int64_t)b * Lmax + t];
+            row[n++] = (int32_t)(id + (id < 0 ? VS : 0));
+        }
+        E[b] = n;
+        const int R = max_new_tokens - lens[b] - (starts ? starts[b] : 0);
+        rmax = R > rmax ? R : rmax;
+    }
+    HIP_TRY(hipMemcpyAsync(w.seq, c->draft_host.data(), (size_t)B * stride * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(w.seq_len, E, (size_t)B * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(w.counters, 0, (size_t)3 * B * 4, s));
+    SpecAcceptArgs aa{};
+    aa.st = st;
+    aa.ids = c->ids; aa.chosen = w.chosen; aa.ext_len = rag_word(c, RAG_EXT_LEN); aa.Lq = Lq;
+    aa.seq = w.seq; aa.seq_stride = stride; aa.seq_len = w.seq_len; aa.counters = w.counters;
+    aa.B = B; aa.n_ids = VS;
+    HIP_TRY(launch_spec_seed(aa, s));
+    SpecDraftArgs da{};
+    da.seq = w.seq; da.seq_stride = stride; da.seq_len = w.seq_len;
+    da.draft_len = sp.draft_len; da.ngram_max = sp.ngram_max; da.ngram_min = sp.ngram_min; da.n_ids = VS;
+    da.ids = c->ids; da.ext_start = rag_word(c, RAG_EXT_START); da.ext_len = rag_word(c, RAG_EXT_LEN);
+    da.pos = st.pos; da.cur = st.cur_id; da.finished = st.finished; da.n_out = st.n_out; da.budget = st.budget;
+    da.Smax = c->d.max_seq_len;
+    const int it_min = (rmax - 1 + Lq - 1) / Lq;
+    // chunks of 2 .. 8 rows: the skinny MFMA kernel instead of what launch_gemm picks by shape at that
+    // M, whose time grows with the rows (DESIGN.md "Speculative decoding", Speed); L3_SPEC_SKINNY=0
+    // keeps the dispatcher's choice (A/B)
+    static const bool skinny_knob = env_knob("L3_SPEC_SKINNY", 1) != 0;
+    const bool skinny = skinny_knob && B * Lq >= 2 && B * Lq <= 8;
+    for (int it = 1; it < st.cap; ++it) {
+        HIP_TRY(launch_spec_draft(da, B, s));
+        if (ragged_extend_layers(c, B, Lq, skinny) || draft_choose(c, w, B, Lq, skinny)) return 1;
+        HIP_TRY(launch_spec_accept(aa, s));
+        if (it + 1 < st.cap && (it >= it_min || (st.n_stop > 0 && it % 4 == 0))) {
+            int32_t live = 1;
+            HIP_TRY(hipMemcpyAsync(&live, st.live, 4, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            if (live == 0) break;
+        }
+    }
+    std::vector<int32_t> cnt((size_t)3 * B);
+    HIP_TRY(hipMemcpyAsync(cnt.data(), w.counters, cnt.size() * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int b = 0; b < B; ++b) {
+        if (sp.row_steps) sp.row_steps[b] = cnt[(size_t)b];
+        if (sp.drafted) sp.drafted[b] = cnt[(size_t)B + b];
+        if (sp.accepted) sp.accepted[b] = cnt[(size_t)2 * B + b];
+    }
+    return 0;
+}
+
+extern "C" int l3_ragged_generate_spec_host(l3_ctx* c, const int64_t* ids_host, const int32_t* lens,
+                                            const int32_t* starts, int32_t B, int32_t Lmax, int32_t max_new_tokens,
+                                            const int64_t* stop_ids, int32_t n_stop, const int64_t* lookup_host,
+                                            const int32_t* lookup_lens, int32_t Lk, int32_t draft_len,
+                                            int32_t ngram_max, int32_t ngram_min, int64_t* out_ids_host,
+                                            int32_t* out_lens, int32_t* row_steps, int32_t* drafted,
+                                            int32_t* accepted) {
+    const char* who = "l3_ragged_generate_spec_host";
+    if (draft_range_check(who, draft_len, ngram_max, ngram_min)) return 1;  // wrong for every context
+    if (Lk < 0) return fail("%s: Lk %d is negative", who, Lk);
+    CHECK_CTX(c);
+    const DraftOpts sp{lookup_host, lookup_lens, Lk, draft_len, ngram_max, ngram_min, row_steps, drafted, accepted};
+    return ragged_generate(c, who, ids_host, lens, starts, B, Lmax, max_new_tokens, stop_ids, n_stop, out_ids_host,
+                           out_lens, &sp);
+}
+
+extern "C" int l3_ragged_verify_host(l3_ctx* c, const int64_t* ids_host, const int32_t* lens, const int32_t* starts,
+                                     int32_t B, int32_t Lmax, int64_t* chosen_host, int32_t* n_accept) {
+    CHECK_CTX(c);
+    const char* who = "l3_ragged_verify_host";
+    if (!chosen_host || !n_accept) return fail("%s: null argument", who);
+    if (ragged_extend_check(c, who, ids_host, lens, starts, B, Lmax)) return 1;
+    if (set_dev(c) || spec_resolve(c)) return 1;
+    const int64_t T = (int64_t)B * Lmax;
+    // (the largest first: a refused call has allocated nothing)
+    if (draft_ws_ensure(c, who, T, 0, B) || ragged_extend_ws(c, who, T) || ensure_ws(c, B, Lmax) || ragged_bufs(c))
+        return 1;
+    if (ragged_extend_run(c, ids_host, lens, starts, B, Lmax, 0, false)) return 1;
+    DraftWs w;
+    draft_ws_carve(c, c->draft_ws, T, 0, B, &w);
+    if (draft_choose(c, w, B, Lmax)) return 1;
+    std::vector<int32_t> ch((size_t)T);
+    HIP_TRY(hipMemcpyAsync(ch.data(), w.chosen, ch.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const int64_t VS = c->d.vocab_size;
+    for (int b = 0; b < B; ++b) {
+        const int64_t* row = ids_host + (int64_t)b * Lmax;
+        int a = 0;
+        bool run = true;  // the draft's accepted prefix: c[t + 1] == chosen[t] for all t < a
+        for (int t = 0; t < Lmax; ++t) {
+            chosen_host[(int64_t)b * Lmax + t] = t < lens[b] ? ch[(size_t)b * Lmax + t] : -1;
+            if (t + 1 < lens[b] && run) {
+                const int64_t next = row[t + 1] + (row[t + 1] < 0 ? VS : 0);
+                run = next == ch[(size_t)b * Lmax + t];
+                a += run;
+            }
+        }
+        n_accept[b] = a;
+    }
+    return 0;
 }
 
 extern "C" int l3_layer_forward_host(l3_ctx* c, int32_t layer, const float* x_host, int32_t B,
@@ -2636,6 +2892,46 @@ extern "C" int l3_op_argmax_host(l3_ctx* c, const float* x, int64_t rows, int64_
     H2D(dx, x, rows * n);
     HIP_TRY(launch_argmax(dx, rows, (int)n, reinterpret_cast<int32_t*>(di), c->stream));
     D2H(out, di, rows);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// The drafting rule of the speculative loop on plain arrays (spec.hip spec_draft_kernel, op form)
+extern "C" int l3_op_spec_draft_host(l3_ctx* c, const int32_t* seq, const int32_t* seq_lens, const int32_t* k,
+                                     int32_t B, int32_t Smax, int32_t draft_len, int32_t ngram_max,
+                                     int32_t ngram_min, int32_t* out, int32_t* out_n) {
+    const char* who = "l3_op_spec_draft_host";
+    if (draft_range_check(who, draft_len, ngram_max, ngram_min)) return 1;
+    if (B <= 0 || B > 65535 || Smax <= 0) return fail("%s: bad shape B=%d Smax=%d", who, B, Smax);
+    if (!seq || !seq_lens || !k || !out_n || (draft_len > 0 && !out)) return fail("%s: null argument", who);
+    for (int b = 0; b < B; ++b) {
+        if (seq_lens[b] < 0 || seq_lens[b] > Smax)
+            return fail("%s: seq_lens[%d] = %d outside [0, %d]", who, b, seq_lens[b], Smax);
+        if (k[b] < 0 || k[b] > draft_len) return fail("%s: k[%d] = %d outside [0, %d]", who, b, k[b], draft_len);
+    }
+    CHECK_CTX(c);
+    if (draft_len == 0) {  // nothing to search for
+        for (int b = 0; b < B; ++b) out_n[b] = 0;
+        return 0;
+    }
+    if (set_dev(c)) return 1;
+    Scratch S{c};
+    SCRATCH(dseq, (int64_t)B * Smax);
+    SCRATCH(dlen, B);
+    SCRATCH(dk, B);
+    SCRATCH(dout, (int64_t)B * draft_len);
+    SCRATCH(dn, B);
+    H2D(dseq, seq, (int64_t)B * Smax);
+    H2D(dlen, seq_lens, B);
+    H2D(dk, k, B);
+    SpecDraftArgs a{};
+    a.seq = reinterpret_cast<int32_t*>(dseq); a.seq_stride = Smax; a.seq_len = reinterpret_cast<int32_t*>(dlen);
+    a.draft_len = draft_len; a.ngram_max = ngram_max; a.ngram_min = ngram_min;
+    a.k = reinterpret_cast<int32_t*>(dk);
+    a.out = reinterpret_cast<int32_t*>(dout); a.out_n = reinterpret_cast<int32_t*>(dn);
+    HIP_TRY(launch_spec_draft(a, B, c->stream));
+    D2H(out, dout, (int64_t)B * draft_len);
+    D2H(out_n, dn, B);
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -3208,6 +3504,7 @@ extern "C" int l3_device_check_counts(l3_ctx* c, uint32_t* counts, int32_t* enab
     HIP_TRY(dcheck_collect_persist(n));
     HIP_TRY(dcheck_collect_ragged(n));
     HIP_TRY(dcheck_collect_extend(n));
+    HIP_TRY(dcheck_collect_spec(n));
     for (int i = 0; i < CHK_N; ++i) counts[i] = n[i];
     return 0;
 }

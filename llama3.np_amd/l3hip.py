@@ -77,6 +77,10 @@ _SIGNATURES = {
     "l3_cache_copy_rows": (ctypes.c_int, [_P, _I32, _P, _I32, _I32]),
     "l3_op_attn_extend_ragged_host": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32,
                                                      _I32, _P]),
+    "l3_ragged_generate_spec_host": (ctypes.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _P, _I32, _P, _P, _I32, _I32,
+                                                    _I32, _I32, _P, _P, _P, _P, _P]),
+    "l3_ragged_verify_host": (ctypes.c_int, [_P, _P, _P, _P, _I32, _I32, _P, _P]),
+    "l3_op_spec_draft_host": (ctypes.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P]),
     "l3_attention_forward_host": (ctypes.c_int, [_P, _I32, _P, _I32, _I32, _I32, _P]),
     "l3_op_softmax_host": (ctypes.c_int, [_P, _P, _I64, _I64, _P]),
     "l3_op_argmax_host": (ctypes.c_int, [_P, _P, _I64, _I64, _P]),
@@ -449,6 +453,69 @@ class Context:
         else:
             check(lib().l3_ragged_generate_from_host(self._h, ptr(ids), ptr(lens), ptr(starts), *tail))
         return out, out_lens
+
+    def ragged_generate_spec(self, ids: np.ndarray, lens, max_new_tokens: int, stop_ids=(), starts=None,
+                             lookup=None, lookup_lens=None, draft_len: int = 4, ngram_max: int = 3,
+                             ngram_min: int = 1):
+        """``ragged_generate`` through speculative iterations with lookup drafts
+        (l3_ragged_generate_spec_host): the same (out, out_lens), and a dict of per-row int32
+        counters — ``row_steps`` (iterations in which the row ran a chunk), ``drafted`` and
+        ``accepted`` (draft tokens run / confirmed).  ``lookup`` int64 [B, Lk] with ``lookup_lens``
+        [B] is an optional reference text per row that the n-gram lookup searches before the row's
+        own tokens."""
+        ids, lens = self._ragged_args(ids, lens)
+        B, Lmax = ids.shape
+        stops = np.ascontiguousarray(list(stop_ids), dtype=np.int64).reshape(-1)
+        if starts is not None:
+            starts = self._ragged_starts(starts, B)
+        if lookup is not None:
+            lookup = np.ascontiguousarray(lookup, dtype=np.int64)
+            lookup_lens = np.ascontiguousarray(lookup_lens, dtype=np.int32)
+            if lookup.ndim != 2 or lookup.shape[0] != B or lookup_lens.shape != (B,):
+                raise ValueError(f"lookup {lookup.shape} must be [{B}, Lk] and lookup_lens {lookup_lens.shape} [{B}]")
+        total = lens if starts is None else lens.astype(np.int64) + starts
+        cap = max(0, int(max_new_tokens) - int(total.min())) if B else 0
+        out = np.full((B, cap), -1, np.int64)
+        out_lens = np.zeros(B, np.int32)
+        stats = {k: np.zeros(B, np.int32) for k in ("row_steps", "drafted", "accepted")}
+        check(lib().l3_ragged_generate_spec_host(
+            self._h, ptr(ids), ptr(lens), None if starts is None else ptr(starts), B, Lmax, int(max_new_tokens),
+            ptr(stops) if stops.size else None, int(stops.size),
+            None if lookup is None else ptr(lookup), None if lookup is None else ptr(lookup_lens),
+            0 if lookup is None else lookup.shape[1], int(draft_len), int(ngram_max), int(ngram_min),
+            ptr(out), ptr(out_lens), ptr(stats["row_steps"]), ptr(stats["drafted"]), ptr(stats["accepted"])))
+        return out, out_lens, stats
+
+    def ragged_verify(self, ids: np.ndarray, lens, starts):
+        """An extend that returns the model's token choice at every chunk position
+        (l3_ragged_verify_host): (chosen int64 [B, Lmax], -1 at pads; n_accept int32 [B], the
+        length of the prefix of ``ids[b][1:]`` that equals those choices).  The cache effect is
+        ``ragged_extend``'s."""
+        ids, lens = self._ragged_args(ids, lens)
+        B, Lmax = ids.shape
+        starts = self._ragged_starts(starts, B)
+        chosen = np.full((B, Lmax), -1, np.int64)
+        n_accept = np.zeros(B, np.int32)
+        check(lib().l3_ragged_verify_host(self._h, ptr(ids), ptr(lens), ptr(starts), B, Lmax, ptr(chosen),
+                                          ptr(n_accept)))
+        return chosen, n_accept
+
+    def op_spec_draft(self, seq, seq_lens, k, draft_len: int, ngram_max: int = 3, ngram_min: int = 1):
+        """The lookup drafting rule on plain arrays (l3_op_spec_draft_host): ``seq`` int32
+        [B, Smax], ``seq_lens`` / ``k`` [B]; returns (out int32 [B, draft_len], -1 past each
+        draft; out_n int32 [B])."""
+        seq = np.ascontiguousarray(seq, dtype=np.int32)
+        seq_lens = np.ascontiguousarray(seq_lens, dtype=np.int32)
+        k = np.ascontiguousarray(k, dtype=np.int32)
+        if seq.ndim != 2 or seq_lens.shape != (seq.shape[0],) or k.shape != seq_lens.shape:
+            raise ValueError(f"seq {seq.shape} must be [B, Smax], seq_lens {seq_lens.shape} and k {k.shape} [B]")
+        B, Smax = seq.shape
+        out = np.full((B, int(draft_len)), -1, np.int32)
+        out_n = np.zeros(B, np.int32)
+        check(lib().l3_op_spec_draft_host(self._h, ptr(seq), ptr(seq_lens), ptr(k), B, Smax, int(draft_len),
+                                          int(ngram_max), int(ngram_min), ptr(out) if out.size else None,
+                                          ptr(out_n)))
+        return out, out_n
 
     def cache_copy_rows(self, src: int, dst_rows, n_slots: int) -> None:
         """The fork of a cache row (l3_cache_copy_rows): slots ``[0, n_slots)`` of K and V in every

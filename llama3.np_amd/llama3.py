@@ -31,6 +31,7 @@ views) is kept, so introspecting code keeps working.
 
 from __future__ import annotations
 
+import dataclasses
 import os
 import sys
 import time
@@ -110,6 +111,17 @@ def repeat_kv(x, n_rep: int):
 
 
 # ---- layers ------------------------------------------------------------------
+
+@dataclasses.dataclass
+class Speculate:
+    """Settings of ``Llama.generate_ragged(..., speculate=)``: up to ``draft_len`` (0 .. 15) draft
+    tokens per row and iteration, found by matching the row's last ``ngram_max`` down to
+    ``ngram_min`` tokens (1 .. 8) against ``lookup[b] + prompt + emitted``."""
+    draft_len: int = 4
+    ngram_max: int = 3
+    ngram_min: int = 1
+    lookup: Optional[Sequence] = None
+
 
 def _dims(args: ModelArgs, hidden_dim: int, n_layers: int, vocab_size: int) -> l3hip.Dims:
     kvh = args.n_heads if args.n_kv_heads is None else args.n_kv_heads
@@ -515,7 +527,8 @@ class Llama:
             raise NotImplementedError("ragged batches on a multi-device model: not implemented")
         self._ctx.cache_copy_rows(src_row, dst_rows, n_slots)
 
-    def generate_ragged(self, prompts, max_new_tokens: int, stop_ids=(), start_pos=None, prefix=None):
+    def generate_ragged(self, prompts, max_new_tokens: int, stop_ids=(), start_pos=None, prefix=None,
+                        speculate=None):
         """Extension (DESIGN.md "Ragged batches"): ``generate_all`` for prompts of different
         lengths, as one device-side loop.  Returns one int64 array per row: what ``generate``
         yields for that row alone on a zeroed cache (the reference's schedule, decode hole
@@ -537,7 +550,15 @@ class Llama:
         rows generate from ``start_pos = len(prefix)``: the ids of ``prefix + prompts[b]``.
         A call in which no row has a token left to emit runs nothing and leaves the caches as they
         were (``prompts`` are not appended; with ``prefix`` only the prefix is): to append without
-        generating, call ``extend_ragged``."""
+        generating, call ``extend_ragged``.
+
+        Speculative decoding (DESIGN.md "Speculative decoding"): with ``speculate`` — a
+        ``Speculate`` or a dict of its fields — the decode steps become iterations that draft up
+        to ``draft_len`` tokens per row by n-gram lookup in ``lookup[b] + prompts[b] + emitted``
+        and verify them in one extend; the ids returned are the same.  ``None`` is the path above,
+        call for call.  ``generate_ragged_spec`` also returns the per-row counters."""
+        if speculate is not None:
+            return self.generate_ragged_spec(prompts, max_new_tokens, stop_ids, start_pos, prefix, speculate)[0]
         ids, lens = self._ragged(prompts)
         if prefix is not None:
             if start_pos is not None:
@@ -549,6 +570,52 @@ class Llama:
             start_pos = [pre.size] * len(lens)
         out, n = self._ctx.ragged_generate(ids, lens, int(max_new_tokens), stop_ids, starts=start_pos)
         return [out[b, :n[b]].copy() for b in range(len(n))]
+
+    def generate_ragged_spec(self, prompts, max_new_tokens: int, stop_ids=(), start_pos=None, prefix=None,
+                             speculate=None):
+        """``generate_ragged`` with lookup-drafted speculative decoding, and its counters:
+        ``(ids_list, stats)`` with ``stats`` a dict of int32 arrays, one entry per row —
+        ``row_steps`` (iterations in which the row ran a chunk), ``drafted`` (draft tokens run)
+        and ``accepted`` (draft tokens that equalled the model's own choice).  ``ids_list`` is
+        ``generate_ragged``'s for the same arguments, greedy or sampled.  ``speculate``: a
+        ``Speculate``, a dict of its fields, or ``None`` for the defaults; ``lookup`` is one id
+        sequence per row (or ``None``) that the drafts may also be taken from.  A row's lookup
+        sequence is ``lookup[b] + prompts[b] + emitted``: the tokens of ``prefix`` or of earlier
+        calls are not part of it.  Not for a model on more than one device."""
+        sp = speculate if isinstance(speculate, Speculate) else Speculate(**(speculate or {}))
+        ids, lens = self._ragged(prompts)
+        if prefix is not None:
+            if start_pos is not None:
+                raise ValueError("pass start_pos or prefix, not both")
+            pre = np.asarray(prefix, dtype=np.int64).reshape(-1)
+            if pre.size:
+                self(pre[None], 0)
+                self.fork_cache(0, range(1, len(lens)), pre.size)
+            start_pos = [pre.size] * len(lens)
+        look = look_lens = None
+        if sp.lookup is not None:
+            rows = [np.asarray(r, dtype=np.int64).reshape(-1) for r in sp.lookup]
+            if len(rows) != len(lens):
+                raise ValueError(f"speculate.lookup has {len(rows)} rows for {len(lens)} prompts")
+            look_lens = np.array([r.size for r in rows], np.int32)
+            look = np.zeros((len(rows), max(1, int(look_lens.max()) if len(rows) else 1)), np.int64)
+            for b, r in enumerate(rows):
+                look[b, :r.size] = r
+        out, n, stats = self._ctx.ragged_generate_spec(ids, lens, int(max_new_tokens), stop_ids, starts=start_pos,
+                                                       lookup=look, lookup_lens=look_lens, draft_len=sp.draft_len,
+                                                       ngram_max=sp.ngram_max, ngram_min=sp.ngram_min)
+        return [out[b, :n[b]].copy() for b in range(len(n))], stats
+
+    def verify_ragged(self, chunks, start_pos):
+        """Extension (DESIGN.md "Speculative decoding"): ``extend_ragged`` that returns what the
+        model would have chosen — ``(chosen_list, n_accept)``: ``chosen_list[b][t]`` is the token
+        picked from the logits of ``chunks[b][t]`` (the argmax, or after ``set_sampling`` the draw
+        of (seed, row, position)), and ``n_accept[b]`` the number of leading tokens of
+        ``chunks[b][1:]`` that equal those picks.  The hook for a caller who drafts some other
+        way.  Not for a model on more than one device."""
+        ids, lens = self._ragged(chunks)
+        chosen, n_accept = self._ctx.ragged_verify(ids, lens, start_pos)
+        return [chosen[b, :lens[b]].copy() for b in range(len(lens))], n_accept
 
 
 def main(argv=None, tokenizer_path="./tokenizer.model.np", model_path="./stories15M.model.npz"):
