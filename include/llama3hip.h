@@ -149,8 +149,9 @@ int l3_set_gemm_x6(l3_ctx* ctx, int32_t on);
  * RMSNorm weights stay fp32.  l3_finalize makes a bf16 copy of each of those tensors (unfolded, in
  * the fp32 tensor's row layout, 2 bytes per element beside the 4 of the fp32 tensor), and every
  * launch that runs on the weight-streaming GEMV — decode and prompts of up to 8 rows — streams
- * that copy instead of the fp32 tensor and applies the norm weight to the activations; every
- * other kernel keeps reading the fp32 tensors, which hold the same model:
+ * that copy instead of the fp32 tensor and applies the norm weight to the activations, as does
+ * the 2 .. 64-row kernel of l3_set_weight_bf16_rows below; every other kernel keeps reading the
+ * fp32 tensors, which hold the same model:
  *   mode 1 (exact): every element must already be a bf16 value; otherwise l3_finalize fails,
  *     naming the first offending tensor (layer, kind) and its count of inexact elements, the
  *     context stays un-finalized and the mode may be changed before finalizing again.  Results
@@ -166,6 +167,28 @@ int l3_set_weight_bf16(l3_ctx* ctx, int32_t mode);
  * captured, not per replay); any pointer may be NULL.  No reference counterpart (llama3.py:265-283
  * keeps one copy of each weight). */
 int l3_weight_bf16_info(l3_ctx* ctx, int32_t* mode, int64_t* bytes, int64_t* gemv_launches);
+/* 2 .. max_rows rows on the bf16 copies (extension; env L3_WEIGHT_BF16_ROWS and
+ * L3_WEIGHT_BF16_MIN_BYTES set the two values for new contexts; DESIGN.md "bf16 weight storage for
+ * 2-64 rows").  The reference multiplies every row of a batch by the one copy of W it holds
+ * (llama3.py:166-168, :211, :99-102, :304-307); with l3_set_weight_bf16 on, a projection launch of
+ * 2 .. max_rows rows whose weight has at least min_bytes bytes as bf16 (N * K * 2) runs on a
+ * weight-streaming MFMA kernel that reads the bf16 copy once — batched and ragged decode steps,
+ * speculative chunks, short continuations, their lm_head — instead of the fp32 kernels, which read
+ * the fp32 tensor; arithmetic stays fp32 on the same model W_b, so results agree to fp32 rounding.
+ * One-row launches (the GEMV, the persistent step) and every launch outside the range are exactly
+ * as without this call, as is a context in mode 0.
+ *   max_rows: 0 turns the kernel off (the dispatch of a context without this call, bit for bit),
+ *     2 .. 64 the largest row count it takes, -1 keeps the current value.
+ *   min_bytes: >= 0, -1 keeps the current value (default 32 MiB).
+ * May be called before or after l3_finalize (it changes dispatch only); a change drops the captured
+ * decode steps, which are captured again with the new choice at the next decode step.
+ * Errors: a value out of range; a member of a multi-device l3_group. */
+int l3_set_weight_bf16_rows(l3_ctx* ctx, int32_t max_rows, int64_t min_bytes);
+/* The two values in force and the launches issued on that kernel since l3_create (a captured decode
+ * step counts when it is captured, not per replay; l3_weight_bf16_info's gemv_launches keeps
+ * counting the GEMV-form launches only); any pointer may be NULL.  No reference counterpart
+ * (llama3.py:265-283 keeps one copy of each weight and has one product, :166-168). */
+int l3_weight_bf16_rows_info(l3_ctx* ctx, int32_t* max_rows, int64_t* min_bytes, int64_t* launches);
 /* Layer 0's QKV of a prefill as a table lookup (extension; default on, env L3_EMBED_QKV=0 turns
  * it off for new contexts).  Layer 0's QKV rows before RoPE depend on the token id and the weights
  * only, and the weights are fixed after l3_finalize, so a table [vocab_size, (H + 2 KVH) * HD] fp32
@@ -467,6 +490,13 @@ int l3_op_to_bf16_host(l3_ctx* ctx, const float* x, int64_t n, uint16_t* out_u16
  * error: no other kernel stands in. */
 int l3_op_linear_bf16_host(l3_ctx* ctx, const float* x, int64_t rows, int32_t K, int32_t N,
                            const uint16_t* w_u16, const float* norm_w, float eps, float* y);
+/* The same product (the reference's `x @ W.T`, llama3.py:166-168, with W stored as bf16 and the
+ * RMSNorm of llama3.py:111-114 when norm_w is given) on the weight-streaming MFMA kernel of
+ * l3_set_weight_bf16_rows, whatever that setting says: rows in [2, 64], K % 32 == 0, N % 4 == 0,
+ * one launch.  Any other shape is an error: no other kernel stands in.  Works on an op-only
+ * context. */
+int l3_op_linear_bf16_rows_host(l3_ctx* ctx, const float* x, int64_t rows, int32_t K, int32_t N,
+                                const uint16_t* w_u16, const float* norm_w, float eps, float* y);
 /* The scoring path of l3_score_host (llama3.py:285-308 with the logits reduced in the lm_head's
  * epilogue) on a plain product: for z = x [rows, K] @ W[N, K]^T (no norm) and targets int32 [rows]
  * (-1: no target; else in [0, N)), logprob [rows], and optionally lse [rows] and argmax int32

@@ -235,28 +235,96 @@ int gemm_store_config(const GemmArgs& a) {
     return a.M <= 32 ? 1 : a.M <= 64 ? 2 : 3;
 }
 
-// GemmArgs::Wb is used exactly where the launch goes to gemv_kernel: the fused-O-proj parts, the
-// folded-argmax QKV and the plain GEMV range (the dispatch order of launch_gemm below); every other
-// kernel reads the fp32 W, which holds the same model (runtime.hip finalize_bf16)
+// GemmArgs::Wb on the GEMV: exactly where the launch goes to gemv_kernel — the fused-O-proj parts,
+// the folded-argmax QKV and the plain GEMV range (the dispatch order of launch_gemm below) — unless
+// gemm_rows_bf16_kernel takes it first (gemm_takes_bf16_rows); every other kernel reads the fp32 W,
+// which holds the same model (runtime.hip finalize_bf16)
 bool gemm_takes_bf16(int epi, const GemmArgs& a) {
     if (!a.Wb || a.M <= 0 || a.N <= 0) return false;
+    if (gemm_takes_bf16_rows(epi, a)) return false;  // gemm_rows_bf16_kernel, not the GEMV
     if (a.parts) return epi == EPI_SWIGLU || epi == EPI_RESID;
     if (a.amax_in) return true;
     if (a.force_skinny || a.force_tiled) return false;
     return gemm_is_gemv(a) && !use_skinny(a);
 }
 
+// 2 .. wb_rows rows on the bf16 copy (gemm_rows_bf16_kernel, gemm_kernel.h): the weight streams
+// once per launch whatever M.  It has the skinny kernel's four epilogues and nothing else, so a
+// launch that asks for partial rows, argmax / scoring partials, the undo slots or a fixed tiled
+// configuration stays where it was, as does one whose M is a batch split's share of the rows
+// (split_rows: this kernel's rounding follows the row-tile count).  With the x6 pieces set, every
+// launch past 32 rows that is not EPI_STORE stays too: a superset of what x6 takes (launch_gemm
+// reaches x6 only after the skinny, GEMV and split-K choices), so with x6 and bf16 storage both
+// on, 33 - 64-row split-K launches keep the fp32 kernels.  force_skinny (speculative chunks) and
+// split-K launches are taken
+bool gemm_takes_bf16_rows(int epi, const GemmArgs& a) {
+    if (!a.Wb || a.wb_rows < 2 || a.M < 2 || a.M > a.wb_rows || a.M > WB_ROWS_MAX || a.N <= 0) return false;
+    if ((int64_t)a.N * a.K * 2 < a.wb_min_bytes) return false;
+    if (a.parts || a.amax_in || a.amax_part || a.amax_rows || a.lse_rows || a.kv_bak || a.force_tiled ||
+        a.split_rows)
+        return false;
+    if (a.W3 && a.M > 32 && epi != EPI_STORE) return false;
+    return epi == EPI_STORE || epi == EPI_RESID || epi == EPI_SWIGLU || epi == EPI_QKV;
+}
+
+// k-blocks in flight per round trip of gemm_rows_bf16_kernel for one / two / four row tiles:
+// 4 / 1 / 1 measured best against 4 / 2 / 2, 8 / 4 / 2 and 2 / 1 / 1 (DESIGN.md decisions table)
+constexpr int WB_ROWS_CH1 = 4, WB_ROWS_CH2 = 1, WB_ROWS_CH4 = 1;
+// eight waves per block when the launch has at most this many blocks (N / 16 TN: the O-proj, down
+// and QKV of the Llama-3 shape), so their k split keeps more loads in flight (6 - 10 % of a
+// Llama-3-shape step against four waves everywhere)
+constexpr unsigned WB_ROWS_WIDE_BLOCKS = 512;
+
+template <int EPI, int TN, int MT, int CH>
+static hipError_t launch_rows_bf16_mt(const GemmArgs& a, hipStream_t s) {
+    const unsigned blocks = (unsigned)((a.N + 16 * TN - 1) / (16 * TN));
+    const bool nt = gemv_nt(a);
+    // (four row tiles of two column tiles keep four waves: eight of them, at 256 registers each,
+    // spilled, and their partial tiles would fill 63 KB of LDS)
+    constexpr bool WIDE_OK = MT * TN < 8;
+    if constexpr (WIDE_OK) {
+        if (blocks <= WB_ROWS_WIDE_BLOCKS) {
+            if (nt) hipLaunchKernelGGL((gemm_rows_bf16_kernel<EPI, TN, MT, CH, true, 8>), dim3(blocks), dim3(512), 0, s, a);
+            else hipLaunchKernelGGL((gemm_rows_bf16_kernel<EPI, TN, MT, CH, false, 8>), dim3(blocks), dim3(512), 0, s, a);
+            return hipGetLastError();
+        }
+    }
+    if (nt) hipLaunchKernelGGL((gemm_rows_bf16_kernel<EPI, TN, MT, CH, true, 4>), dim3(blocks), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((gemm_rows_bf16_kernel<EPI, TN, MT, CH, false, 4>), dim3(blocks), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// one, two or four 16-row tiles per block: every row of the launch in one block
+template <int EPI, int TN>
+static hipError_t launch_rows_bf16(const GemmArgs& a, hipStream_t s) {
+    if (a.M <= 16) return launch_rows_bf16_mt<EPI, TN, 1, WB_ROWS_CH1>(a, s);
+    if (a.M <= 32) return launch_rows_bf16_mt<EPI, TN, 2, WB_ROWS_CH2>(a, s);
+    return launch_rows_bf16_mt<EPI, TN, 4, WB_ROWS_CH4>(a, s);
+}
+
 hipError_t launch_gemm(int epi, const GemmArgs& a_in, hipStream_t s) {
     GemmArgs a_own;
-    if (a_in.Wb && !gemm_takes_bf16(epi, a_in)) {  // not a GEMV launch: the fp32 kernels, as without Wb
+    const bool rows_bf16 = gemm_takes_bf16_rows(epi, a_in);
+    // neither a GEMV launch nor a rows launch: the fp32 kernels, as without Wb
+    const bool drop_wb = a_in.Wb && !rows_bf16 && !gemm_takes_bf16(epi, a_in);
+    if (drop_wb) {
         a_own = a_in;
         a_own.Wb = nullptr;
     }
-    const GemmArgs& a = a_in.Wb && !gemm_takes_bf16(epi, a_in) ? a_own : a_in;
+    const GemmArgs& a = drop_wb ? a_own : a_in;
     if (a.M <= 0 || a.N <= 0) return hipSuccess;
     if (a.K % 32 != 0 || a.K <= 0) return hipErrorInvalidValue;  // whole 32-deep k-tiles
     if (epi == EPI_SWIGLU && a.N % 32 != 0) return hipErrorInvalidValue;
     if (a.N % 4 != 0 || a.ldc % 4 != 0 || a.lda % 4 != 0) return hipErrorInvalidValue;  // 16-B rows
+    if (rows_bf16) {  // before the skinny, GEMV and split-K choices
+        if (a.pos_adv) return hipErrorInvalidValue;
+        switch (epi) {
+            case EPI_SWIGLU: return launch_rows_bf16<EPI_SWIGLU, 2>(a, s);
+            case EPI_QKV: return launch_rows_bf16<EPI_QKV, 1>(a, s);
+            case EPI_RESID: return launch_rows_bf16<EPI_RESID, 1>(a, s);
+            default: return launch_rows_bf16<EPI_STORE, 1>(a, s);
+        }
+    }
     // Short M (decode, batched decode, short prompts): weight-streaming GEMV with the same
     // epilogues, 8-row blocks beyond M = 8 re-reading W through L2 — for the layer weights up
     // to M = 256 (a 128-row MFMA tile there is one k-loop of memory round trips on a handful of

@@ -1385,4 +1385,192 @@ __global__ void __launch_bounds__(256) gemv_kernel(GemmArgs p) {
     }
 }
 
+// ---------------------------------------------------------------------------------------
+// Weight-streaming MFMA GEMM for 2..64 rows on the bf16 weight copy (GemmArgs::Wb; DESIGN.md
+// "bf16 weight storage for 2-64 rows"): batched / ragged decode, speculative chunks and short
+// continuations (llama3.py:166-178,211,99-102,304-307 at a few rows) against a weight past the
+// caches.  A block owns 16 * TN rows of W (output columns) and ALL MT 16-row tiles of the
+// activations, so every W element is read once per launch whatever M is (the skinny kernel's grid
+// re-reads W per row tile); its NW waves split K in 32-deep k-blocks and meet in LDS, summed by
+// wave 0 in a fixed pairwise tree over the wave index (deterministic, no atomics), which then runs
+// the skinny kernel's epilogues.
+// Lane l = (frow = l & 15, q = l >> 4) loads one 16-byte piece of Wb row n0 + 16j + frow — the
+// eight bf16 at k = 32 kb + 8 q .. + 8, unpacked with u << 16 / u & 0xffff0000 — and the same
+// eight k of A rows 16 i + frow as two float4; sub-step s of the piece's eight MFMAs feeds
+// k = 32 kb + 8 q + s on both operands (the K-permutation of gemm_lds_kernel: W as the first
+// operand, A as the second, so the accumulators have the register-direct epilogue layout).  CH
+// k-blocks are in flight per memory round trip.  All arithmetic is fp32: the result is that of
+// the model float(Wb).
+//
+// Norm launches: Wb is NOT norm-folded (as in the bf16 GEMV), so g = GemmArgs::norm_w is
+// multiplied into the A fragment, each row's sum of squares comes from the raw x of the same
+// loads, and 1/sqrt(mean + eps) is applied per row in the epilogue.
+// NT: the Wb pieces are loaded non-temporal (the gemv_nt rule: >= 64 MB of bf16 per launch).
+// Rows are clamped at M - 1 and W rows at N - 1 for the loads, stores are predicated: M need not
+// be a multiple of 16, nor N of 16 * TN.
+template <int EPI, int TN, int MT, int CH, bool NT = false, int NW = 4>
+__global__ void __launch_bounds__(64 * NW) gemm_rows_bf16_kernel(GemmArgs p) {
+    static_assert(EPI != EPI_SWIGLU || TN % 2 == 0, "SwiGLU pairs gate / up tiles");
+    static_assert(MT == 1 || MT == 2 || MT == 4, "up to 64 rows");
+    constexpr int WN = 16 * TN;
+    constexpr bool GN = EPI != EPI_RESID;  // the norm weight may ride on x (p.norm_w)
+    __shared__ f32x4 red[NW - 1][MT][TN][64];  // waves 1 .. NW - 1 (wave 0 keeps its registers)
+    __shared__ float rss[NW - 1][MT][64];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int frow = lane & 15, kq = 8 * (lane >> 4), fq4 = 4 * (lane >> 4);
+    const int n0 = blockIdx.x * WN;
+    const float* arow[MT];
+#pragma unroll
+    for (int i = 0; i < MT; ++i) arow[i] = a_row(p, min(16 * i + frow, p.M - 1));
+    const u32x4* wrow[TN];
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+        wrow[j] = reinterpret_cast<const u32x4*>(p.Wb + (int64_t)min(n0 + 16 * j + frow, p.N - 1) * p.K);
+    const bool gn = GN && p.norm_w != nullptr;  // launch-uniform
+    // The rows' sums of squares are taken in every launch, also where no row factor is applied
+    // (EPI_RESID, a plain product): 16 FMAs per row tile and k-block beside 8 * TN MFMAs.  Guarding
+    // them measured slower, not faster — by the launch-uniform p.norm inside the k loop, or compiled
+    // out of EPI_RESID, a 32-row Llama-3-shape decode step went from 8.86 to 9.68 / 9.61 ms and a
+    // 64-row one from 14.68 to 14.85 / 14.70 (hipcc schedules the k loop differently; DESIGN.md
+    // decisions table)
+    // the epilogue's own operands, fetched with the first fragments (as gemm_skinny_kernel does)
+    f32x4 res[EPI == EPI_RESID ? MT * TN : 1];
+    float2 pcs[EPI == EPI_QKV && MT == 1 ? TN : 1], psn[EPI == EPI_QKV && MT == 1 ? TN : 1];
+    if constexpr (EPI == EPI_RESID) {
+#pragma unroll
+        for (int i = 0; i < MT; ++i) {
+            const float* rb = res_row(p, min(16 * i + frow, p.M - 1));
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+                res[i * TN + j] = *reinterpret_cast<const f32x4*>(rb + min(n0 + j * 16 + fq4, p.N - 4));
+        }
+    } else if constexpr (EPI == EPI_QKV && MT == 1) {
+        qkv_tables<TN>(p, 0, n0, lane, pcs, psn);
+    }
+    // NA accumulators per tile, sub-step s of every piece on accumulator s % NA: the eight MFMAs
+    // of a piece do not wait for each other, and each chain of rounded additions is 1 / NA as long
+    // (one and two row tiles, where the kernel is measured against the GEMV's short per-lane sums)
+    constexpr int NA = MT * TN >= 8 ? 1 : MT * TN == 4 ? 2 : MT * TN == 2 ? 4 : 8;
+    f32x4 accs[NA][MT][TN];
+    float ss[MT];
+#pragma unroll
+    for (int i = 0; i < MT; ++i) {
+        ss[i] = 0.f;
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int n = 0; n < NA; ++n) accs[n][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    const int nkb = p.K >> 5;
+    const int kb_lo = wid * nkb / NW, kb_hi = (wid + 1) * nkb / NW;  // this wave's k-blocks
+    for (int kb0 = kb_lo; kb0 < kb_hi; kb0 += CH) {
+        u32x4 wv[CH][TN];
+        f32x4 av[CH][MT][2], gv[GN ? CH : 1][2];
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+            const int k = 32 * min(kb0 + c, kb_hi - 1) + kq;
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+                wv[c][j] = NT ? __builtin_nontemporal_load(wrow[j] + (k >> 3)) : wrow[j][k >> 3];
+#pragma unroll
+            for (int i = 0; i < MT; ++i) {
+                av[c][i][0] = *reinterpret_cast<const f32x4*>(arow[i] + k);
+                av[c][i][1] = *reinterpret_cast<const f32x4*>(arow[i] + k + 4);
+            }
+            if constexpr (GN) {
+                if (gn) {
+                    gv[c][0] = *reinterpret_cast<const f32x4*>(p.norm_w + k);
+                    gv[c][1] = *reinterpret_cast<const f32x4*>(p.norm_w + k + 4);
+                }
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+            if (kb0 + c < kb_hi) {  // wave-uniform
+                float wf[TN][8];
+#pragma unroll
+                for (int j = 0; j < TN; ++j) {
+                    wf[j][0] = bf16_lo(wv[c][j].x); wf[j][1] = bf16_hi(wv[c][j].x);
+                    wf[j][2] = bf16_lo(wv[c][j].y); wf[j][3] = bf16_hi(wv[c][j].y);
+                    wf[j][4] = bf16_lo(wv[c][j].z); wf[j][5] = bf16_hi(wv[c][j].z);
+                    wf[j][6] = bf16_lo(wv[c][j].w); wf[j][7] = bf16_hi(wv[c][j].w);
+                }
+#pragma unroll
+                for (int i = 0; i < MT; ++i) {
+                    f32x4& xa = av[c][i][0];
+                    f32x4& xb = av[c][i][1];
+                    ss[i] += xa.x * xa.x + xa.y * xa.y + xa.z * xa.z + xa.w * xa.w +
+                             xb.x * xb.x + xb.y * xb.y + xb.z * xb.z + xb.w * xb.w;
+                    if constexpr (GN) {
+                        if (gn) {
+                            xa *= gv[c][0];
+                            xb *= gv[c][1];
+                        }
+                    }
+                }
+                // sub-step outermost: consecutive MFMAs write different accumulators
+#pragma unroll
+                for (int s = 0; s < 8; ++s)
+#pragma unroll
+                    for (int i = 0; i < MT; ++i)
+#pragma unroll
+                        for (int j = 0; j < TN; ++j)
+                            accs[s % NA][i][j] = mfma4(wf[j][s], av[c][i][s >> 2][s & 3], accs[s % NA][i][j]);
+            }
+        }
+    }
+    // the wave's partial tile: its accumulators added pairwise in a fixed tree (neighbours first)
+    f32x4 acc[MT][TN];
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+#pragma unroll
+            for (int st = 1; st < NA; st *= 2)
+#pragma unroll
+                for (int n = 0; n + st < NA; n += 2 * st) accs[n][i][j] += accs[n + st][i][j];
+            acc[i][j] = accs[0][i][j];
+        }
+    if (wid != 0) {
+#pragma unroll
+        for (int i = 0; i < MT; ++i) {
+#pragma unroll
+            for (int j = 0; j < TN; ++j) red[wid - 1][i][j][lane] = acc[i][j];
+            rss[wid - 1][i][lane] = ss[i];
+        }
+    }
+    __syncthreads();
+    if (wid != 0) return;
+    // wave 0 adds the waves' partial tiles pairwise in a fixed tree ((w0 + w1) + (w2 + w3)) + ...:
+    // fewer additions at the full magnitude than a running sum, and the same bits every launch
+    float rs[MT];
+#pragma unroll
+    for (int i = 0; i < MT; ++i) {
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+            f32x4 t[NW];
+            t[0] = acc[i][j];
+#pragma unroll
+            for (int w = 1; w < NW; ++w) t[w] = red[w - 1][i][j][lane];
+#pragma unroll
+            for (int st = 1; st < NW; st *= 2)
+#pragma unroll
+                for (int w = 0; w + st < NW; w += 2 * st) t[w] += t[w + st];
+            acc[i][j] = t[0];
+        }
+#pragma unroll
+        for (int w = 1; w < NW; ++w) ss[i] += rss[w - 1][i][lane];
+        const float v = sum_xor16_32(ss[i]);  // the four k-quarters of the row
+        rs[i] = p.norm ? __builtin_amdgcn_rsqf(v / (float)p.K + p.eps) : 1.0f;
+    }
+    if constexpr (EPI == EPI_QKV) {
+        if constexpr (MT == 1) qkv_epilogue<1, TN, true>(p, acc, rs, 0, n0, lane, pcs, psn);
+        else qkv_epilogue<MT, TN>(p, acc, rs, 0, n0, lane);
+    } else if constexpr (EPI == EPI_RESID) {
+        direct_epilogue<MT, TN, EPI, true, MT * TN>(p, acc, rs, res, 0, n0, lane);
+    } else {
+        direct_epilogue<MT, TN, EPI, false, 1>(p, acc, rs, res, 0, n0, lane);
+    }
+}
+
 }  // namespace l3

@@ -134,11 +134,15 @@ struct GemmArgs {
                                    // [N][3][K] (null: the fp32 MFMA kernels)
     // opt-in bf16 weight storage (l3_set_weight_bf16; DESIGN.md "bf16 weight storage"): W as one
     // bf16 value per element, [N, K] row-major in W's row layout and WITHOUT the RMSNorm fold, read
-    // by the bf16-weight form of gemv_kernel only (launch_gemm takes it exactly where the launch
-    // goes to gemv_kernel, gemm_takes_bf16; every other kernel reads W).  norm_w [K]: the RMSNorm
-    // weight that form multiplies into the activations instead (null: none)
+    // by the bf16-weight form of gemv_kernel (where the launch goes to gemv_kernel,
+    // gemm_takes_bf16) and by gemm_rows_bf16_kernel (2 .. wb_rows rows against at least
+    // wb_min_bytes of bf16, gemm_takes_bf16_rows); every other kernel reads W.  norm_w [K]: the
+    // RMSNorm weight those two multiply into the activations instead (null: none)
     const unsigned short* Wb;
     const float* norm_w;
+    // the context's l3_set_weight_bf16_rows setting (runtime.hip gemm()): the largest M that
+    // gemm_rows_bf16_kernel takes (0: none) and the least N * K * 2 bytes of Wb it takes
+    int wb_rows; int64_t wb_min_bytes;
     float* C; int64_t ldc;         // output (EPI_QKV: unused)
     int M, N, K;
     bool norm;                     // RMSNorm on A: rows scaled by 1/sqrt(mean(A^2)+eps); the norm
@@ -204,8 +208,13 @@ struct GemmArgs {
     float* ws; int64_t ws_cap;
     int splits;                    // set by launch_gemm
     // the skinny MFMA kernel whatever M and W (a pruned last layer: every row rounds the same
-    // way for any batch split, runtime.hip run_layer last_rows)
+    // way for any batch split, runtime.hip run_layer last_rows) — unless gemm_rows_bf16_kernel
+    // takes the launch first (speculative chunks with bf16 storage; never with split_rows)
     bool force_skinny;
+    // M is a batch split's share of the rows (the pruned last layer of a model forward): the
+    // launch keeps a kernel whose rows round the same way at any M, so gemm_rows_bf16_kernel —
+    // whose accumulator and wave counts follow the row tiles — does not take it
+    bool split_rows;
     // EPI_STORE: that gemm_store_config id (1..3) on the tiled kernels whatever M, N and K (0: by
     // shape) — scoring keeps one configuration for every row chunk of a call, so a row rounds the
     // same way wherever the chunk boundaries fall; 3 is always the 128 x 128 tile
@@ -614,6 +623,10 @@ bool gemm_is_gemv(const GemmArgs& a);
 bool gemv_direct(const GemmArgs& a);
 // true when launch_gemm serves this launch from GemmArgs::Wb (the bf16-weight gemv_kernel)
 bool gemm_takes_bf16(int epi, const GemmArgs& a);
+// true when launch_gemm serves this launch from GemmArgs::Wb on gemm_rows_bf16_kernel (2 ..
+// GemmArgs::wb_rows rows, N * K * 2 >= GemmArgs::wb_min_bytes); checked before every other choice
+bool gemm_takes_bf16_rows(int epi, const GemmArgs& a);
+constexpr int WB_ROWS_MAX = 64;  // rows gemm_rows_bf16_kernel is instantiated for
 // bf16 weight storage (misc.hip): out[i] = bf16(w[i]), round-to-nearest-even on the top 16 bits
 // (NaN -> 0x7fc0); *n_inexact (a pair, zeroed by the caller) += the elements whose value changed
 // (NaN not counted) — pair entry (i / sel_stride) & 1 when sel_stride > 0 (gate / up interleaved

@@ -111,6 +111,14 @@ struct l3_ctx {
     unsigned short* lm_headb = nullptr;
     int64_t wb_bytes = 0;            // bytes of the bf16 copies
     int64_t wb_launches = 0;         // GEMV launches issued on them (a captured step: at capture)
+    // 2 .. wb_rows rows on the bf16 copies (l3_set_weight_bf16_rows, L3_WEIGHT_BF16_ROWS /
+    // L3_WEIGHT_BF16_MIN_BYTES; gemm.hip gemm_takes_bf16_rows): the largest M (0: off) and the
+    // least bf16 bytes of a launch's weight that gemm_rows_bf16_kernel takes; its launches
+    static constexpr int WB_ROWS_DEFAULT = 32;  // measured: DESIGN.md "bf16 weight storage for 2-64 rows"
+    static constexpr int64_t WB_ROWS_MIN_BYTES_DEFAULT = (int64_t)32 << 20;
+    int wb_rows = WB_ROWS_DEFAULT;
+    int64_t wb_rows_min_bytes = WB_ROWS_MIN_BYTES_DEFAULT;
+    int64_t wb_rows_launches = 0;
     // layer 0's QKV of a prefill as a lookup in a table of its pre-RoPE rows per token id
     // (embed_qkv.h, l3_set_embed_qkv, L3_EMBED_QKV): built at the first call that qualifies, on
     // stream, if its bytes fit embed_qkv_cap; a refused allocation is not retried
@@ -488,6 +496,18 @@ extern "C" int l3_create(int32_t device, const l3_dims* dims, l3_ctx** out) {
     {
         const int m = env_knob("L3_WEIGHT_BF16", 0);
         c->weight_bf16 = m == 1 || m == 2 ? m : 0;
+        // l3_set_weight_bf16_rows' defaults for new contexts (values out of range: ignored)
+        // and text that is not a number
+        if (const char* rw = getenv("L3_WEIGHT_BF16_ROWS"); rw && *rw) {
+            char* end = nullptr;
+            const long r = strtol(rw, &end, 10);
+            if (end != rw && *end == '\0' && (r == 0 || (r >= 2 && r <= WB_ROWS_MAX))) c->wb_rows = (int)r;
+        }
+        if (const char* mb = getenv("L3_WEIGHT_BF16_MIN_BYTES"); mb && *mb) {
+            char* end = nullptr;
+            const long long v = strtoll(mb, &end, 10);
+            if (end != mb && *end == '\0' && v >= 0) c->wb_rows_min_bytes = v;  // whole string a number
+        }
     }
     c->embed_qkv = env_knob("L3_EMBED_QKV", 1) != 0;
     {  // split-KV ragged decode attention defaults for new contexts (values out of range: ignored)
@@ -823,9 +843,16 @@ extern "C" int l3_weight_bf16_info(l3_ctx* c, int32_t* mode, int64_t* bytes, int
     return 0;
 }
 
-// launch_gemm, counting the launches served from the bf16 copies (l3_weight_bf16_info)
-static hipError_t gemm(l3_ctx* c, int epi, const GemmArgs& g, hipStream_t s) {
-    if (g.Wb && gemm_takes_bf16(epi, g)) c->wb_launches += 1;
+// launch_gemm, counting the launches served from the bf16 copies (the GEMV: l3_weight_bf16_info;
+// gemm_rows_bf16_kernel: l3_weight_bf16_rows_info); the context's rows setting travels in the
+// arguments, so two contexts of one process may differ
+static hipError_t gemm(l3_ctx* c, int epi, const GemmArgs& g_in, hipStream_t s) {
+    if (!g_in.Wb) return launch_gemm(epi, g_in, s);
+    GemmArgs g = g_in;
+    g.wb_rows = c->wb_rows;
+    g.wb_min_bytes = c->wb_rows_min_bytes;
+    if (gemm_takes_bf16_rows(epi, g)) c->wb_rows_launches += 1;
+    else if (gemm_takes_bf16(epi, g)) c->wb_launches += 1;
     return launch_gemm(epi, g, s);
 }
 
@@ -993,7 +1020,8 @@ static int check_call(l3_ctx* c, int B, int L, int start_pos) {
 // and down run on B rows instead of B*L: the logits and every cache slot are what the full
 // layer gives (the other rows of h are never read again: the next forward starts from the
 // embedding).  Those GEMMs always take the skinny MFMA kernel, whose rows round the same way
-// at any M, so a batch split still gives bit-identical logits
+// at any M, so a batch split still gives bit-identical logits (GemmArgs::split_rows keeps them
+// off gemm_rows_bf16_kernel, which rounds by row-tile count, whatever l3_set_weight_bf16_rows says)
 static int run_layer(l3_ctx* c, int li, int B, int L, int start_pos, const int* pos_dev = nullptr,
                      const int32_t* emb_ids = nullptr, int b0 = 0, hipStream_t s = nullptr,
                      bool last_rows = false) {
@@ -1064,7 +1092,7 @@ static int run_layer(l3_ctx* c, int li, int B, int L, int start_pos, const int* 
         if (kv_only) {
             GemmArgs gq = g;  // q of the last rows: [B, qdim], compact
             gq.A = hl; gq.lda = (int64_t)L * D4; gq.W = Ly.wqkv; gq.W3 = nullptr; gq.Wb = Ly.wqkvb; gq.N = c->qdim; gq.col_base = 0;
-            gq.M = B; gq.L = 1; gq.start_pos = start_pos + L - 1; gq.force_skinny = true;
+            gq.M = B; gq.L = 1; gq.start_pos = start_pos + L - 1; gq.force_skinny = gq.split_rows = true;
             gq.ws = nullptr;
             if (timed_on(c, L3_K_QKV, s, [&] { return gemm(c, EPI_QKV, gq, s); })) return 1;
             a.q = q; a.B = B; a.L = 1; a.start_pos = start_pos + L - 1;  // one query per sequence
@@ -1076,16 +1104,16 @@ static int run_layer(l3_ctx* c, int li, int B, int L, int start_pos, const int* 
             o.A = attn + (int64_t)(L - 1) * c->qdim; o.lda = (int64_t)L * c->qdim;
         }
         o.W = Ly.wo; o.Wb = Ly.wob; o.C = hl; o.ldc = (int64_t)L * D4;
-        o.M = B; o.N = D4; o.K = c->qdim; o.norm = false; o.force_skinny = true;
+        o.M = B; o.N = D4; o.K = c->qdim; o.norm = false; o.force_skinny = o.split_rows = true;
         if (timed_on(c, L3_K_OPROJ, s, [&] { return gemm(c, EPI_RESID, o, s); })) return 1;
         GemmArgs gl{};  // rmsnorm -> gate|up -> SwiGLU on the last rows
         gl.A = hl; gl.lda = (int64_t)L * D4; gl.W = Ly.wgu; gl.C = hid; gl.ldc = FD;
         gl.Wb = Ly.wgub; gl.norm_w = Ly.wgub ? Ly.n_ffn : nullptr;
-        gl.M = B; gl.N = 2 * FD; gl.K = D4; gl.norm = true; gl.eps = c->d.norm_eps; gl.force_skinny = true;
+        gl.M = B; gl.N = 2 * FD; gl.K = D4; gl.norm = true; gl.eps = c->d.norm_eps; gl.force_skinny = gl.split_rows = true;
         if (timed_on(c, L3_K_GATEUP, s, [&] { return gemm(c, EPI_SWIGLU, gl, s); })) return 1;
         GemmArgs dl{};  // down + residual on the last rows
         dl.A = hid; dl.lda = FD; dl.W = Ly.wd; dl.Wb = Ly.wdb; dl.C = hl; dl.ldc = (int64_t)L * D4;
-        dl.M = B; dl.N = D4; dl.K = FD; dl.norm = false; dl.force_skinny = true;
+        dl.M = B; dl.N = D4; dl.K = FD; dl.norm = false; dl.force_skinny = dl.split_rows = true;
         return timed_on(c, L3_K_DOWN, s, [&] { return gemm(c, EPI_RESID, dl, s); });
     }
     GemmArgs gu{};  // rmsnorm -> gate|up -> SwiGLU
@@ -1242,10 +1270,18 @@ static int forward_dev(l3_ctx* c, const int32_t* ids_dev, int B, int L, int star
     }
     // the lm_head too runs per part when every part picks the unsplit batch's tile (then each
     // part's lm_head overlaps the other parts' last layer); otherwise once after the join
-    bool lm_parts = parts > 1;
+    // (gemm_rows_bf16_kernel rounds by row-tile count: where it would take the batch's lm_head or a
+    // part's, the lm_head runs once after the join, on the unsplit batch's M)
+    auto lm_rows = [&](int n, int first) {
+        GemmArgs g = lm_head_args(c, n, L, logits_dev, first);
+        g.wb_rows = c->wb_rows;
+        g.wb_min_bytes = c->wb_rows_min_bytes;
+        return gemm_takes_bf16_rows(EPI_STORE, g);
+    };
+    bool lm_parts = parts > 1 && !lm_rows(B, 0);
     const int lm_cfg = gemm_store_config(lm_head_args(c, B, L, logits_dev, 0));
     for (int p = 0; p < parts && lm_parts; ++p)
-        lm_parts = gemm_store_config(lm_head_args(c, nb[p], L, logits_dev, b0[p])) == lm_cfg;
+        lm_parts = gemm_store_config(lm_head_args(c, nb[p], L, logits_dev, b0[p])) == lm_cfg && !lm_rows(nb[p], b0[p]);
     int rc = 0;
     const int nl = (int)c->layers.size();
     // host path (logits_host): the logits copy is PCIe-bound (32.8 MB at C3, ~0.59 ms at 56 GB/s)
@@ -1835,6 +1871,39 @@ extern "C" int l3_get_sampling(l3_ctx* c, float* temperature, int32_t* top_k, fl
     if (top_k) *top_k = c->samp.top_k;
     if (top_p) *top_p = c->samp.top_p;
     if (seed) *seed = (uint64_t)c->samp.seed_hi << 32 | c->samp.seed_lo;
+    return 0;
+}
+
+// 2 .. max_rows rows on the bf16 copies (DESIGN.md "bf16 weight storage for 2-64 rows").  The
+// arguments are checked before anything else, so a bad value is reported whatever the context.
+extern "C" int l3_set_weight_bf16_rows(l3_ctx* c, int32_t max_rows, int64_t min_bytes) {
+    if (max_rows != -1 && max_rows != 0 && (max_rows < 2 || max_rows > WB_ROWS_MAX))
+        return fail("l3_set_weight_bf16_rows: max_rows %d must be 0 (off), in [2, %d], or -1 (keep)", max_rows, WB_ROWS_MAX);
+    if (min_bytes < -1)
+        return fail("l3_set_weight_bf16_rows: min_bytes %lld must be >= 0, or -1 (keep)", (long long)min_bytes);
+    CHECK_CTX(c);
+    if (c->group && group_members(c->group) > 1)
+        return fail("l3_set_weight_bf16_rows: this context is a member of a multi-device l3_group (not supported)");
+    const int rows = max_rows == -1 ? c->wb_rows : max_rows;
+    const int64_t mb = min_bytes == -1 ? c->wb_rows_min_bytes : min_bytes;
+    if (rows == c->wb_rows && mb == c->wb_rows_min_bytes) return 0;
+    // the captured steps hold the kernels they were captured with: dropped as l3_set_sampling
+    // drops them, so the next decode step runs eagerly and captures again with the new choice
+    if (set_dev(c) || spec_resolve(c) || persist_settle(c)) return 1;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    drop_decode_graph(c);
+    c->persist_graph = false;
+    c->dec_pos_mirror = -1;
+    c->wb_rows = rows;
+    c->wb_rows_min_bytes = mb;
+    return 0;
+}
+
+extern "C" int l3_weight_bf16_rows_info(l3_ctx* c, int32_t* max_rows, int64_t* min_bytes, int64_t* launches) {
+    CHECK_CTX(c);
+    if (max_rows) *max_rows = c->wb_rows;
+    if (min_bytes) *min_bytes = c->wb_rows_min_bytes;
+    if (launches) *launches = c->wb_rows_launches;
     return 0;
 }
 
@@ -3240,8 +3309,44 @@ extern "C" int l3_op_linear_bf16_host(l3_ctx* c, const float* x, int64_t rows, i
         g.M = (int)(rows - r0 < per ? rows - r0 : per); g.N = N; g.K = K;
         if (!gemm_takes_bf16(EPI_STORE, g))
             return fail("l3_op_linear_bf16: %d x %d x %d is not a shape of the weight-streaming GEMV", g.M, K, N);
-        HIP_TRY(gemm(c, EPI_STORE, g, c->stream));
+        c->wb_launches += 1;  // always the GEMV, whatever l3_set_weight_bf16_rows says
+        HIP_TRY(launch_gemm(EPI_STORE, g, c->stream));
     }
+    D2H(y, dy, rows * N);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// gemm_rows_bf16_kernel with EPI_STORE on plain arrays: y [rows, N] = x [rows, K] . float(w)^T, with
+// norm_w the RMSNorm of x first.  No other kernel stands in, and the context's own rows setting
+// plays no part: the launch carries max_rows 64 and min_bytes 0
+extern "C" int l3_op_linear_bf16_rows_host(l3_ctx* c, const float* x, int64_t rows, int32_t K, int32_t N,
+                                           const uint16_t* w_u16, const float* norm_w, float eps, float* y) {
+    CHECK_CTX(c);
+    if (!x || !w_u16 || !y) return fail("l3_op_linear_bf16_rows: null argument");
+    if (rows < 2 || rows > WB_ROWS_MAX)
+        return fail("l3_op_linear_bf16_rows: rows = %lld outside [2, %d] (the kernel's range)", (long long)rows, WB_ROWS_MAX);
+    if (K <= 0 || K % 32) return fail("l3_op_linear_bf16_rows: K=%d must be a positive multiple of 32", K);
+    if (N <= 0 || N % 4) return fail("l3_op_linear_bf16_rows: N=%d must be a positive multiple of 4", N);
+    if (set_dev(c)) return 1;
+    Scratch S{c};
+    SCRATCH(dx, rows * K);
+    SCRATCH(dw, ((int64_t)N * K + 1) / 2);
+    SCRATCH(dg, K);
+    SCRATCH(dy, rows * N);
+    H2D(dx, x, rows * K);
+    HIP_TRY(hipMemcpyAsync(dw, w_u16, (size_t)N * K * 2, hipMemcpyHostToDevice, c->stream));
+    if (norm_w) H2D(dg, norm_w, K);
+    GemmArgs g{};
+    g.A = dx; g.lda = K; g.W = nullptr; g.Wb = reinterpret_cast<const unsigned short*>(dw);
+    g.norm_w = norm_w ? dg : nullptr; g.norm = norm_w != nullptr; g.eps = eps;
+    g.C = dy; g.ldc = N;
+    g.M = (int)rows; g.N = N; g.K = K;
+    g.wb_rows = WB_ROWS_MAX; g.wb_min_bytes = 0;
+    if (!gemm_takes_bf16_rows(EPI_STORE, g))
+        return fail("l3_op_linear_bf16_rows: %d x %d x %d is not a shape of the bf16 rows kernel", g.M, K, N);
+    c->wb_rows_launches += 1;
+    HIP_TRY(launch_gemm(EPI_STORE, g, c->stream));
     D2H(y, dy, rows * N);
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;

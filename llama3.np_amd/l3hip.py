@@ -104,6 +104,9 @@ _SIGNATURES = {
     "l3_set_embed_qkv": (ctypes.c_int, [_P, _I32, _I64]),
     "l3_set_weight_bf16": (ctypes.c_int, [_P, _I32]),
     "l3_weight_bf16_info": (ctypes.c_int, [_P, _P, _P, _P]),
+    "l3_set_weight_bf16_rows": (ctypes.c_int, [_P, _I32, _I64]),
+    "l3_weight_bf16_rows_info": (ctypes.c_int, [_P, _P, _P, _P]),
+    "l3_op_linear_bf16_rows_host": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _P, _P, _F, _P]),
     "l3_op_to_bf16_host": (ctypes.c_int, [_P, _P, _I64, _P, _P]),
     "l3_op_linear_bf16_host": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _P, _P, _F, _P]),
     "l3_set_last_layer_rows": (ctypes.c_int, [_P, _I32]),
@@ -660,6 +663,20 @@ class Context:
         check(lib().l3_weight_bf16_info(self._h, ctypes.byref(m), ctypes.byref(b), ctypes.byref(n)))
         return {"mode": m.value, "bytes": b.value, "gemv_launches": n.value}
 
+    def set_weight_bf16_rows(self, max_rows: Optional[int] = None, min_bytes: Optional[int] = None) -> None:
+        """Extension (l3_set_weight_bf16_rows): with bf16 weight storage on, launches of 2 ..
+        ``max_rows`` rows (0: off; at most 64) against a weight of at least ``min_bytes`` bf16 bytes
+        run on the weight-streaming MFMA kernel that reads the bf16 copy once.  ``None`` keeps a
+        value.  Before or after ``finalize``; a change re-captures the decode steps."""
+        check(lib().l3_set_weight_bf16_rows(self._h, -1 if max_rows is None else int(max_rows),
+                                            -1 if min_bytes is None else int(min_bytes)))
+
+    def weight_bf16_rows_info(self) -> dict:
+        """``max_rows`` and ``min_bytes`` in force and the ``launches`` issued on that kernel."""
+        r, b, n = ctypes.c_int32(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        check(lib().l3_weight_bf16_rows_info(self._h, ctypes.byref(r), ctypes.byref(b), ctypes.byref(n)))
+        return {"max_rows": r.value, "min_bytes": b.value, "launches": n.value}
+
     def synchronize(self) -> None:
         check(lib().l3_synchronize(self._h))
 
@@ -855,6 +872,24 @@ class Context:
         y = np.empty((x.shape[0], w.shape[0]), np.float32)
         check(lib().l3_op_linear_bf16_host(self._h, ptr(x), x.shape[0], x.shape[1], w.shape[0], ptr(w),
                                            ptr(g) if g is not None else None, float(eps), ptr(y)))
+        return y
+
+    def op_linear_bf16_rows(self, x: np.ndarray, w_u16: np.ndarray, norm_w: Optional[np.ndarray] = None,
+                            eps: float = 0.0) -> np.ndarray:
+        """``x [2 <= rows <= 64, K] @ W.T`` with W [N, K] given as bf16 bit patterns (uint16), on the
+        weight-streaming MFMA kernel of ``set_weight_bf16_rows`` (l3_op_linear_bf16_rows_host); with
+        ``norm_w`` the RMSNorm of x (weight norm_w, ``eps``) is applied first.  A shape that kernel
+        does not take raises."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        w = np.ascontiguousarray(w_u16, dtype=np.uint16)
+        if x.ndim != 2 or w.ndim != 2 or w.shape[1] != x.shape[1]:
+            raise ValueError(f"x {x.shape} and w {w.shape} must be [rows, K] and [N, K]")
+        g = None if norm_w is None else np.ascontiguousarray(norm_w, dtype=np.float32)
+        if g is not None and g.shape != (x.shape[1],):
+            raise ValueError(f"norm_w {g.shape} must be [K = {x.shape[1]}]")
+        y = np.empty((x.shape[0], w.shape[0]), np.float32)
+        check(lib().l3_op_linear_bf16_rows_host(self._h, ptr(x), x.shape[0], x.shape[1], w.shape[0], ptr(w),
+                                                ptr(g) if g is not None else None, float(eps), ptr(y)))
         return y
 
     def op_linear_logprob(self, x: np.ndarray, w: np.ndarray, targets: np.ndarray):

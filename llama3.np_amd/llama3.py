@@ -298,7 +298,10 @@ class Llama:
         decode GEMVs (half the bytes per token) and needs a checkpoint whose values are bf16
         already, as published Llama-3 weights are — a tensor that is not raises ``ValueError``
         naming it; ``"bf16-round"`` rounds them (``utils.round_bf16``), and the model computed is
-        the rounded one on every path.  Not with more than one device.
+        the rounded one on every path.  Not with more than one device.  Launches of 2 .. 32 rows
+        against a large weight (batched and ragged decode, speculative chunks, continuations at the
+        Llama-3 shape) stream the bf16 copies too; ``model.context.set_weight_bf16_rows`` moves
+        the row and weight-size limits (DESIGN.md "bf16 weight storage for 2-64 rows").
 
         ``devices=[0, ..., N-1]``: one process drives N GPUs (``l3hip.Group``, the C ABI's
         l3_group_*).  Every call keeps the reference's signature and result: batch row r runs on
