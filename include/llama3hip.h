@@ -497,6 +497,60 @@ int l3_op_linear_bf16_host(l3_ctx* ctx, const float* x, int64_t rows, int32_t K,
  * context. */
 int l3_op_linear_bf16_rows_host(l3_ctx* ctx, const float* x, int64_t rows, int32_t K, int32_t N,
                                 const uint16_t* w_u16, const float* norm_w, float eps, float* y);
+/* One GEMM launch with any fused epilogue, on plain host arrays (tests/test_gpu_gemm_routes.py):
+ * the dense contractions of llama3.py:166-168 / :211 / :99-102 / :304-307 with what the kernels
+ * fuse into them, through exactly one call of the library's GEMM dispatcher, and a report of the
+ * kernel it chose.  A launch the dispatcher refuses is an error: no other kernel stands in.
+ *   epi 0  c[M, N] = s * (x @ w^T)                        (s = 1 / sqrt(mean(x^2) + eps) with norm, else 1)
+ *   epi 1  c[M, N] = res + x @ w^T                         (res: c as given, or res_src rows)
+ *   epi 2  c[M, N/2] = silu(s * g) * (s * u)               (w in the kernels' gate|up layout: 16 gate
+ *                                                           rows, then the 16 up rows of the same units)
+ *   epi 3  s * (x @ w^T) as [q | k | v] columns from col_base on: RoPE on (even, odd) pairs of q and
+ *          k at position start_pos + r % L (llama3.py:41-76), q * q_scale to q_out[r], k / v to
+ *          slot start_pos + r % L of sequence r / L of the caches (llama3.py:184-185)
+ * fp32 storage: the caller has folded an RMSNorm weight into w.  bf16 storage (bf16 != 0): the
+ * entry stores w as bf16 and as float(bf16(w)) (the round mode of l3_set_weight_bf16) and norm_w
+ * [K] is the RMSNorm weight (required with norm).  a_rows [M] (may be NULL) gathers the A rows
+ * from x [x_rows, K]; res_src [res_src_rows, N] with res_rows [M] (may be NULL: row r) replaces
+ * c as epi 1's residual.  c, q_out and the caches are in/out and carry guard space the launch
+ * must leave alone: c_rows >= M + 1, q_rows >= M + 1, cache_B >= M / L + 1.
+ * Route controls (0: off): ws_floats (a split-K workspace of that many floats), force_skinny,
+ * force_tiled (passed through unchanged), x6 (the three-piece bf16 planes are built from w),
+ * wb_rows / wb_min_bytes (the l3_set_weight_bf16_rows setting of this launch).
+ * route (out): [0] family (0 none, 1 gemv, 2 gemv_bf16, 3 skinny, 4 splitk, 5 tiled, 6 x6,
+ * 7 rows_bf16), [1..5] by family — gemv: rows per block, lanes per unit, non-temporal, row blocks;
+ * skinny: column tiles, k-blocks per round trip; splitk: slice tile BM, BN, BK, slices; tiled:
+ * BM, BN, BK, LDS stages, group_m; x6: BM, BN, BK, waves, group_m; rows_bf16: row tiles, waves,
+ * non-temporal, column tiles — [6] launch sites passed.  struct_size = sizeof(l3_gemm_op). */
+typedef struct l3_gemm_op {
+    int32_t struct_size;
+    int32_t epi, M, N, K;
+    int32_t norm;
+    float eps;
+    float q_scale;
+    const float* x;
+    const float* w;
+    const float* norm_w;
+    const int32_t* a_rows;
+    int64_t x_rows;
+    float* c;
+    int64_t c_rows;
+    const float* res_src;
+    const int32_t* res_rows;
+    int64_t res_src_rows;
+    int32_t L, start_pos, H, KVH, HD, Smax, col_base, cache_B;
+    const float* rope_cos;
+    const float* rope_sin;
+    float* q_out;
+    int64_t q_rows;
+    float* cache_k;
+    float* cache_v;
+    int64_t ws_floats;
+    int64_t wb_min_bytes;
+    int32_t force_skinny, force_tiled, x6, bf16, wb_rows;
+    int32_t route[8];
+} l3_gemm_op;
+int l3_op_gemm_host(l3_ctx* ctx, l3_gemm_op* op);
 /* The scoring path of l3_score_host (llama3.py:285-308 with the logits reduced in the lm_head's
  * epilogue) on a plain product: for z = x [rows, K] @ W[N, K]^T (no norm) and targets int32 [rows]
  * (-1: no target; else in [0, N)), logprob [rows], and optionally lse [rows] and argmax int32

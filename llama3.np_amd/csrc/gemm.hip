@@ -8,6 +8,18 @@
 
 namespace l3 {
 
+// The route report: every launch site below notes the kernel it launches here (host-side, per
+// thread; ids and fields: GemmRoute in kernels.h), so a test can ask which one a launch_gemm
+// call took.  Written where the launch is, not re-derived from the shape.
+static thread_local GemmRoute g_route;
+static void note_route(int family, int v0 = 0, int v1 = 0, int v2 = 0, int v3 = 0, int v4 = 0) {
+    g_route.family = family;
+    g_route.v[0] = v0; g_route.v[1] = v1; g_route.v[2] = v2; g_route.v[3] = v3; g_route.v[4] = v4;
+    g_route.launches += 1;
+}
+GemmRoute gemm_last_route() { return g_route; }
+void gemm_route_reset() { g_route = GemmRoute{}; }
+
 // Product kernels: k-tiles filled by global_load_lds (GLDS) and the register-direct epilogue
 // (DIRECT): RMSNorm weights are folded into W at l3_finalize, the row factor comes from the A
 // fragments, the tile leaves from registers.
@@ -15,6 +27,7 @@ template <int EPI, int WM, int WN, int TM, int TN, int WPE, int BK, int NS = 2>
 static hipError_t launch(const GemmArgs& a, hipStream_t s) {
     constexpr int BM = WM * TM * 16, BN = WN * TN * 16;
     const int64_t tiles = (int64_t)((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
+    note_route(ROUTE_TILED, BM, BN, BK, NS, a.group_m);
     hipLaunchKernelGGL((gemm_lds_kernel<WM, WN, TM, TN, EPI, WPE, false, BK, true, NS>),
                        dim3((unsigned)tiles), dim3(64 * WM * WN), 0, s, a);
     return hipGetLastError();
@@ -26,6 +39,7 @@ template <int EPI, int WM, int WN, int TM, int TN>
 static hipError_t launch_x6(const GemmArgs& a, hipStream_t s) {
     constexpr int BM = WM * TM * 16, BN = WN * TN * 16;
     const int64_t tiles = (int64_t)((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
+    note_route(ROUTE_X6, BM, BN, 32, WM * WN, a.group_m);
     hipLaunchKernelGGL((gemm_x6_kernel<WM, WN, TM, TN, EPI, 2>), dim3((unsigned)tiles), dim3(64 * WM * WN), 0, s, a);
     return hipGetLastError();
 }
@@ -56,6 +70,7 @@ static hipError_t launch_split_cfg(int epi, GemmArgs a, hipStream_t s) {
         S *= 2;
     if (S == 1) return hipErrorNotReady;  // not worth it: the caller runs the unsplit tiles
     a.splits = S;
+    note_route(ROUTE_SPLITK, BM, BN, BK, S);
     hipLaunchKernelGGL((gemm_lds_kernel<WM, WN, TM, TN, EPI_STORE, 2, false, BK, true, NS, true>),
                        dim3((unsigned)(tiles * S)), dim3(64 * WM * WN), 0, s, a);
     if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
@@ -93,6 +108,7 @@ static hipError_t launch_gemv_lpu(const GemmArgs& a, hipStream_t s) {
     const int per_block = 4 * (64 / LPU);
     const dim3 grid((unsigned)((units + per_block - 1) / per_block), (unsigned)((a.M + MR - 1) / MR)),
         block(256);
+    note_route(a.Wb ? ROUTE_GEMV_BF16 : ROUTE_GEMV, MR, LPU, NT ? 1 : 0, (int)grid.y);
     // GemmArgs::Wb (bf16 weight storage): the same grid on the bf16-weight form
     if (a.Wb)
         hipLaunchKernelGGL((gemv_kernel<EPI, MR, LPU, PARTS, NT, FOLD, true>), grid, block, MR == 1 ? 0 : (size_t)MR * a.K * 4, s, a);
@@ -197,6 +213,7 @@ static hipError_t launch_skinny(const GemmArgs& a, hipStream_t s) {
     static const bool xcd = env_knob("L3_SKINNY_XCD", 0) != 0;
     GemmArgs g = a;
     g.skinny_xcd = xcd;
+    note_route(ROUTE_SKINNY, TN, ch >= 12 ? 12 : ch >= 6 ? 6 : 2);
     if (ch >= 12)
         hipLaunchKernelGGL((gemm_skinny_kernel<EPI, TN, 12>), dim3((unsigned)blocks), dim3(256), 0, s, g);
     else if (ch >= 6)
@@ -284,11 +301,13 @@ static hipError_t launch_rows_bf16_mt(const GemmArgs& a, hipStream_t s) {
     constexpr bool WIDE_OK = MT * TN < 8;
     if constexpr (WIDE_OK) {
         if (blocks <= WB_ROWS_WIDE_BLOCKS) {
+            note_route(ROUTE_ROWS_BF16, MT, 8, nt ? 1 : 0, TN);
             if (nt) hipLaunchKernelGGL((gemm_rows_bf16_kernel<EPI, TN, MT, CH, true, 8>), dim3(blocks), dim3(512), 0, s, a);
             else hipLaunchKernelGGL((gemm_rows_bf16_kernel<EPI, TN, MT, CH, false, 8>), dim3(blocks), dim3(512), 0, s, a);
             return hipGetLastError();
         }
     }
+    note_route(ROUTE_ROWS_BF16, MT, 4, nt ? 1 : 0, TN);
     if (nt) hipLaunchKernelGGL((gemm_rows_bf16_kernel<EPI, TN, MT, CH, true, 4>), dim3(blocks), dim3(256), 0, s, a);
     else hipLaunchKernelGGL((gemm_rows_bf16_kernel<EPI, TN, MT, CH, false, 4>), dim3(blocks), dim3(256), 0, s, a);
     return hipGetLastError();

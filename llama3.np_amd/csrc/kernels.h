@@ -225,6 +225,27 @@ struct GemmArgs {
     int group_m;
 };
 constexpr int GEMV_MAXP = 8;
+
+// Which kernel the calling thread's last launch_gemm launched (gemm.hip writes it at each launch
+// site; a host-side record, read by l3_op_gemm_host).  v[] by family:
+//   gemv / gemv_bf16: rows per block, lanes per unit, NT, row blocks (grid.y)
+//   skinny:           TN (column tiles per block), k-blocks per round trip
+//   splitk:           slice tile BM, BN, BK, slices S (then splitk_finish_kernel)
+//   tiled:            BM, BN, BK, LDS stages, group_m
+//   x6:               BM, BN, BK, waves, group_m
+//   rows_bf16:        MT (row tiles), waves, NT, TN
+// launches counts the launch sites passed since gemm_route_reset (0: nothing was launched)
+enum GemmRouteFamily : int {
+    ROUTE_NONE = 0, ROUTE_GEMV = 1, ROUTE_GEMV_BF16 = 2, ROUTE_SKINNY = 3, ROUTE_SPLITK = 4, ROUTE_TILED = 5,
+    ROUTE_X6 = 6, ROUTE_ROWS_BF16 = 7,
+};
+struct GemmRoute {
+    int family;
+    int v[5];
+    unsigned launches;  // (unsigned: a long-running process wraps, never overflows)
+};
+GemmRoute gemm_last_route();
+void gemm_route_reset();
 constexpr int KV_BAK_SLOTS = 32;  // > the decode steps ever run ahead (runtime.hip SPEC_AHEAD)
 
 

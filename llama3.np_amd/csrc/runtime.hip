@@ -426,7 +426,7 @@ extern "C" const char* l3_last_error(void) { return g_err.c_str(); }
 
 extern "C" int l3_version(int32_t* major, int32_t* minor) {
     if (major) *major = 0;
-    if (minor) *minor = 18;
+    if (minor) *minor = 19;
     return 0;
 }
 
@@ -3374,6 +3374,167 @@ extern "C" int l3_op_ffn_host(l3_ctx* c, const float* x, int64_t rows, int32_t d
     if (op_linear(c, EPI_RESID, dh, rows, hidden, dim, dd, dy, false)) return 1;
     D2H(y, dy, rows * dim);
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// One launch_gemm call on plain host arrays, any epilogue and any route the dispatcher reaches
+// without the captured-decode arguments (include/llama3hip.h l3_gemm_op).  The shapes are checked
+// against the buffers here, so no kernel is handed an index outside them; what the dispatcher
+// itself refuses comes back as an error, and no other kernel stands in.
+extern "C" int l3_op_gemm_host(l3_ctx* c, l3_gemm_op* op) {
+    CHECK_CTX(c);
+    const char* who = "l3_op_gemm";
+    if (!op) return fail("%s: null argument", who);
+    if (op->struct_size != (int32_t)sizeof(l3_gemm_op))
+        return fail("%s: struct_size %d, this library's l3_gemm_op has %d bytes", who, op->struct_size, (int)sizeof(l3_gemm_op));
+    for (int i = 0; i < 8; ++i) op->route[i] = 0;
+    const int epi = op->epi, M = op->M, N = op->N, K = op->K;
+    if (epi < EPI_STORE || epi > EPI_QKV) return fail("%s: epi %d outside [0, 3]", who, epi);
+    if (M < 1 || N < 1 || K < 1 || (int64_t)M * K > INT32_MAX || (int64_t)N * K > ((int64_t)1 << 32))
+        return fail("%s: bad shape %d x %d x %d", who, M, K, N);
+    if (!op->x || !op->w) return fail("%s: null operand", who);
+    const bool qkv = epi == EPI_QKV;
+    const int64_t x_rows = op->a_rows ? op->x_rows : M;
+    if (x_rows < 1) return fail("%s: x_rows %lld", who, (long long)x_rows);
+    if (op->a_rows)
+        for (int r = 0; r < M; ++r)
+            if (op->a_rows[r] < 0 || op->a_rows[r] >= x_rows)
+                return fail("%s: a_rows[%d] = %d outside [0, %lld)", who, r, op->a_rows[r], (long long)x_rows);
+    const int64_t ldc = epi == EPI_SWIGLU ? N / 2 : N;
+    int64_t res_rows_n = 0;
+    if (!qkv) {
+        if (!op->c || op->c_rows < M + 1) return fail("%s: c must hold M + 1 = %d rows (one of guard space)", who, M + 1);
+        if ((op->res_src || op->res_rows) && epi != EPI_RESID) return fail("%s: res_src / res_rows go with EPI_RESID", who);
+        if (op->res_rows && !op->res_src) return fail("%s: res_rows without res_src", who);
+        if (op->res_src) {
+            res_rows_n = op->res_rows ? op->res_src_rows : M;
+            if (res_rows_n < 1 || (!op->res_rows && op->res_src_rows < M)) return fail("%s: res_src_rows %lld", who, (long long)op->res_src_rows);
+            if (op->res_rows)
+                for (int r = 0; r < M; ++r)
+                    if (op->res_rows[r] < 0 || op->res_rows[r] >= res_rows_n)
+                        return fail("%s: res_rows[%d] = %d outside [0, %lld)", who, r, op->res_rows[r], (long long)res_rows_n);
+        }
+    }
+    int Bq = 0;
+    int64_t qdim = 0, cache_n = 0;
+    if (qkv) {
+        const int L = op->L, H = op->H, KVH = op->KVH, HD = op->HD, Smax = op->Smax;
+        if (L < 1 || H < 1 || KVH < 1 || HD < 4 || HD % 4 || Smax < 1 || M % L)
+            return fail("%s: bad QKV geometry (L %d, H %d, KVH %d, HD %d, Smax %d, M %d)", who, L, H, KVH, HD, Smax, M);
+        if (op->start_pos < 0 || (int64_t)op->start_pos + L > Smax)
+            return fail("%s: slots [%d, %d) outside the cache's %d", who, op->start_pos, op->start_pos + L, Smax);
+        if (op->col_base != 0 && op->col_base != H * HD) return fail("%s: col_base %d is neither 0 nor H * HD", who, op->col_base);
+        // all of [q | k | v] from col_base on, or the q columns alone (a pruned last block's q launch)
+        if ((int64_t)N + op->col_base != (int64_t)(H + 2 * KVH) * HD && !(op->col_base == 0 && N == H * HD))
+            return fail("%s: N %d + col_base %d is neither (H + 2 KVH) * HD nor the q columns H * HD", who, N, op->col_base);
+        Bq = M / L;
+        qdim = (int64_t)H * HD;
+        if (!op->q_out || op->q_rows < M + 1 || !op->cache_k || !op->cache_v || op->cache_B < Bq + 1)
+            return fail("%s: q_out must hold M + 1 rows and the caches M / L + 1 sequences (guard space)", who);
+        if (!op->rope_cos || !op->rope_sin) return fail("%s: null RoPE table", who);
+        cache_n = (int64_t)op->cache_B * KVH * Smax * HD;
+    }
+    if (op->ws_floats < 0 || op->wb_rows < 0 || op->wb_min_bytes < 0) return fail("%s: negative route control", who);
+    if (op->bf16 && op->norm && !op->norm_w) return fail("%s: bf16 storage with the norm takes norm_w", who);
+    if (set_dev(c)) return 1;
+    Scratch S{c};
+    SCRATCH(dx, x_rows * K);
+    SCRATCH(dw, (int64_t)N * K);
+    H2D(dx, op->x, x_rows * K);
+    H2D(dw, op->w, (int64_t)N * K);
+    GemmArgs g{};
+    g.A = dx; g.lda = K; g.W = dw; g.M = M; g.N = N; g.K = K;
+    g.norm = op->norm != 0; g.eps = op->eps;
+    if (op->a_rows) {
+        SCRATCH(da, M);
+        H2D(da, op->a_rows, M);
+        g.a_rows = reinterpret_cast<const int32_t*>(da);
+    }
+    float* dc = nullptr;
+    float *dq = nullptr, *dk = nullptr, *dv = nullptr;
+    if (!qkv) {
+        SCRATCH(dc_, op->c_rows * ldc);
+        dc = dc_;
+        H2D(dc, op->c, op->c_rows * ldc);
+        g.C = dc; g.ldc = ldc;
+        if (op->res_src) {
+            SCRATCH(drs, res_rows_n * ldc);
+            H2D(drs, op->res_src, res_rows_n * ldc);
+            g.res_src = drs;
+            if (op->res_rows) {
+                SCRATCH(drr, M);
+                H2D(drr, op->res_rows, M);
+                g.res_rows = reinterpret_cast<const int32_t*>(drr);
+            }
+        }
+    } else {
+        const int64_t tab = (int64_t)op->Smax * (op->HD / 2);
+        SCRATCH(dq_, op->q_rows * qdim);
+        SCRATCH(dk_, cache_n);
+        SCRATCH(dv_, cache_n);
+        SCRATCH(dcos, tab);
+        SCRATCH(dsin, tab);
+        dq = dq_; dk = dk_; dv = dv_;
+        H2D(dq, op->q_out, op->q_rows * qdim);
+        H2D(dk, op->cache_k, cache_n);
+        H2D(dv, op->cache_v, cache_n);
+        H2D(dcos, op->rope_cos, tab);
+        H2D(dsin, op->rope_sin, tab);
+        g.q_out = dq; g.cache_k = dk; g.cache_v = dv; g.rope_cos = dcos; g.rope_sin = dsin;
+        g.L = op->L; g.start_pos = op->start_pos; g.H = op->H; g.KVH = op->KVH; g.HD = op->HD; g.Smax = op->Smax;
+        g.q_scale = op->q_scale; g.col_base = op->col_base;
+    }
+    if (op->ws_floats > 0) {
+        SCRATCH(dws, op->ws_floats);
+        g.ws = dws; g.ws_cap = op->ws_floats;
+    }
+    g.force_skinny = op->force_skinny != 0;
+    g.force_tiled = op->force_tiled;
+    if (op->bf16) {
+        // finalize_bf16's round mode: Wb = bf16(w), W = float(Wb); the norm weight stays beside Wb
+        // and is folded into the fp32 copy, which then holds the same model for the fp32 routes
+        SCRATCH(dwb, ((int64_t)N * K + 1) / 2);
+        SCRATCH(dcnt, 4);
+        HIP_TRY(hipMemsetAsync(dcnt, 0, 16, c->stream));
+        HIP_TRY(launch_to_bf16(dw, reinterpret_cast<unsigned short*>(dwb), (int64_t)N * K, 0, true,
+                               reinterpret_cast<unsigned long long*>(dcnt), c->stream));
+        g.Wb = reinterpret_cast<const unsigned short*>(dwb);
+        if (op->norm_w) {
+            SCRATCH(dnw, K);
+            H2D(dnw, op->norm_w, K);
+            g.norm_w = dnw;
+            if (g.norm) HIP_TRY(launch_fold_cols(dw, N, K, dnw, c->stream));
+        }
+        g.wb_rows = op->wb_rows; g.wb_min_bytes = op->wb_min_bytes;
+    }
+    if (op->x6) {
+        SCRATCH(dw3, ((int64_t)N * 3 * K + 1) / 2);
+        HIP_TRY(launch_split_planes(dw, reinterpret_cast<unsigned short*>(dw3), N, K, c->stream));
+        g.W3 = reinterpret_cast<const unsigned short*>(dw3);
+    }
+    if (g.Wb) {
+        if (gemm_takes_bf16_rows(epi, g)) c->wb_rows_launches += 1;
+        else if (gemm_takes_bf16(epi, g)) c->wb_launches += 1;
+    }
+    gemm_route_reset();
+    if (const hipError_t e = launch_gemm(epi, g, c->stream); e != hipSuccess) {
+        (void)hipStreamSynchronize(c->stream);
+        if (e == hipErrorInvalidValue)
+            return fail("%s: launch_gemm refused epi %d, %d x %d x %d (no other kernel stands in)", who, epi, M, K, N);
+        return fail("%s: launch_gemm failed: %s", who, hipGetErrorString(e));
+    }
+    const GemmRoute rt = gemm_last_route();
+    if (!qkv) {
+        D2H(op->c, dc, op->c_rows * ldc);
+    } else {
+        D2H(op->q_out, dq, op->q_rows * qdim);
+        D2H(op->cache_k, dk, cache_n);
+        D2H(op->cache_v, dv, cache_n);
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    op->route[0] = rt.family;
+    for (int i = 0; i < 5; ++i) op->route[1 + i] = rt.v[i];
+    op->route[6] = (int32_t)rt.launches;
     return 0;
 }
 

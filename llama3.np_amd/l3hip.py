@@ -109,6 +109,7 @@ _SIGNATURES = {
     "l3_op_linear_bf16_rows_host": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _P, _P, _F, _P]),
     "l3_op_to_bf16_host": (ctypes.c_int, [_P, _P, _I64, _P, _P]),
     "l3_op_linear_bf16_host": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _P, _P, _F, _P]),
+    "l3_op_gemm_host": (ctypes.c_int, [_P, _P]),
     "l3_set_last_layer_rows": (ctypes.c_int, [_P, _I32]),
     "l3_kernel_timing": (ctypes.c_int, [_P, _I32]),
     "l3_kernel_stats": (ctypes.c_int, [_P, _P, _P]),
@@ -138,6 +139,55 @@ _SIGNATURES = {
 }
 
 BUSID_LEN = 16  # L3_BUSID_LEN
+
+
+class GemmOp(ctypes.Structure):
+    """l3_gemm_op (include/llama3hip.h)."""
+    _fields_ = [
+        ("struct_size", _I32), ("epi", _I32), ("M", _I32), ("N", _I32), ("K", _I32), ("norm", _I32),
+        ("eps", _F), ("q_scale", _F),
+        ("x", _P), ("w", _P), ("norm_w", _P), ("a_rows", _P), ("x_rows", _I64),
+        ("c", _P), ("c_rows", _I64), ("res_src", _P), ("res_rows", _P), ("res_src_rows", _I64),
+        ("L", _I32), ("start_pos", _I32), ("H", _I32), ("KVH", _I32), ("HD", _I32), ("Smax", _I32),
+        ("col_base", _I32), ("cache_B", _I32),
+        ("rope_cos", _P), ("rope_sin", _P), ("q_out", _P), ("q_rows", _I64), ("cache_k", _P), ("cache_v", _P),
+        ("ws_floats", _I64), ("wb_min_bytes", _I64),
+        ("force_skinny", _I32), ("force_tiled", _I32), ("x6", _I32), ("bf16", _I32), ("wb_rows", _I32),
+        ("route", _I32 * 8),
+    ]
+
+
+EPI_STORE, EPI_RESID, EPI_SWIGLU, EPI_QKV = range(4)
+GEMM_FAMILIES = ["none", "gemv", "gemv_bf16", "skinny", "splitk", "tiled", "x6", "rows_bf16"]
+_ROUTE_FIELDS = {
+    "gemv": ("rows_per_block", "lanes_per_unit", "nt", "row_blocks"),
+    "gemv_bf16": ("rows_per_block", "lanes_per_unit", "nt", "row_blocks"),
+    "skinny": ("tn", "ch"),
+    "splitk": ("bm", "bn", "bk", "s"),
+    "tiled": ("bm", "bn", "bk", "stages", "group_m"),
+    "x6": ("bm", "bn", "bk", "waves", "group_m"),
+    "rows_bf16": ("mt", "waves", "nt", "tn"),
+    "none": (),
+}
+
+
+def gemm_sentinel(shape, salt: int = 0) -> np.ndarray:
+    """A NaN-free float32 fill whose every element differs from its neighbours: what op_gemm puts in
+    the guard space (and a test in whatever else a launch must not touch), compared bit for bit."""
+    n = int(np.prod(shape))
+    i = np.arange(n, dtype=np.uint64) + np.uint64(salt) * np.uint64(1000003)
+    bits = np.uint32(0x40800000) + ((i * np.uint64(2654435761)) & np.uint64(0x3FFFFF)).astype(np.uint32)
+    return bits.view(np.float32).reshape(shape)
+
+
+def interleave_gate_up(wg: np.ndarray, wu: np.ndarray) -> np.ndarray:
+    """Separate gate and up [hidden, K] -> the kernels' fused [2 hidden, K] layout (16 gate rows,
+    then the 16 up rows of the same hidden units), as l3_op_ffn_host builds it."""
+    hidden, K = wg.shape
+    if wu.shape != wg.shape or hidden % 16:
+        raise ValueError(f"gate {wg.shape} and up {wu.shape} must be equal with hidden % 16 == 0")
+    return np.ascontiguousarray(np.stack([wg.reshape(hidden // 16, 16, K), wu.reshape(hidden // 16, 16, K)],
+                                         axis=1).reshape(2 * hidden, K))
 
 _lib: Optional[ctypes.CDLL] = None
 
@@ -909,6 +959,106 @@ class Context:
         check(lib().l3_op_linear_logprob_host(self._h, ptr(x), x.size // K, K, N, ptr(w), ptr(t), ptr(lp),
                                               ptr(lse), ptr(am)))
         return lp, lse, am
+
+    def op_gemm(self, epi: int, x: np.ndarray, w=None, *, gate_up=None, c=None, norm: bool = False,
+                eps: float = 0.0, norm_w=None, a_rows=None, res_src=None, res_rows=None, qkv: Optional[dict] = None,
+                ws_floats: int = 0, force_skinny: bool = False, force_tiled: int = 0, x6: bool = False,
+                bf16: bool = False, wb_rows: int = 0, wb_min_bytes: int = 0) -> dict:
+        """One GEMM launch with epilogue ``epi`` through the library's dispatcher (l3_op_gemm_host).
+
+        ``x`` [M, K] (or the table ``a_rows`` [M] gathers from), ``w`` [N, K]; EPI_SWIGLU takes
+        ``gate_up=(wg, wu)`` instead and builds the fused layout.  ``c`` [M, N]: EPI_RESID's
+        residual / the initial contents of the output (default: the sentinel).  EPI_QKV takes
+        ``qkv`` = dict(L, start_pos, H, KVH, HD, Smax, q_scale, rope_cos, rope_sin, cache_k, cache_v
+        [B, KVH, Smax, HD], and optionally col_base, q_out [M, H * HD]).
+
+        Returns a dict: ``route`` (family and the instantiation's parameters), and the outputs WITH
+        their guard space — ``c`` [M + 1, ldc], or ``q_out`` [M + 1, H * HD] and ``cache_k`` /
+        ``cache_v`` [B + 1, KVH, Smax, HD]; the guard was filled with ``gemm_sentinel(shape, 7)``
+        (c, q_out) and ``gemm_sentinel(shape, 8 / 9)`` (cache_k / cache_v).  A launch the
+        dispatcher refuses raises."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if epi == EPI_SWIGLU and gate_up is not None:
+            w = interleave_gate_up(np.asarray(gate_up[0], np.float32), np.asarray(gate_up[1], np.float32))
+        w = np.ascontiguousarray(w, dtype=np.float32)
+        if x.ndim != 2 or w.ndim != 2 or w.shape[1] != x.shape[1]:
+            raise ValueError(f"x {x.shape} and w {w.shape} must be [rows, K] and [N, K]")
+        keep = [x, w]
+        op = GemmOp()
+        op.struct_size = ctypes.sizeof(GemmOp)
+        op.epi = epi
+        N, K = w.shape
+        M = x.shape[0]
+        if a_rows is not None:
+            ar = np.ascontiguousarray(a_rows, dtype=np.int32)
+            keep.append(ar)
+            M = ar.shape[0]
+            op.a_rows = ptr(ar)
+        op.M, op.N, op.K = M, N, K
+        op.x, op.w, op.x_rows = ptr(x), ptr(w), x.shape[0]
+        op.norm, op.eps = int(bool(norm)), float(eps)
+        if norm_w is not None:
+            g = np.ascontiguousarray(norm_w, dtype=np.float32)
+            if g.shape != (K,):
+                raise ValueError(f"norm_w {g.shape} must be [K = {K}]")
+            keep.append(g)
+            op.norm_w = ptr(g)
+        out = {}
+        if epi != EPI_QKV:
+            ldc = N // 2 if epi == EPI_SWIGLU else N
+            cbuf = np.empty((M + 1, ldc), np.float32)
+            cbuf[:M] = gemm_sentinel((M, ldc), 6) if c is None else np.asarray(c, np.float32).reshape(M, ldc)
+            cbuf[M:] = gemm_sentinel((1, ldc), 7)
+            out["c"] = cbuf
+            op.c, op.c_rows = ptr(cbuf), M + 1
+            if res_src is not None:
+                rs = np.ascontiguousarray(res_src, dtype=np.float32)
+                if rs.ndim != 2 or rs.shape[1] != ldc:
+                    raise ValueError(f"res_src {rs.shape} must be [rows, {ldc}]")
+                keep.append(rs)
+                op.res_src, op.res_src_rows = ptr(rs), rs.shape[0]
+            if res_rows is not None:
+                rr = np.ascontiguousarray(res_rows, dtype=np.int32)
+                if rr.shape != (M,):
+                    raise ValueError(f"res_rows {rr.shape} must be [M = {M}]")
+                keep.append(rr)
+                op.res_rows = ptr(rr)
+        else:
+            q = dict(qkv)
+            L, H, KVH, HD, Smax = (int(q[k]) for k in ("L", "H", "KVH", "HD", "Smax"))
+            if L < 1 or M % L:
+                raise ValueError(f"M = {M} rows are not whole sequences of L = {L}")
+            B = M // L
+            cos = np.ascontiguousarray(q["rope_cos"], dtype=np.float32)
+            sin = np.ascontiguousarray(q["rope_sin"], dtype=np.float32)
+            if cos.shape != (Smax, HD // 2) or sin.shape != cos.shape:
+                raise ValueError(f"rope tables {cos.shape} / {sin.shape} must be [Smax, HD / 2]")
+            keep += [cos, sin]
+            qbuf = np.empty((M + 1, H * HD), np.float32)
+            qbuf[:M] = gemm_sentinel((M, H * HD), 5) if q.get("q_out") is None else np.asarray(q["q_out"], np.float32)
+            qbuf[M:] = gemm_sentinel((1, H * HD), 7)
+            caches = []
+            for name, salt in (("cache_k", 8), ("cache_v", 9)):
+                buf = np.empty((B + 1, KVH, Smax, HD), np.float32)
+                buf[:B] = np.asarray(q[name], np.float32).reshape(B, KVH, Smax, HD)
+                buf[B:] = gemm_sentinel((1, KVH, Smax, HD), salt)
+                caches.append(buf)
+            out.update(q_out=qbuf, cache_k=caches[0], cache_v=caches[1])
+            op.L, op.start_pos, op.H, op.KVH, op.HD, op.Smax = L, int(q["start_pos"]), H, KVH, HD, Smax
+            op.col_base, op.cache_B, op.q_scale = int(q.get("col_base", 0)), B + 1, float(q["q_scale"])
+            op.rope_cos, op.rope_sin = ptr(cos), ptr(sin)
+            op.q_out, op.q_rows, op.cache_k, op.cache_v = ptr(qbuf), M + 1, ptr(caches[0]), ptr(caches[1])
+        op.ws_floats, op.wb_min_bytes = int(ws_floats), int(wb_min_bytes)
+        op.force_skinny, op.force_tiled, op.x6 = int(bool(force_skinny)), int(force_tiled), int(bool(x6))
+        op.bf16, op.wb_rows = int(bool(bf16)), int(wb_rows)
+        check(lib().l3_op_gemm_host(self._h, ctypes.byref(op)))
+        del keep
+        fam = GEMM_FAMILIES[op.route[0]]
+        route = {"family": fam, "launches": int(op.route[6])}
+        for i, name in enumerate(_ROUTE_FIELDS[fam]):
+            route[name] = int(op.route[1 + i])
+        out["route"] = route
+        return out
 
     def op_ffn(self, x: np.ndarray, wg: np.ndarray, wu: np.ndarray, wd: np.ndarray) -> np.ndarray:
         x = np.ascontiguousarray(x, dtype=np.float32)

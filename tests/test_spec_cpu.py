@@ -102,7 +102,7 @@ def test_header_declares_the_entry_points():
         "l3_ctx* ctx", "const int32_t* seq", "const int32_t* seq_lens", "const int32_t* k", "int32_t B",
         "int32_t Smax", "int32_t draft_len", "int32_t ngram_max", "int32_t ngram_min", "int32_t* out",
         "int32_t* out_n"]
-    assert l3hip.version() == "0.18"
+    assert l3hip.version() == "0.19"
 
 
 def test_binding_argument_types_match_the_header():
