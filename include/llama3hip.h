@@ -189,6 +189,42 @@ int l3_set_weight_bf16_rows(l3_ctx* ctx, int32_t max_rows, int64_t min_bytes);
  * counting the GEMV-form launches only); any pointer may be NULL.  No reference counterpart
  * (llama3.py:265-283 keeps one copy of each weight and has one product, :166-168). */
 int l3_weight_bf16_rows_info(l3_ctx* ctx, int32_t* max_rows, int64_t* min_bytes, int64_t* launches);
+/* fp8 e4m3 weight storage for the 1 .. 64-row decode kernels (extension; default off, env
+ * L3_WEIGHT_FP8=1|2 sets the mode for new single-device contexts, an error at l3_create if
+ * L3_WEIGHT_BF16 is set too; DESIGN.md "fp8 weight storage").  The reference holds every projection
+ * as the fp32 array np.load gives (llama3.py:219-237, 280-281) and multiplies x @ W.T in that
+ * precision (:166-168, :211, :99-102, :304-307); with mode != 0 the context computes, still in
+ * fp32, the model whose q / k / v / o / gate / up / down projections and lm_head are
+ *   W_q[n, k] = s_n * float(code[n, k]),  code[n, k] = e4m3fn(W[n, k] / s_n),
+ * per row n of each [out, in] matrix: s_n = 2^e_n the smallest power of two with
+ * max_k |W[n, k]| / s_n <= 448, e_n in [-126, 127], s_n = 1 for an all-zero row; OCP e4m3fn (no
+ * fnuz), round-to-nearest-even, subnormals (down to 2^-9) rounded like any value, -0 kept, nothing
+ * saturates, the NaN codes 0x7f / 0xff never produced.  W_q is one exact fp32 value.  A non-finite
+ * element makes l3_finalize fail naming the tensor, in both modes.  The embedding, the RMSNorm
+ * weights, activations, accumulation, KV cache, RoPE, softmax and logits stay fp32.  l3_finalize
+ * makes the copy (codes in the fp32 tensor's row layout, unfolded, and one fp32 scale per row:
+ * 1 byte per element beside the 4 of the fp32 tensor), and the launches that l3_set_weight_bf16
+ * would serve from a bf16 copy — the weight-streaming GEMV, and the 2 .. 64-row kernel under the
+ * setting of l3_set_weight_bf16_rows, which governs whichever compact copy the context has, its
+ * threshold still N * K * 2 >= min_bytes — stream the codes instead, decoded in registers, with the
+ * norm weight applied to the activations; every other kernel keeps reading the fp32 tensors:
+ *   mode 1 (exact): every element must already equal W_q of itself; otherwise l3_finalize fails,
+ *     naming the first offending tensor (layer, kind, .npz key) and its count of inexact elements,
+ *     frees the copies, and the context stays un-finalized: the mode may be changed before
+ *     finalizing again.
+ *   mode 2 (round): the fp32 tensors are replaced by W_q before the norm fold, so every kernel
+ *     computes one model (which is not the uploaded one).
+ *   mode 0: everything as without this call.
+ * Errors: a mode outside [0, 2]; a call after l3_finalize; mode != 0 while l3_set_weight_bf16 is
+ * non-zero (and the reverse: one compact copy per context); mode != 0 on a member of a
+ * multi-device l3_group. */
+int l3_set_weight_fp8(l3_ctx* ctx, int32_t mode);
+/* The mode in force, the bytes of the code and scale copies (0 before l3_finalize and in mode 0)
+ * and the launches issued on them since l3_create, by kernel: the GEMV's fp8 form and the rows
+ * kernel's (a captured decode step counts when it is captured, not per replay); any pointer may be
+ * NULL.  No reference counterpart (llama3.py:265-283 keeps one copy of each weight). */
+int l3_weight_fp8_info(l3_ctx* ctx, int32_t* mode, int64_t* bytes, int64_t* gemv_launches,
+                       int64_t* rows_launches);
 /* Layer 0's QKV of a prefill as a table lookup (extension; default on, env L3_EMBED_QKV=0 turns
  * it off for new contexts).  Layer 0's QKV rows before RoPE depend on the token id and the weights
  * only, and the weights are fixed after l3_finalize, so a table [vocab_size, (H + 2 KVH) * HD] fp32
@@ -497,6 +533,31 @@ int l3_op_linear_bf16_host(l3_ctx* ctx, const float* x, int64_t rows, int32_t K,
  * context. */
 int l3_op_linear_bf16_rows_host(l3_ctx* ctx, const float* x, int64_t rows, int32_t K, int32_t N,
                                 const uint16_t* w_u16, const float* norm_w, float eps, float* y);
+/* The conversion of l3_set_weight_fp8 on a plain array x [rows, K] (K % 4 == 0): per row the
+ * power-of-two scale and the e4m3fn codes defined there, *n_inexact (may be NULL) = the elements
+ * that differ from scale * float(code).  A non-finite element is an error.  The storage format of
+ * the reference's `W` (llama3.py:219-237), not an op of it. */
+int l3_op_to_fp8_rows_host(l3_ctx* ctx, const float* x, int64_t rows, int32_t K, uint8_t* codes_out,
+                           float* scale_out, int64_t* n_inexact);
+/* y [rows, N] = s * ((x * g) [rows, K] @ W_q [N, K]^T), W_q[n, k] = scale[n] * float(codes[n, k]),
+ * on the GEMV's fp8 form (the reference's `x @ W.T`, llama3.py:166-168, with W stored as fp8):
+ * norm_w = g [K] applies the RMSNorm of llama3.py:111-114 with eps (s = 1 / sqrt(mean(x^2) + eps)
+ * per row, of x itself); NULL: g = 1, s = 1.  rows in [1, 8], K % 32 == 0, N % 4 == 0; rows whose
+ * K does not fit one launch's 64 KB of staged rows run as several launches (K <= 16256: the
+ * one-row form stages its row too).  Any other shape is an error: no other kernel stands in.  A code 0x7f / 0xff or a scale that is not a
+ * power of two is refused on the host.  route (out, may be NULL): the last launch's report,
+ * [0] family (8 gemv_fp8), [1..5] as l3_op_gemm_host's. */
+int l3_op_linear_fp8_host(l3_ctx* ctx, const float* x, int64_t rows, int32_t K, int32_t N, const uint8_t* codes,
+                          const float* scale, const float* norm_w, float eps, float* y, int32_t* route);
+/* The same product (the reference's `x @ W.T`, llama3.py:166-168, with W stored as fp8 and the
+ * RMSNorm of llama3.py:111-114 when norm_w is given) on the fp8 form of the weight-streaming MFMA
+ * kernel of l3_set_weight_bf16_rows, whatever that setting says: rows in [2, 64], K % 32 == 0,
+ * N % 4 == 0, one launch.  Any other shape is an error: no other kernel stands in; operands are
+ * checked as above.  route: [0] family (9 rows_fp8), then row tiles, waves, non-temporal, TN.
+ * Works on an op-only context. */
+int l3_op_linear_fp8_rows_host(l3_ctx* ctx, const float* x, int64_t rows, int32_t K, int32_t N,
+                               const uint8_t* codes, const float* scale, const float* norm_w, float eps,
+                               float* y, int32_t* route);
 /* One GEMM launch with any fused epilogue, on plain host arrays (tests/test_gpu_gemm_routes.py):
  * the dense contractions of llama3.py:166-168 / :211 / :99-102 / :304-307 with what the kernels
  * fuse into them, through exactly one call of the library's GEMM dispatcher, and a report of the
@@ -518,7 +579,7 @@ int l3_op_linear_bf16_rows_host(l3_ctx* ctx, const float* x, int64_t rows, int32
  * force_tiled (passed through unchanged), x6 (the three-piece bf16 planes are built from w),
  * wb_rows / wb_min_bytes (the l3_set_weight_bf16_rows setting of this launch).
  * route (out): [0] family (0 none, 1 gemv, 2 gemv_bf16, 3 skinny, 4 splitk, 5 tiled, 6 x6,
- * 7 rows_bf16), [1..5] by family — gemv: rows per block, lanes per unit, non-temporal, row blocks;
+ * 7 rows_bf16; 8 gemv_fp8 and 9 rows_fp8 come from the fp8 entries above only), [1..5] by family — gemv: rows per block, lanes per unit, non-temporal, row blocks;
  * skinny: column tiles, k-blocks per round trip; splitk: slice tile BM, BN, BK, slices; tiled:
  * BM, BN, BK, LDS stages, group_m; x6: BM, BN, BK, waves, group_m; rows_bf16: row tiles, waves,
  * non-temporal, column tiles — [6] launch sites passed.  struct_size = sizeof(l3_gemm_op). */

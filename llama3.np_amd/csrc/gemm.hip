@@ -102,15 +102,20 @@ static hipError_t launch_split(int epi, const GemmArgs& a, hipStream_t s) {
     }
 }
 
-template <int EPI, int MR, int LPU, bool PARTS = false, bool NT = false, bool FOLD = false>
+// F8_ONLY: a form that only fp8 launches reach (no fp32 / bf16 instantiation)
+template <int EPI, int MR, int LPU, bool PARTS = false, bool NT = false, bool FOLD = false, bool F8_ONLY = false>
 static hipError_t launch_gemv_lpu(const GemmArgs& a, hipStream_t s) {
     const int units = (EPI == EPI_SWIGLU || EPI == EPI_QKV) ? a.N / 2 : a.N;
     const int per_block = 4 * (64 / LPU);
     const dim3 grid((unsigned)((units + per_block - 1) / per_block), (unsigned)((a.M + MR - 1) / MR)),
         block(256);
-    note_route(a.Wb ? ROUTE_GEMV_BF16 : ROUTE_GEMV, MR, LPU, NT ? 1 : 0, (int)grid.y);
-    // GemmArgs::Wb (bf16 weight storage): the same grid on the bf16-weight form
-    if (a.Wb)
+    note_route(a.Wq ? ROUTE_GEMV_FP8 : a.Wb ? ROUTE_GEMV_BF16 : ROUTE_GEMV, MR, LPU, NT ? 1 : 0, (int)grid.y);
+    // GemmArgs::Wq / Wb (fp8 / bf16 weight storage): the same grid on the compact-weight forms
+    if (a.Wq)  // (every fp8 form stages its rows in LDS, the one-row form too)
+        hipLaunchKernelGGL((gemv_kernel<EPI, MR, LPU, PARTS, NT, FOLD, true, true>), grid, block, (size_t)MR * a.K * 4, s, a);
+    else if constexpr (F8_ONLY)
+        return hipErrorInvalidValue;
+    else if (a.Wb)
         hipLaunchKernelGGL((gemv_kernel<EPI, MR, LPU, PARTS, NT, FOLD, true>), grid, block, MR == 1 ? 0 : (size_t)MR * a.K * 4, s, a);
     else
         hipLaunchKernelGGL((gemv_kernel<EPI, MR, LPU, PARTS, NT, FOLD>), grid, block, MR == 1 ? 0 : (size_t)MR * a.K * 4, s, a);
@@ -118,15 +123,19 @@ static hipError_t launch_gemv_lpu(const GemmArgs& a, hipStream_t s) {
 }
 
 // non-temporal W loads for the one-row GEMV over a weight larger than the caches would keep
-// (>= 64 MB — of the copy that is streamed: fp32, or bf16 with GemmArgs::Wb; the Llama-3-shape
-// decode; gemv_kernel NT); L3_GEMV_NT=0 turns them off (A/B)
+// (>= 64 MB — of the copy that is streamed: fp32, bf16 with GemmArgs::Wb, or fp8 codes with
+// GemmArgs::Wq; the Llama-3-shape decode; gemv_kernel NT); L3_GEMV_NT=0 turns them off (A/B), and
+// L3_FP8_NT_MB moves the fp8 threshold (the A/B of DESIGN.md "fp8 weight storage")
 static bool gemv_nt(const GemmArgs& a) {
     static const int on = env_knob("L3_GEMV_NT", 1);
+    static const int f8_mb = env_knob("L3_FP8_NT_MB", 64);
+    if (a.Wq) return on && (int64_t)a.N * a.K >= ((int64_t)f8_mb << 20);
     return on && (int64_t)a.N * a.K * (a.Wb ? 2 : 4) >= ((int64_t)64 << 20);
 }
 
-// 16-byte pieces of a W row: float4, or eight bf16 with GemmArgs::Wb
-static int gemv_pieces(const GemmArgs& a) { return a.Wb ? a.K / 8 : a.K / 4; }
+// 16-byte pieces of a W row: float4, eight bf16 with GemmArgs::Wb, sixteen fp8 codes with
+// GemmArgs::Wq
+static int gemv_pieces(const GemmArgs& a) { return a.Wb ? a.K / 8 : a.Wq ? a.K / 16 : a.K / 4; }
 
 // the O-proj partial rows of the fused decode attention (GemmArgs::parts): EPI_SWIGLU carries
 // GEMV_MAXP partial loads per piece, so its lanes take fewer pieces (<= 4 up to K = 1024)
@@ -158,6 +167,8 @@ template <int EPI, int MR>
 static hipError_t launch_gemv_mr(const GemmArgs& a, hipStream_t s) {
     if constexpr (MR == 1) {
         if (gemv_lpu(a) == 64 && gemv_nt(a)) return launch_gemv_lpu<EPI, 1, 64, false, true>(a, s);
+        // fp8: K = 4096 is 256 sixteen-code pieces, 32 lanes per unit
+        if (a.Wq && gemv_lpu(a) == 32 && gemv_nt(a)) return launch_gemv_lpu<EPI, 1, 32, false, true, false, true>(a, s);
     }
     switch (gemv_lpu(a)) {
         case 16: return launch_gemv_lpu<EPI, MR, 16>(a, s);
@@ -256,13 +267,20 @@ int gemm_store_config(const GemmArgs& a) {
 // the folded-argmax QKV and the plain GEMV range (the dispatch order of launch_gemm below) — unless
 // gemm_rows_bf16_kernel takes it first (gemm_takes_bf16_rows); every other kernel reads the fp32 W,
 // which holds the same model (runtime.hip finalize_bf16)
-bool gemm_takes_bf16(int epi, const GemmArgs& a) {
-    if (!a.Wb || a.M <= 0 || a.N <= 0) return false;
-    if (gemm_takes_bf16_rows(epi, a)) return false;  // gemm_rows_bf16_kernel, not the GEMV
+static bool takes_compact_rows(int epi, const GemmArgs& a);
+static bool takes_compact(int epi, const GemmArgs& a) {
+    if (a.M <= 0 || a.N <= 0) return false;
+    if (takes_compact_rows(epi, a)) return false;  // gemm_rows_bf16_kernel, not the GEMV
     if (a.parts) return epi == EPI_SWIGLU || epi == EPI_RESID;
     if (a.amax_in) return true;
     if (a.force_skinny || a.force_tiled) return false;
     return gemm_is_gemv(a) && !use_skinny(a);
+}
+bool gemm_takes_bf16(int epi, const GemmArgs& a) { return a.Wb && takes_compact(epi, a); }
+// GemmArgs::Wq: the same launches on the fp8 form (Wb wins if a caller ever set both)
+// (its one-row form stages the row in LDS too, beside a few words of its own: K <= 16256)
+bool gemm_takes_fp8(int epi, const GemmArgs& a) {
+    return a.Wq && !a.Wb && a.K <= 16256 && takes_compact(epi, a);
 }
 
 // 2 .. wb_rows rows on the bf16 copy (gemm_rows_bf16_kernel, gemm_kernel.h): the weight streams
@@ -274,8 +292,8 @@ bool gemm_takes_bf16(int epi, const GemmArgs& a) {
 // reaches x6 only after the skinny, GEMV and split-K choices), so with x6 and bf16 storage both
 // on, 33 - 64-row split-K launches keep the fp32 kernels.  force_skinny (speculative chunks) and
 // split-K launches are taken
-bool gemm_takes_bf16_rows(int epi, const GemmArgs& a) {
-    if (!a.Wb || a.wb_rows < 2 || a.M < 2 || a.M > a.wb_rows || a.M > WB_ROWS_MAX || a.N <= 0) return false;
+static bool takes_compact_rows(int epi, const GemmArgs& a) {
+    if (a.wb_rows < 2 || a.M < 2 || a.M > a.wb_rows || a.M > WB_ROWS_MAX || a.N <= 0) return false;
     if ((int64_t)a.N * a.K * 2 < a.wb_min_bytes) return false;
     if (a.parts || a.amax_in || a.amax_part || a.amax_rows || a.lse_rows || a.kv_bak || a.force_tiled ||
         a.split_rows)
@@ -283,6 +301,10 @@ bool gemm_takes_bf16_rows(int epi, const GemmArgs& a) {
     if (a.W3 && a.M > 32 && epi != EPI_STORE) return false;
     return epi == EPI_STORE || epi == EPI_RESID || epi == EPI_SWIGLU || epi == EPI_QKV;
 }
+bool gemm_takes_bf16_rows(int epi, const GemmArgs& a) { return a.Wb && takes_compact_rows(epi, a); }
+// GemmArgs::Wq: the same launches (the threshold stays N * K * 2, so they do not move with the
+// storage) on the fp8 form of the kernel
+bool gemm_takes_fp8_rows(int epi, const GemmArgs& a) { return a.Wq && !a.Wb && takes_compact_rows(epi, a); }
 
 // k-blocks in flight per round trip of gemm_rows_bf16_kernel for one / two / four row tiles:
 // 4 / 1 / 1 measured best against 4 / 2 / 2, 8 / 4 / 2 and 2 / 1 / 1 (DESIGN.md decisions table)
@@ -292,7 +314,7 @@ constexpr int WB_ROWS_CH1 = 4, WB_ROWS_CH2 = 1, WB_ROWS_CH4 = 1;
 // Llama-3-shape step against four waves everywhere)
 constexpr unsigned WB_ROWS_WIDE_BLOCKS = 512;
 
-template <int EPI, int TN, int MT, int CH>
+template <int EPI, int TN, int MT, int CH, bool F8>
 static hipError_t launch_rows_bf16_mt(const GemmArgs& a, hipStream_t s) {
     const unsigned blocks = (unsigned)((a.N + 16 * TN - 1) / (16 * TN));
     const bool nt = gemv_nt(a);
@@ -301,36 +323,42 @@ static hipError_t launch_rows_bf16_mt(const GemmArgs& a, hipStream_t s) {
     constexpr bool WIDE_OK = MT * TN < 8;
     if constexpr (WIDE_OK) {
         if (blocks <= WB_ROWS_WIDE_BLOCKS) {
-            note_route(ROUTE_ROWS_BF16, MT, 8, nt ? 1 : 0, TN);
-            if (nt) hipLaunchKernelGGL((gemm_rows_bf16_kernel<EPI, TN, MT, CH, true, 8>), dim3(blocks), dim3(512), 0, s, a);
-            else hipLaunchKernelGGL((gemm_rows_bf16_kernel<EPI, TN, MT, CH, false, 8>), dim3(blocks), dim3(512), 0, s, a);
+            note_route(F8 ? ROUTE_ROWS_FP8 : ROUTE_ROWS_BF16, MT, 8, nt ? 1 : 0, TN);
+            if (nt) hipLaunchKernelGGL((gemm_rows_bf16_kernel<EPI, TN, MT, CH, true, 8, F8>), dim3(blocks), dim3(512), 0, s, a);
+            else hipLaunchKernelGGL((gemm_rows_bf16_kernel<EPI, TN, MT, CH, false, 8, F8>), dim3(blocks), dim3(512), 0, s, a);
             return hipGetLastError();
         }
     }
-    note_route(ROUTE_ROWS_BF16, MT, 4, nt ? 1 : 0, TN);
-    if (nt) hipLaunchKernelGGL((gemm_rows_bf16_kernel<EPI, TN, MT, CH, true, 4>), dim3(blocks), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((gemm_rows_bf16_kernel<EPI, TN, MT, CH, false, 4>), dim3(blocks), dim3(256), 0, s, a);
+    note_route(F8 ? ROUTE_ROWS_FP8 : ROUTE_ROWS_BF16, MT, 4, nt ? 1 : 0, TN);
+    if (nt) hipLaunchKernelGGL((gemm_rows_bf16_kernel<EPI, TN, MT, CH, true, 4, F8>), dim3(blocks), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((gemm_rows_bf16_kernel<EPI, TN, MT, CH, false, 4, F8>), dim3(blocks), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
 // one, two or four 16-row tiles per block: every row of the launch in one block
 template <int EPI, int TN>
 static hipError_t launch_rows_bf16(const GemmArgs& a, hipStream_t s) {
-    if (a.M <= 16) return launch_rows_bf16_mt<EPI, TN, 1, WB_ROWS_CH1>(a, s);
-    if (a.M <= 32) return launch_rows_bf16_mt<EPI, TN, 2, WB_ROWS_CH2>(a, s);
-    return launch_rows_bf16_mt<EPI, TN, 4, WB_ROWS_CH4>(a, s);
+    if (a.Wq) {  // the fp8 form, same tiles and k-blocks in flight
+        if (a.M <= 16) return launch_rows_bf16_mt<EPI, TN, 1, WB_ROWS_CH1, true>(a, s);
+        if (a.M <= 32) return launch_rows_bf16_mt<EPI, TN, 2, WB_ROWS_CH2, true>(a, s);
+        return launch_rows_bf16_mt<EPI, TN, 4, WB_ROWS_CH4, true>(a, s);
+    }
+    if (a.M <= 16) return launch_rows_bf16_mt<EPI, TN, 1, WB_ROWS_CH1, false>(a, s);
+    if (a.M <= 32) return launch_rows_bf16_mt<EPI, TN, 2, WB_ROWS_CH2, false>(a, s);
+    return launch_rows_bf16_mt<EPI, TN, 4, WB_ROWS_CH4, false>(a, s);
 }
 
 hipError_t launch_gemm(int epi, const GemmArgs& a_in, hipStream_t s) {
     GemmArgs a_own;
-    const bool rows_bf16 = gemm_takes_bf16_rows(epi, a_in);
-    // neither a GEMV launch nor a rows launch: the fp32 kernels, as without Wb
-    const bool drop_wb = a_in.Wb && !rows_bf16 && !gemm_takes_bf16(epi, a_in);
-    if (drop_wb) {
+    const bool rows_bf16 = gemm_takes_bf16_rows(epi, a_in) || gemm_takes_fp8_rows(epi, a_in);
+    // neither a GEMV launch nor a rows launch: the fp32 kernels, as without Wb / Wq
+    const bool drop_wb = (a_in.Wb || a_in.Wq) && !rows_bf16 && !gemm_takes_bf16(epi, a_in) && !gemm_takes_fp8(epi, a_in);
+    if (drop_wb || (a_in.Wb && a_in.Wq)) {
         a_own = a_in;
-        a_own.Wb = nullptr;
+        if (drop_wb) a_own.Wb = nullptr;
+        if (drop_wb || a_in.Wb) a_own.Wq = nullptr;
     }
-    const GemmArgs& a = drop_wb ? a_own : a_in;
+    const GemmArgs& a = drop_wb || (a_in.Wb && a_in.Wq) ? a_own : a_in;
     if (a.M <= 0 || a.N <= 0) return hipSuccess;
     if (a.K % 32 != 0 || a.K <= 0) return hipErrorInvalidValue;  // whole 32-deep k-tiles
     if (epi == EPI_SWIGLU && a.N % 32 != 0) return hipErrorInvalidValue;

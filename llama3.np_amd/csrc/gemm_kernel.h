@@ -41,6 +41,7 @@ namespace l3 {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 // silu (llama3.py:27-28) with v_rcp_f32 (1 ulp) instead of the IEEE division sequence: the
 // SwiGLU epilogue's VALU share drops, gate|up 123.5 -> 126.4 TF/s (tools/gemm_tune A/B)
@@ -952,13 +953,38 @@ __global__ void __launch_bounds__(64 * NW) gemm_skinny_kernel(GemmArgs p) {
 // registers in the one-row form (g loaded beside x in the same round trip), while staging x into
 // LDS in the row-blocked forms, which therefore take the rows' sums of squares (of raw x) from the
 // staging pass.  Each piece takes two float4 of x (XN); everything else is the fp32 form's.
+//
+// F8 (with WB; opt-in fp8 weight storage, GemmArgs::Wq / wq_scale; DESIGN.md "fp8 weight storage"):
+// the W pieces are 16 bytes of e4m3fn codes, sixteen k each, eight per row and lane in flight.  A
+// 32-bit word of four codes is decoded by two v_cvt_scalef32_pk_f32_fp8 with the row's power-of-two
+// scale as the scale operand: the registers hold wq_scale[n] * float(code), the model, and the FMAs
+// run in fp32 in a fixed k order.  Every F8 form, the one-row one included, stages x * g in LDS
+// once per block (the row-blocked WB forms' staging pass, which also takes the sum of squares of
+// raw x): a lane that kept x and g for 128 k in registers beside the codes would hold half the
+// codes in flight, and at one byte per weight the per-lane x and g loads are eight bytes of L2
+// traffic per byte of W.  On the one-row form the staging pass reads the FOLD row once the id is
+// known, and with partial rows (EPI_SWIGLU) adds them in head order before the square and the
+// norm weight, block 0 storing the summed row to x_out.
 // unpack a 32-bit pair of bf16: element 2i in the low half, 2i + 1 in the high half
 __device__ __forceinline__ float bf16_lo(unsigned u) { return __uint_as_float(u << 16); }
 __device__ __forceinline__ float bf16_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
+// unpack a 32-bit word of four e4m3fn codes (element i in byte i) times the power-of-two scale sc
+__device__ __forceinline__ void fp8x4_scaled(unsigned u, float sc, float* out) {
+#if L3_FP8_UNSCALED_CVT  // (the fall-back: plain conversion, then an exact fp32 multiply)
+    const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8(u, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8(u, true);
+    out[0] = lo[0] * sc; out[1] = lo[1] * sc; out[2] = hi[0] * sc; out[3] = hi[1] * sc;
+#else
+    const auto lo = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(u, sc, false);
+    const auto hi = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(u, sc, true);
+    out[0] = lo[0]; out[1] = lo[1]; out[2] = hi[0]; out[3] = hi[1];
+#endif
+}
 
-template <int EPI, int MR, int LPU, bool PARTS = false, bool NT = false, bool FOLD = false, bool WB = false>
+template <int EPI, int MR, int LPU, bool PARTS = false, bool NT = false, bool FOLD = false, bool WB = false,
+          bool F8 = false>
 __global__ void __launch_bounds__(256) gemv_kernel(GemmArgs p) {
     extern __shared__ __attribute__((aligned(16))) float xs[];  // [MR][K]
+    static_assert(!F8 || WB, "the fp8 form is a compact-weight form");
     static_assert(!PARTS || MR == 1, "partial rows only on the one-row GEMV");
     static_assert(!FOLD || (MR == 1 && EPI == EPI_QKV && !PARTS), "the folded argmax feeds a one-row QKV");
     constexpr int ROWS = (EPI == EPI_SWIGLU || EPI == EPI_QKV) ? 2 : 1;
@@ -966,12 +992,12 @@ __global__ void __launch_bounds__(256) gemv_kernel(GemmArgs p) {
     constexpr bool XPARTS = PARTS && EPI == EPI_SWIGLU;
     // 16-byte pieces per W row per lane in flight (WB with partial rows on x: two float4 of each
     // partial row per piece, so half the pieces keep the fp32 form's registers)
-    constexpr int CH = PARTS ? (WB && XPARTS ? 2 : 4) : 8;
-    constexpr int XN = WB ? 2 : 1;     // float4 of x per W piece
+    constexpr int CH = F8 ? 8 : PARTS ? (WB && XPARTS ? 2 : 4) : 8;  // (F8: no x / partial-row registers)
+    constexpr int XN = F8 ? 4 : WB ? 2 : 1;  // float4 of x per W piece
     constexpr bool GN = WB && EPI != EPI_RESID;  // the norm weight may ride on x (p.norm_w)
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int K4 = p.K >> 2;
-    const int KP = WB ? p.K >> 3 : K4;  // pieces per W row
+    const int KP = F8 ? p.K >> 4 : WB ? p.K >> 3 : K4;  // pieces per W row
     const int j = lane % LPU;
     const int unit = (blockIdx.x * 4 + wid) * UPW + lane / LPU;
     const int nunits = ROWS == 2 ? p.N / 2 : p.N;
@@ -989,6 +1015,12 @@ __global__ void __launch_bounds__(256) gemv_kernel(GemmArgs p) {
     }
     const f32x4* W4 = reinterpret_cast<const f32x4*>(p.W);
     const u32x4* WB4 = reinterpret_cast<const u32x4*>(p.Wb);
+    const u32x4* WQ4 = reinterpret_cast<const u32x4*>(p.Wq);
+    float wsc[F8 ? ROWS : 1];  // F8: the rows' scales, in flight with the first pieces
+    if constexpr (F8) {
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r) wsc[r] = p.wq_scale[wrow[r]];
+    }
     const f32x4* G4 = reinterpret_cast<const f32x4*>(p.norm_w);
     const bool gn = GN && p.norm_w != nullptr;  // launch-uniform
     // row block: rows [m0, m0 + Mb) of A (grid.y row blocks of MR rows re-read W through L2)
@@ -996,13 +1028,14 @@ __global__ void __launch_bounds__(256) gemv_kernel(GemmArgs p) {
     // MR == 1 (batch-1 decode): each lane loads its own float4s of the input row next to its W
     // pieces — one memory round trip, no LDS staging pass and no block barrier; MR > 1 stages
     // the rows once in LDS (re-read by every unit of the block)
-    constexpr bool DIRECT = MR == 1;
+    constexpr bool DIRECT = MR == 1 && !F8;
     const f32x4* X4 = reinterpret_cast<const f32x4*>(FOLD ? p.A : a_row(p, m0));
     f32x4 w[WB ? 1 : ROWS][WB ? 1 : CH];
-    u32x4 wb[WB ? ROWS : 1][WB ? CH : 1];
+    u32x4 wb[WB && !F8 ? ROWS : 1][WB && !F8 ? CH : 1];
+    u32x4 wq[F8 ? ROWS : 1][F8 ? CH : 1];
     f32x4 xv[DIRECT ? CH * XN : 1];
     f32x4 gv[GN && DIRECT ? CH * XN : 1];
-    f32x4 xp[XPARTS ? CH * XN : 1][XPARTS ? GEMV_MAXP : 1];
+    f32x4 xp[XPARTS && DIRECT ? CH * XN : 1][XPARTS && DIRECT ? GEMV_MAXP : 1];
     const f32x4* P4 = reinterpret_cast<const f32x4*>(p.parts) + (int64_t)m0 * p.nparts * K4;
     // Row-blocked forms (MR > 1): W loads unpredicated from clamped addresses, x zeroed past K
     // where it is used (their predicated loads compiled to exec-masked branches that each waited
@@ -1016,7 +1049,10 @@ __global__ void __launch_bounds__(256) gemv_kernel(GemmArgs p) {
             if constexpr (WB) {
 #pragma unroll
                 for (int r = 0; r < ROWS; ++r) {
-                    if constexpr (DIRECT)
+                    if constexpr (F8)
+                        wq[r][t] = NT ? __builtin_nontemporal_load(&WQ4[(int64_t)wrow[r] * KP + kk])
+                                      : WQ4[(int64_t)wrow[r] * KP + kk];
+                    else if constexpr (DIRECT)
                         wb[r][t] = k4 >= KP ? u32x4{0u, 0u, 0u, 0u}
                                    : NT ? __builtin_nontemporal_load(&WB4[(int64_t)wrow[r] * KP + k4])
                                         : WB4[(int64_t)wrow[r] * KP + k4];
@@ -1063,7 +1099,7 @@ __global__ void __launch_bounds__(256) gemv_kernel(GemmArgs p) {
     };
     // x = A row + the heads' O-proj rows, summed in head order
     auto add_parts = [&]() {
-        if constexpr (XPARTS) {
+        if constexpr (XPARTS && DIRECT) {
 #pragma unroll
             for (int t = 0; t < CH * XN; ++t)
 #pragma unroll
@@ -1166,7 +1202,7 @@ __global__ void __launch_bounds__(256) gemv_kernel(GemmArgs p) {
             }
         X4 = reinterpret_cast<const f32x4*>(p.A + (int64_t)bi * p.lda);
 #pragma unroll
-        for (int t = 0; t < CH; ++t) {
+        for (int t = 0; t < (DIRECT ? CH : 0); ++t) {  // (staged forms read X4 in the staging pass)
             if constexpr (WB) {
                 xv[2 * t] = X4[2 * min(j + LPU * t, KP - 1)];
                 xv[2 * t + 1] = X4[2 * min(j + LPU * t, KP - 1) + 1];
@@ -1186,7 +1222,7 @@ __global__ void __launch_bounds__(256) gemv_kernel(GemmArgs p) {
     // thread before the first LDS store (a serial load -> store walk costs a round trip each)
     // (unpredicated loads from clamped addresses, zeroed after they land: predicated loads
     // compiled to exec-masked branches that waited for each load before issuing the next)
-    constexpr int SU = 8;
+    constexpr int SU = XPARTS ? 2 : 8;  // (partial rows: GEMV_MAXP more loads per staged float4)
     // WB: the staged rows carry the norm weight (x * g), so each row's sum of squares of raw x is
     // taken here: per thread, then per wave (group_sum), then the four waves' sums in wave order
     __shared__ float ss_w[WB && !DIRECT ? 4 : 1][MR];
@@ -1198,18 +1234,31 @@ __global__ void __launch_bounds__(256) gemv_kernel(GemmArgs p) {
         }
         for (int f0 = tid; f0 < MR * K4; f0 += 256 * SU) {
             f32x4 v[SU], g[GN ? SU : 1];
+            f32x4 pv[XPARTS ? SU : 1][XPARTS ? GEMV_MAXP : 1];
 #pragma unroll
             for (int u = 0; u < SU; ++u) {
                 const int f = f0 + 256 * u, m = f / K4, k4 = f - m * K4;
                 const bool ok = f < MR * K4 && m < Mb;
-                v[u] = reinterpret_cast<const f32x4*>(a_row(p, m0 + (ok ? m : 0)))[ok ? k4 : 0];
+                if constexpr (MR == 1) v[u] = X4[ok ? k4 : 0];  // (FOLD: the row of the id found above)
+                else v[u] = reinterpret_cast<const f32x4*>(a_row(p, m0 + (ok ? m : 0)))[ok ? k4 : 0];
                 if constexpr (GN) {
                     if (gn) g[u] = G4[ok ? k4 : 0];
+                }
+                if constexpr (XPARTS) {
+#pragma unroll
+                    for (int pp = 0; pp < GEMV_MAXP; ++pp)
+                        pv[u][pp] = (pp < p.nparts && ok) ? P4[(int64_t)pp * K4 + k4] : f32x4{0.f, 0.f, 0.f, 0.f};
                 }
             }
 #pragma unroll
             for (int u = 0; u < SU; ++u) {
                 const int f = f0 + 256 * u, m = f / K4;
+                if constexpr (XPARTS) {  // x = A row + the heads' O-proj rows, summed in head order
+#pragma unroll
+                    for (int pp = 0; pp < GEMV_MAXP; ++pp) v[u] += pv[u][pp];
+                    if (p.x_out && blockIdx.x == 0 && f < K4)
+                        reinterpret_cast<f32x4*>(p.x_out + (int64_t)m0 * p.K)[f] = v[u];
+                }
                 if constexpr (WB) {
                     const float sq = v[u].x * v[u].x + v[u].y * v[u].y + v[u].z * v[u].z + v[u].w * v[u].w;
 #pragma unroll
@@ -1242,7 +1291,7 @@ __global__ void __launch_bounds__(256) gemv_kernel(GemmArgs p) {
     for (int t0 = 0; t0 < nt; t0 += CH) {
         if (t0) load_chunk(t0);
         add_parts();
-        if constexpr (XPARTS) {  // block 0's first unit holds every k4 of the summed row
+        if constexpr (XPARTS && DIRECT) {  // block 0's first unit holds every k4 of the summed row
             if (p.x_out && blockIdx.x == 0 && tid < LPU) {
 #pragma unroll
                 for (int t = 0; t < CH; ++t) {
@@ -1265,6 +1314,34 @@ __global__ void __launch_bounds__(256) gemv_kernel(GemmArgs p) {
             // counts no norm; the row-blocked form holds clamped W and zeroes x
             const int k4 = j + LPU * (t0 + t), kk = min(k4, KP - 1);
             const float in = k4 < KP ? 1.f : 0.f;
+            if constexpr (F8) {
+                // the piece's sixteen weights, then fp32 FMAs in k order 0..15 for every row
+                float wf[ROWS][16];
+#pragma unroll
+                for (int r = 0; r < ROWS; ++r) {
+                    fp8x4_scaled(wq[r][t].x, wsc[r], &wf[r][0]);
+                    fp8x4_scaled(wq[r][t].y, wsc[r], &wf[r][4]);
+                    fp8x4_scaled(wq[r][t].z, wsc[r], &wf[r][8]);
+                    fp8x4_scaled(wq[r][t].w, wsc[r], &wf[r][12]);
+                }
+#pragma unroll
+                for (int m = 0; m < MR; ++m) {
+                    f32x4 xq[4];
+#pragma unroll
+                    for (int h = 0; h < 4; ++h)
+                        xq[h] = k4 < KP ? reinterpret_cast<const f32x4*>(xs + m * p.K)[4 * kk + h] : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int r = 0; r < ROWS; ++r) {
+                        float a = acc[r][m];
+#pragma unroll
+                        for (int h = 0; h < 4; ++h)
+                            a += wf[r][4 * h] * xq[h].x + wf[r][4 * h + 1] * xq[h].y + wf[r][4 * h + 2] * xq[h].z +
+                                 wf[r][4 * h + 3] * xq[h].w;
+                        acc[r][m] = a;
+                    }
+                }
+                continue;
+            }
             if constexpr (WB) {
                 // the piece's eight weights, then fp32 FMAs in k order 0..7 for every row
                 float wf[ROWS][8];
@@ -1408,7 +1485,12 @@ __global__ void __launch_bounds__(256) gemv_kernel(GemmArgs p) {
 // NT: the Wb pieces are loaded non-temporal (the gemv_nt rule: >= 64 MB of bf16 per launch).
 // Rows are clamped at M - 1 and W rows at N - 1 for the loads, stores are predicated: M need not
 // be a multiple of 16, nor N of 16 * TN.
-template <int EPI, int TN, int MT, int CH, bool NT = false, int NW = 4>
+//
+// F8 (opt-in fp8 weight storage, GemmArgs::Wq / wq_scale; DESIGN.md "fp8 weight storage"): the
+// lane's piece is the 8 bytes of e4m3fn codes at the same eight k of row n0 + 16j + frow, decoded
+// with that row's power-of-two scale (one register per j) as in the GEMV's F8 form; the k-block
+// stays 32 deep (K % 32 == 0 is the only K condition) and everything after the decode is shared.
+template <int EPI, int TN, int MT, int CH, bool NT = false, int NW = 4, bool F8 = false>
 __global__ void __launch_bounds__(64 * NW) gemm_rows_bf16_kernel(GemmArgs p) {
     static_assert(EPI != EPI_SWIGLU || TN % 2 == 0, "SwiGLU pairs gate / up tiles");
     static_assert(MT == 1 || MT == 2 || MT == 4, "up to 64 rows");
@@ -1422,10 +1504,19 @@ __global__ void __launch_bounds__(64 * NW) gemm_rows_bf16_kernel(GemmArgs p) {
     const float* arow[MT];
 #pragma unroll
     for (int i = 0; i < MT; ++i) arow[i] = a_row(p, min(16 * i + frow, p.M - 1));
-    const u32x4* wrow[TN];
+    const u32x4* wrow[F8 ? 1 : TN];
+    const u32x2* qrow[F8 ? TN : 1];
+    float wsc[F8 ? TN : 1];
 #pragma unroll
-    for (int j = 0; j < TN; ++j)
-        wrow[j] = reinterpret_cast<const u32x4*>(p.Wb + (int64_t)min(n0 + 16 * j + frow, p.N - 1) * p.K);
+    for (int j = 0; j < TN; ++j) {
+        const int n = min(n0 + 16 * j + frow, p.N - 1);
+        if constexpr (F8) {
+            qrow[j] = reinterpret_cast<const u32x2*>(p.Wq + (int64_t)n * p.K);
+            wsc[j] = p.wq_scale[n];
+        } else {
+            wrow[j] = reinterpret_cast<const u32x4*>(p.Wb + (int64_t)n * p.K);
+        }
+    }
     const bool gn = GN && p.norm_w != nullptr;  // launch-uniform
     // The rows' sums of squares are taken in every launch, also where no row factor is applied
     // (EPI_RESID, a plain product): 16 FMAs per row tile and k-block beside 8 * TN MFMAs.  Guarding
@@ -1464,14 +1555,17 @@ __global__ void __launch_bounds__(64 * NW) gemm_rows_bf16_kernel(GemmArgs p) {
     const int nkb = p.K >> 5;
     const int kb_lo = wid * nkb / NW, kb_hi = (wid + 1) * nkb / NW;  // this wave's k-blocks
     for (int kb0 = kb_lo; kb0 < kb_hi; kb0 += CH) {
-        u32x4 wv[CH][TN];
+        u32x4 wv[F8 ? 1 : CH][F8 ? 1 : TN];
+        u32x2 qv[F8 ? CH : 1][F8 ? TN : 1];
         f32x4 av[CH][MT][2], gv[GN ? CH : 1][2];
 #pragma unroll
         for (int c = 0; c < CH; ++c) {
             const int k = 32 * min(kb0 + c, kb_hi - 1) + kq;
 #pragma unroll
-            for (int j = 0; j < TN; ++j)
-                wv[c][j] = NT ? __builtin_nontemporal_load(wrow[j] + (k >> 3)) : wrow[j][k >> 3];
+            for (int j = 0; j < TN; ++j) {
+                if constexpr (F8) qv[c][j] = NT ? __builtin_nontemporal_load(qrow[j] + (k >> 3)) : qrow[j][k >> 3];
+                else wv[c][j] = NT ? __builtin_nontemporal_load(wrow[j] + (k >> 3)) : wrow[j][k >> 3];
+            }
 #pragma unroll
             for (int i = 0; i < MT; ++i) {
                 av[c][i][0] = *reinterpret_cast<const f32x4*>(arow[i] + k);
@@ -1490,10 +1584,15 @@ __global__ void __launch_bounds__(64 * NW) gemm_rows_bf16_kernel(GemmArgs p) {
                 float wf[TN][8];
 #pragma unroll
                 for (int j = 0; j < TN; ++j) {
-                    wf[j][0] = bf16_lo(wv[c][j].x); wf[j][1] = bf16_hi(wv[c][j].x);
-                    wf[j][2] = bf16_lo(wv[c][j].y); wf[j][3] = bf16_hi(wv[c][j].y);
-                    wf[j][4] = bf16_lo(wv[c][j].z); wf[j][5] = bf16_hi(wv[c][j].z);
-                    wf[j][6] = bf16_lo(wv[c][j].w); wf[j][7] = bf16_hi(wv[c][j].w);
+                    if constexpr (F8) {
+                        fp8x4_scaled(qv[c][j].x, wsc[j], &wf[j][0]);
+                        fp8x4_scaled(qv[c][j].y, wsc[j], &wf[j][4]);
+                    } else {
+                        wf[j][0] = bf16_lo(wv[c][j].x); wf[j][1] = bf16_hi(wv[c][j].x);
+                        wf[j][2] = bf16_lo(wv[c][j].y); wf[j][3] = bf16_hi(wv[c][j].y);
+                        wf[j][4] = bf16_lo(wv[c][j].z); wf[j][5] = bf16_hi(wv[c][j].z);
+                        wf[j][6] = bf16_lo(wv[c][j].w); wf[j][7] = bf16_hi(wv[c][j].w);
+                    }
                 }
 #pragma unroll
                 for (int i = 0; i < MT; ++i) {

@@ -140,6 +140,13 @@ struct GemmArgs {
     // RMSNorm weight those two multiply into the activations instead (null: none)
     const unsigned short* Wb;
     const float* norm_w;
+    // opt-in fp8 weight storage (l3_set_weight_fp8; DESIGN.md "fp8 weight storage"): W as one OCP
+    // e4m3fn code per element, [N, K] row-major in W's row layout and WITHOUT the RMSNorm fold, with
+    // one power-of-two scale per row, wq_scale [N]: the model is wq_scale[n] * float(Wq[n, k]).  Read
+    // by the fp8 forms of gemv_kernel (gemm_takes_fp8) and gemm_rows_bf16_kernel
+    // (gemm_takes_fp8_rows) under the conditions of Wb, with norm_w as there; never set beside Wb
+    const unsigned char* Wq;
+    const float* wq_scale;
     // the context's l3_set_weight_bf16_rows setting (runtime.hip gemm()): the largest M that
     // gemm_rows_bf16_kernel takes (0: none) and the least N * K * 2 bytes of Wb it takes
     int wb_rows; int64_t wb_min_bytes;
@@ -234,10 +241,12 @@ constexpr int GEMV_MAXP = 8;
 //   tiled:            BM, BN, BK, LDS stages, group_m
 //   x6:               BM, BN, BK, waves, group_m
 //   rows_bf16:        MT (row tiles), waves, NT, TN
+//   gemv_fp8:         as gemv, on GemmArgs::Wq
+//   rows_fp8:         as rows_bf16, on GemmArgs::Wq
 // launches counts the launch sites passed since gemm_route_reset (0: nothing was launched)
 enum GemmRouteFamily : int {
     ROUTE_NONE = 0, ROUTE_GEMV = 1, ROUTE_GEMV_BF16 = 2, ROUTE_SKINNY = 3, ROUTE_SPLITK = 4, ROUTE_TILED = 5,
-    ROUTE_X6 = 6, ROUTE_ROWS_BF16 = 7,
+    ROUTE_X6 = 6, ROUTE_ROWS_BF16 = 7, ROUTE_GEMV_FP8 = 8, ROUTE_ROWS_FP8 = 9,
 };
 struct GemmRoute {
     int family;
@@ -648,6 +657,20 @@ bool gemm_takes_bf16(int epi, const GemmArgs& a);
 // GemmArgs::wb_rows rows, N * K * 2 >= GemmArgs::wb_min_bytes); checked before every other choice
 bool gemm_takes_bf16_rows(int epi, const GemmArgs& a);
 constexpr int WB_ROWS_MAX = 64;  // rows gemm_rows_bf16_kernel is instantiated for
+// the same two questions for GemmArgs::Wq (fp8 weight storage): the fp8 form of gemv_kernel, and
+// the fp8 form of gemm_rows_bf16_kernel (the rows setting and its N * K * 2 threshold are shared,
+// so the same launches are taken under either storage)
+bool gemm_takes_fp8(int epi, const GemmArgs& a);
+bool gemm_takes_fp8_rows(int epi, const GemmArgs& a);
+// fp8 weight storage (misc.hip): per row of w [rows, K] the power-of-two scale 2^e (the smallest
+// with amax / 2^e <= 448, e in [-126, 127]; 1 for an all-zero row) -> scale[row], and
+// codes[row, k] = e4m3fn(w / scale), round-to-nearest-even.  cnt (four counters, zeroed by the
+// caller): cnt[sel] += the elements that differ from scale * float(code), cnt[2 + sel] += the
+// non-finite elements (coded as 0, not counted as inexact); sel = (row / sel_rows) & 1 when
+// sel_rows > 0 (gate / up interleaved in groups of that many rows), else 0.  write_back:
+// w = scale * float(code) as well.  K % 4 == 0
+hipError_t launch_to_fp8_rows(float* w, unsigned char* codes, float* scale, int64_t rows, int K, int sel_rows,
+                              bool write_back, unsigned long long* cnt, hipStream_t s);
 // bf16 weight storage (misc.hip): out[i] = bf16(w[i]), round-to-nearest-even on the top 16 bits
 // (NaN -> 0x7fc0); *n_inexact (a pair, zeroed by the caller) += the elements whose value changed
 // (NaN not counted) — pair entry (i / sel_stride) & 1 when sel_stride > 0 (gate / up interleaved

@@ -269,6 +269,91 @@ hipError_t launch_to_bf16(float* w, unsigned short* out, int64_t n, int64_t sel_
     return hipGetLastError();
 }
 
+// fp8 weight storage (l3_set_weight_fp8; DESIGN.md "fp8 weight storage"): per-row power-of-two
+// scaled OCP e4m3fn.  |a| <= 448 always (the scale sees to it), so nothing saturates and the NaN
+// codes 0x7f / 0xff are never produced.  Round-to-nearest-even in integer arithmetic: below the
+// least normal 2^-6 the code is rint(a * 2^9) (8 is the least normal's code), else the fp32 bits
+// rounded to three mantissa bits with the carry running into the exponent; -0 keeps its sign.
+__device__ __forceinline__ unsigned e4m3_rne(float v) {
+    const unsigned u = __float_as_uint(v), sign = (u >> 24) & 0x80u;
+    const float a = __uint_as_float(u & 0x7fffffffu);
+    if (a < 0.015625f) return sign | (unsigned)__builtin_rintf(a * 512.0f);
+    const unsigned b = __float_as_uint(a);
+    return sign | (((b + 0x7ffffu + ((b >> 20) & 1u)) >> 20) - (120u << 3));
+}
+__device__ __forceinline__ float e4m3_value(unsigned c) {
+    const unsigned e = (c >> 3) & 15u, m = c & 7u;
+    const float a = e ? __uint_as_float(((e + 120u) << 23) | (m << 20)) : (float)m * 0.001953125f;
+    return (c & 0x80u) ? -a : a;
+}
+
+// one wave per row, four rows per block: the row's amax (non-finite elements left out and counted),
+// its scale, then the codes four at a time; the wave's counts leave in vector atomics
+__global__ void __launch_bounds__(256) to_fp8_rows_kernel(float* w, unsigned char* codes, float* scale, int64_t rows,
+                                                          int K, int sel_rows, int write_back,
+                                                          unsigned long long* cnt) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;  // wave-uniform
+    float* wr = w + row * K;
+    const int K4 = K >> 2;
+    unsigned amax = 0;  // |x| as bits: ordered like the values
+    int bad = 0, nonfin = 0;
+    for (int k4 = lane; k4 < K4; k4 += 64) {
+        const uint4 v = reinterpret_cast<const uint4*>(wr)[k4];
+        const unsigned a[4] = {v.x & 0x7fffffffu, v.y & 0x7fffffffu, v.z & 0x7fffffffu, v.w & 0x7fffffffu};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (a[i] >= 0x7f800000u) nonfin += 1;
+            else amax = max(amax, a[i]);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) amax = max(amax, (unsigned)__shfl_xor((int)amax, o));
+    // amax = (1 + f) 2^E, 448 = 1.75 * 2^8: the smallest e with amax / 2^e <= 448
+    int e = 0;
+    if (amax) {
+        const int E = (int)(amax >> 23) - 127;
+        e = (amax & 0x7fffffu) <= 0x600000u ? E - 8 : E - 7;
+        e = e < -126 ? -126 : e;  // (E <= 127, so e <= 120)
+    }
+    const float sc = __uint_as_float((unsigned)(e + 127) << 23), inv = __uint_as_float((unsigned)(127 - e) << 23);
+    if (lane == 0) scale[row] = sc;
+    for (int k4 = lane; k4 < K4; k4 += 64) {
+        const uint4 v = reinterpret_cast<const uint4*>(wr)[k4];
+        const unsigned in[4] = {v.x, v.y, v.z, v.w};
+        unsigned c[4], r[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const bool fin = (in[i] & 0x7fffffffu) < 0x7f800000u;
+            c[i] = fin ? e4m3_rne(__uint_as_float(in[i]) * inv) : 0u;
+            r[i] = __float_as_uint(e4m3_value(c[i]) * sc);
+            bad += fin && r[i] != in[i];
+        }
+        reinterpret_cast<unsigned*>(codes + row * K)[k4] = c[0] | (c[1] << 8) | (c[2] << 16) | (c[3] << 24);
+        if (write_back) reinterpret_cast<uint4*>(wr)[k4] = uint4{r[0], r[1], r[2], r[3]};
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        bad += __shfl_xor(bad, o);
+        nonfin += __shfl_xor(nonfin, o);
+    }
+    if (lane == 0) {
+        const int sel = sel_rows > 0 ? (int)((row / sel_rows) & 1) : 0;
+        if (bad) atomicAdd(cnt + sel, (unsigned long long)bad);
+        if (nonfin) atomicAdd(cnt + 2 + sel, (unsigned long long)nonfin);
+    }
+}
+
+hipError_t launch_to_fp8_rows(float* w, unsigned char* codes, float* scale, int64_t rows, int K, int sel_rows,
+                              bool write_back, unsigned long long* cnt, hipStream_t s) {
+    if (rows <= 0) return hipSuccess;
+    if (K <= 0 || K % 4 != 0 || sel_rows < 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(to_fp8_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, w, codes, scale, rows, K,
+                       sel_rows, write_back ? 1 : 0, cnt);
+    return hipGetLastError();
+}
+
 // undo of a speculative decode step's K / V append (runtime.hip, l3_greedy_step_host)
 // Put back one cache slot from kv_bak (the run-ahead undo).  With a guard (the persistent batch-1
 // step, B = 1), what to put back is decided on the device when the restore runs, stream-ordered

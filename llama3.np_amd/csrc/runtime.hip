@@ -85,6 +85,11 @@ struct Layer {
     // layout and without the norm fold, made by l3_finalize (null when the mode is off); read by
     // the bf16-weight GEMV, with n_attn / n_ffn applied to the activations (GemmArgs::norm_w)
     unsigned short *wqkvb = nullptr, *wob = nullptr, *wgub = nullptr, *wdb = nullptr;
+    // opt-in fp8 weight storage (l3_set_weight_fp8): each weight as e4m3fn codes in the same layout,
+    // unfolded, with one power-of-two scale per row (null when the mode is off; never beside the
+    // bf16 copies); read by the fp8 forms of the same two kernels (GemmArgs::Wq, wq_scale)
+    unsigned char *wqkvq = nullptr, *woq = nullptr, *wguq = nullptr, *wdq = nullptr;
+    float *wqkvs = nullptr, *wos = nullptr, *wgus = nullptr, *wds = nullptr;
 };
 
 struct Timer {
@@ -119,6 +124,15 @@ struct l3_ctx {
     int wb_rows = WB_ROWS_DEFAULT;
     int64_t wb_rows_min_bytes = WB_ROWS_MIN_BYTES_DEFAULT;
     int64_t wb_rows_launches = 0;
+    // fp8 weight storage (l3_set_weight_fp8, L3_WEIGHT_FP8): 0 off, 1 exact, 2 round; taken at
+    // l3_finalize, which makes the code / scale copies (Layer::wqkvq / wqkvs ..., lm_headq / lm_heads);
+    // exclusive with weight_bf16.  The rows setting above governs whichever copy the context has
+    int weight_fp8 = 0;
+    unsigned char* lm_headq = nullptr;
+    float* lm_heads = nullptr;
+    int64_t wq_bytes = 0;            // bytes of the codes and the scales
+    int64_t wq_launches = 0;         // GEMV launches issued on them (a captured step: at capture)
+    int64_t wq_rows_launches = 0;    // launches of the rows kernel's fp8 form
     // layer 0's QKV of a prefill as a lookup in a table of its pre-RoPE rows per token id
     // (embed_qkv.h, l3_set_embed_qkv, L3_EMBED_QKV): built at the first call that qualifies, on
     // stream, if its bytes fit embed_qkv_cap; a refused allocation is not retried
@@ -496,6 +510,12 @@ extern "C" int l3_create(int32_t device, const l3_dims* dims, l3_ctx** out) {
     {
         const int m = env_knob("L3_WEIGHT_BF16", 0);
         c->weight_bf16 = m == 1 || m == 2 ? m : 0;
+        const int f = env_knob("L3_WEIGHT_FP8", 0);
+        c->weight_fp8 = f == 1 || f == 2 ? f : 0;
+        if (c->weight_bf16 && c->weight_fp8) {
+            delete c;
+            return fail("l3_create: L3_WEIGHT_BF16 and L3_WEIGHT_FP8 are both set (one compact weight copy per context)");
+        }
         // l3_set_weight_bf16_rows' defaults for new contexts (values out of range: ignored)
         // and text that is not a number
         if (const char* rw = getenv("L3_WEIGHT_BF16_ROWS"); rw && *rw) {
@@ -583,8 +603,10 @@ extern "C" int l3_destroy(l3_ctx* c) {
         dfree(L.cache_k); dfree(L.cache_v);
         dfree(L.wqkv3); dfree(L.wo3); dfree(L.wgu3); dfree(L.wd3);
         dfree(L.wqkvb); dfree(L.wob); dfree(L.wgub); dfree(L.wdb);
+        dfree(L.wqkvq); dfree(L.woq); dfree(L.wguq); dfree(L.wdq);
+        dfree(L.wqkvs); dfree(L.wos); dfree(L.wgus); dfree(L.wds);
     }
-    dfree(c->lm_headb);
+    dfree(c->lm_headb); dfree(c->lm_headq); dfree(c->lm_heads);
     dfree(c->emb); dfree(c->lm_head); dfree(c->final_norm); dfree(c->rope_cos); dfree(c->rope_sin);
     dfree(c->h); dfree(c->q); dfree(c->attn); dfree(c->hid); dfree(c->logits); dfree(c->ids);
     dfree(c->oparts); dfree(c->amax_part); dfree(c->hsum); dfree(c->skws); dfree(c->amax_rows);
@@ -831,6 +853,9 @@ extern "C" int l3_set_weight_bf16(l3_ctx* c, int32_t mode) {
                     "fp32 weights there; set the mode before l3_finalize)");
     if (mode && c->group && group_members(c->group) > 1)
         return fail("l3_set_weight_bf16: this context is a member of a multi-device l3_group (not supported)");
+    if (mode && c->weight_fp8)
+        return fail("l3_set_weight_bf16: fp8 weight storage is set on this context (mode %d); set it to 0 first",
+                    c->weight_fp8);
     c->weight_bf16 = mode;
     return 0;
 }
@@ -847,13 +872,138 @@ extern "C" int l3_weight_bf16_info(l3_ctx* c, int32_t* mode, int64_t* bytes, int
 // gemm_rows_bf16_kernel: l3_weight_bf16_rows_info); the context's rows setting travels in the
 // arguments, so two contexts of one process may differ
 static hipError_t gemm(l3_ctx* c, int epi, const GemmArgs& g_in, hipStream_t s) {
-    if (!g_in.Wb) return launch_gemm(epi, g_in, s);
+    if (!g_in.Wb && !g_in.Wq) return launch_gemm(epi, g_in, s);
     GemmArgs g = g_in;
     g.wb_rows = c->wb_rows;
     g.wb_min_bytes = c->wb_rows_min_bytes;
     if (gemm_takes_bf16_rows(epi, g)) c->wb_rows_launches += 1;
     else if (gemm_takes_bf16(epi, g)) c->wb_launches += 1;
+    else if (gemm_takes_fp8_rows(epi, g)) c->wq_rows_launches += 1;
+    else if (gemm_takes_fp8(epi, g)) c->wq_launches += 1;
     return launch_gemm(epi, g, s);
+}
+
+// ---- fp8 weight storage (DESIGN.md "fp8 weight storage") --------------------------------------
+static void free_fp8(l3_ctx* c) {
+    for (auto& L : c->layers) {
+        dfree(L.wqkvq); dfree(L.woq); dfree(L.wguq); dfree(L.wdq);
+        dfree(L.wqkvs); dfree(L.wos); dfree(L.wgus); dfree(L.wds);
+        L.wqkvq = L.woq = L.wguq = L.wdq = nullptr;
+        L.wqkvs = L.wos = L.wgus = L.wds = nullptr;
+    }
+    dfree(c->lm_headq); dfree(c->lm_heads);
+    c->lm_headq = nullptr;
+    c->lm_heads = nullptr;
+    c->wq_bytes = 0;
+}
+
+extern "C" int l3_set_weight_fp8(l3_ctx* c, int32_t mode) {
+    CHECK_CTX(c);
+    if (mode < 0 || mode > 2) return fail("l3_set_weight_fp8: mode %d (0 off, 1 exact, 2 round)", mode);
+    if (c->finalized)
+        return fail("l3_set_weight_fp8: context already finalized (the norm weights are folded into the "
+                    "fp32 weights there; set the mode before l3_finalize)");
+    if (mode && c->group && group_members(c->group) > 1)
+        return fail("l3_set_weight_fp8: this context is a member of a multi-device l3_group (not supported)");
+    if (mode && c->weight_bf16)
+        return fail("l3_set_weight_fp8: bf16 weight storage is set on this context (mode %d); set it to 0 first",
+                    c->weight_bf16);
+    c->weight_fp8 = mode;
+    return 0;
+}
+
+extern "C" int l3_weight_fp8_info(l3_ctx* c, int32_t* mode, int64_t* bytes, int64_t* gemv_launches,
+                                  int64_t* rows_launches) {
+    CHECK_CTX(c);
+    if (mode) *mode = c->weight_fp8;
+    if (bytes) *bytes = c->wq_bytes;
+    if (gemv_launches) *gemv_launches = c->wq_launches;
+    if (rows_launches) *rows_launches = c->wq_rows_launches;
+    return 0;
+}
+
+// The code / scale copies of every projection whose kinds were all uploaded, and of the lm_head,
+// from the weights as uploaded (before the norm fold).  A non-finite element fails the call in
+// both modes.  Exact mode: any element that is not scale * float(code) of its own row fails the
+// call — the first (layer, kind) in upload order is named — and leaves the context as it was.
+// Round mode: the fp32 tensors become that value too, so the kernels that read them compute the
+// same model.
+static int finalize_fp8(l3_ctx* c) {
+    static const char* const kind_name[] = {"self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj",
+                                            "self_attn.o_proj", "mlp.gate_proj", "mlp.up_proj", "mlp.down_proj"};
+    const int D = c->d.dim, FD = c->d.hidden_dim, VS = c->d.vocab_size;
+    const int nl = (int)c->layers.size();
+    const bool wr = c->weight_fp8 == 2;
+    // [nl + 1][7][4]: per layer and kind slot (kind - L3_W_Q; the lm_head: slot 0 of the last group)
+    // the four counters of launch_to_fp8_rows {inexact, inexact of the up rows, non-finite,
+    // non-finite of the up rows}; gate | up are one launch, on slot 4's group
+    unsigned long long* cnt = nullptr;
+    const size_t per = 7 * 4, ncnt = (size_t)(nl + 1) * per;
+    HIP_TRY(hipMalloc(&cnt, ncnt * 8));
+    auto bail = [&](int rc) {
+        (void)hipStreamSynchronize(c->stream);
+        dfree(cnt);
+        free_fp8(c);
+        return rc;
+    };
+    if (hipMemsetAsync(cnt, 0, ncnt * 8, c->stream) != hipSuccess) return bail(fail("l3_finalize: memset failed"));
+    const unsigned QKV = (1u << L3_W_Q) | (1u << L3_W_K) | (1u << L3_W_V);
+    const unsigned GU = (1u << L3_W_GATE) | (1u << L3_W_UP);
+    hipError_t e = hipSuccess;
+    int64_t bytes = 0;
+    auto conv = [&](float* w, unsigned char** codes, float** sc, int64_t rows, int K, int sel_rows,
+                    unsigned long long* k) {
+        if (e != hipSuccess) return;
+        e = hipMalloc(codes, (size_t)rows * K);
+        if (e == hipSuccess) e = hipMalloc(sc, (size_t)rows * 4);
+        if (e == hipSuccess) e = launch_to_fp8_rows(w, *codes, *sc, rows, K, sel_rows, wr, k, c->stream);
+        bytes += rows * K + rows * 4;
+    };
+    for (int li = 0; li < nl; ++li) {
+        Layer& L = c->layers[li];
+        unsigned long long* k = cnt + (size_t)li * per;
+        if ((L.have & QKV) == QKV) {  // q | k | v stacked: one copy, a launch and a counter group per section
+            if (e == hipSuccess) e = hipMalloc(&L.wqkvq, (size_t)c->qkvn * D);
+            if (e == hipSuccess) e = hipMalloc(&L.wqkvs, (size_t)c->qkvn * 4);
+            const int64_t off[4] = {0, c->qdim, c->qdim + c->kvdim, c->qkvn};  // rows
+            for (int t = 0; t < 3 && e == hipSuccess; ++t)
+                e = launch_to_fp8_rows(L.wqkv + off[t] * D, L.wqkvq + off[t] * D, L.wqkvs + off[t], off[t + 1] - off[t],
+                                       D, 0, wr, k + 4 * t, c->stream);
+            bytes += (int64_t)c->qkvn * D + (int64_t)c->qkvn * 4;
+        }
+        if (L.have & (1u << L3_W_O)) conv(L.wo, &L.woq, &L.wos, D, c->qdim, 0, k + 4 * 3);
+        if ((L.have & GU) == GU) conv(L.wgu, &L.wguq, &L.wgus, 2 * (int64_t)FD, D, 16, k + 4 * 4);  // 16-row groups: gate, up
+        if (L.have & (1u << L3_W_DOWN)) conv(L.wd, &L.wdq, &L.wds, D, FD, 0, k + 4 * 6);
+    }
+    if (c->have_lm) conv(c->lm_head, &c->lm_headq, &c->lm_heads, VS, D, 0, cnt + (size_t)nl * per);
+    std::vector<unsigned long long> h(ncnt, 0);
+    if (e == hipSuccess) e = hipMemcpyAsync(h.data(), cnt, ncnt * 8, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return bail(fail("l3_finalize: making the fp8 weight copies failed: %s", hipGetErrorString(e)));
+    }
+    // slot t of a layer: its inexact / non-finite counts (gate | up share a launch: the up rows'
+    // counts are the second of each pair of slot 4)
+    auto count = [&](int li, int t, int what) {
+        const unsigned long long* k = h.data() + (size_t)li * per;
+        return t == 5 ? k[4 * 4 + 2 * what + 1] : k[4 * t + 2 * what];
+    };
+    for (int what = 1; what >= (c->weight_fp8 == 1 ? 0 : 1); --what) {  // non-finite first, then exact mode's check
+        for (int li = 0; li < nl; ++li)
+            for (int t = 0; t < 7; ++t)
+                if (const unsigned long long n = count(li, t, what))
+                    return bail(fail("l3_finalize: weight_fp8%s: model.layers.%d.%s.weight (layer %d, kind %d) has %llu "
+                                     "elements that are %s", what ? "" : " exact mode", li, kind_name[t], li,
+                                     t + (int)L3_W_Q, n, what ? "not finite" : "not fp8-e4m3 values at the row's scale"));
+        if (const unsigned long long n = h[(size_t)nl * per + 2 * what])
+            return bail(fail("l3_finalize: weight_fp8%s: lm_head.weight (kind %d) has %llu elements that are %s",
+                             what ? "" : " exact mode", (int)L3_W_LM_HEAD, n,
+                             what ? "not finite" : "not fp8-e4m3 values at the row's scale"));
+    }
+    dfree(cnt);
+    c->wq_bytes = bytes;
+    return 0;
 }
 
 // The bf16 copies of every projection whose kinds were all uploaded, and of the lm_head, from the
@@ -930,6 +1080,7 @@ extern "C" int l3_finalize(l3_ctx* c) {
     if (c->finalized) return 0;
     if (set_dev(c)) return 1;
     if (c->weight_bf16 && finalize_bf16(c)) return 1;
+    if (c->weight_fp8 && finalize_fp8(c)) return 1;
     // Fold each RMSNorm weight into the columns of the GEMM that consumes the normalised rows
     // (attention norm -> wqkv, FFN norm -> wgu, final norm -> lm_head): the GEMMs then apply
     // only the per-row 1/rms factor.  Only where both were uploaded: a layer-only (attention)
@@ -1063,11 +1214,13 @@ static int run_layer(l3_ctx* c, int li, int B, int L, int start_pos, const int* 
     // the last row of each sequence only (its RoPE at position start_pos + L - 1)
     const bool kv_only = prune && T > 256;
     g.W3 = Ly.wqkv3;  // null unless the x6 path is on (then launch_gemm takes it past 32 rows)
-    g.Wb = Ly.wqkvb; g.norm_w = Ly.wqkvb ? Ly.n_attn : nullptr;  // null unless bf16 weight storage is on
+    g.Wb = Ly.wqkvb; g.Wq = Ly.wqkvq; g.wq_scale = Ly.wqkvs;  // null unless bf16 / fp8 weight storage is on
+    g.norm_w = Ly.wqkvb || Ly.wqkvq ? Ly.n_attn : nullptr;
     if (kv_only) {
         g.W = Ly.wqkv + (int64_t)c->qdim * D; g.N = 2 * c->kvdim; g.col_base = c->qdim;
         if (g.W3) g.W3 += (int64_t)c->qdim * 3 * D;
         if (g.Wb) g.Wb += (int64_t)c->qdim * D;
+        if (g.Wq) { g.Wq += (int64_t)c->qdim * D; g.wq_scale += c->qdim; }
     }
     // Layer 0 on embedding rows, exactly where launch_gemm would reach the tiled fp32 kernel with
     // a_rows set (more than 256 rows: past the GEMV, the skinny kernel and split-K, which round
@@ -1091,7 +1244,7 @@ static int run_layer(l3_ctx* c, int li, int B, int L, int start_pos, const int* 
         GemmArgs o{};  // O-proj + residual on the last rows, in place on h
         if (kv_only) {
             GemmArgs gq = g;  // q of the last rows: [B, qdim], compact
-            gq.A = hl; gq.lda = (int64_t)L * D4; gq.W = Ly.wqkv; gq.W3 = nullptr; gq.Wb = Ly.wqkvb; gq.N = c->qdim; gq.col_base = 0;
+            gq.A = hl; gq.lda = (int64_t)L * D4; gq.W = Ly.wqkv; gq.W3 = nullptr; gq.Wb = Ly.wqkvb; gq.Wq = Ly.wqkvq; gq.wq_scale = Ly.wqkvs; gq.N = c->qdim; gq.col_base = 0;
             gq.M = B; gq.L = 1; gq.start_pos = start_pos + L - 1; gq.force_skinny = gq.split_rows = true;
             gq.ws = nullptr;
             if (timed_on(c, L3_K_QKV, s, [&] { return gemm(c, EPI_QKV, gq, s); })) return 1;
@@ -1103,27 +1256,27 @@ static int run_layer(l3_ctx* c, int li, int B, int L, int start_pos, const int* 
             if (timed_on(c, L3_K_ATTN, s, [&] { return launch_attention_last(a, s); })) return 1;
             o.A = attn + (int64_t)(L - 1) * c->qdim; o.lda = (int64_t)L * c->qdim;
         }
-        o.W = Ly.wo; o.Wb = Ly.wob; o.C = hl; o.ldc = (int64_t)L * D4;
+        o.W = Ly.wo; o.Wb = Ly.wob; o.Wq = Ly.woq; o.wq_scale = Ly.wos; o.C = hl; o.ldc = (int64_t)L * D4;
         o.M = B; o.N = D4; o.K = c->qdim; o.norm = false; o.force_skinny = o.split_rows = true;
         if (timed_on(c, L3_K_OPROJ, s, [&] { return gemm(c, EPI_RESID, o, s); })) return 1;
         GemmArgs gl{};  // rmsnorm -> gate|up -> SwiGLU on the last rows
         gl.A = hl; gl.lda = (int64_t)L * D4; gl.W = Ly.wgu; gl.C = hid; gl.ldc = FD;
-        gl.Wb = Ly.wgub; gl.norm_w = Ly.wgub ? Ly.n_ffn : nullptr;
+        gl.Wb = Ly.wgub; gl.Wq = Ly.wguq; gl.wq_scale = Ly.wgus; gl.norm_w = Ly.wgub || Ly.wguq ? Ly.n_ffn : nullptr;
         gl.M = B; gl.N = 2 * FD; gl.K = D4; gl.norm = true; gl.eps = c->d.norm_eps; gl.force_skinny = gl.split_rows = true;
         if (timed_on(c, L3_K_GATEUP, s, [&] { return gemm(c, EPI_SWIGLU, gl, s); })) return 1;
         GemmArgs dl{};  // down + residual on the last rows
-        dl.A = hid; dl.lda = FD; dl.W = Ly.wd; dl.Wb = Ly.wdb; dl.C = hl; dl.ldc = (int64_t)L * D4;
+        dl.A = hid; dl.lda = FD; dl.W = Ly.wd; dl.Wb = Ly.wdb; dl.Wq = Ly.wdq; dl.wq_scale = Ly.wds; dl.C = hl; dl.ldc = (int64_t)L * D4;
         dl.M = B; dl.N = D4; dl.K = FD; dl.norm = false; dl.force_skinny = dl.split_rows = true;
         return timed_on(c, L3_K_DOWN, s, [&] { return gemm(c, EPI_RESID, dl, s); });
     }
     GemmArgs gu{};  // rmsnorm -> gate|up -> SwiGLU
     gu.A = h; gu.lda = D; gu.W = Ly.wgu; gu.W3 = Ly.wgu3; gu.C = hid; gu.ldc = FD;
     gu.M = (int)T; gu.N = 2 * FD; gu.K = D; gu.norm = true;  // n_ffn folded into wgu
-    gu.Wb = Ly.wgub; gu.norm_w = Ly.wgub ? Ly.n_ffn : nullptr;
+    gu.Wb = Ly.wgub; gu.Wq = Ly.wguq; gu.wq_scale = Ly.wgus; gu.norm_w = Ly.wgub || Ly.wguq ? Ly.n_ffn : nullptr;
     gu.eps = c->d.norm_eps;
     GemmArgs dn{};  // down + residual
     dn.A = hid; dn.lda = FD; dn.W = Ly.wd; dn.W3 = Ly.wd3; dn.C = h; dn.ldc = D;
-    dn.M = (int)T; dn.N = D; dn.K = FD; dn.norm = false; dn.Wb = Ly.wdb;
+    dn.M = (int)T; dn.N = D; dn.K = FD; dn.norm = false; dn.Wb = Ly.wdb; dn.Wq = Ly.wdq; dn.wq_scale = Ly.wds;
     gu.ws = dn.ws = skws; gu.ws_cap = dn.ws_cap = c->skws_cap;
     // Batch-1 decode: the O-proj rides in the attention launch as per-head partial rows, which
     // gate|up adds to its input and down to its residual (h + attn . Wo^T, llama3.py:211,253),
@@ -1149,7 +1302,7 @@ static int run_layer(l3_ctx* c, int li, int B, int L, int start_pos, const int* 
     } else {
         // O-proj + residual (in place on h)
         GemmArgs o{};
-        o.A = attn; o.lda = c->qdim; o.W = Ly.wo; o.W3 = Ly.wo3; o.Wb = Ly.wob; o.C = h; o.ldc = D;
+        o.A = attn; o.lda = c->qdim; o.W = Ly.wo; o.W3 = Ly.wo3; o.Wb = Ly.wob; o.Wq = Ly.woq; o.wq_scale = Ly.wos; o.C = h; o.ldc = D;
         o.M = (int)T; o.N = D; o.K = c->qdim; o.norm = false;
         o.ws = skws; o.ws_cap = c->skws_cap;
         if (emb_ids) { o.res_src = c->emb; o.res_rows = emb_ids; }  // h = emb[ids] + attn . Wo^T
@@ -1167,7 +1320,8 @@ static GemmArgs lm_head_args(l3_ctx* c, int B, int L, float* logits_dev, int b0)
     lm.A = c->h + ((int64_t)b0 * L + L - 1) * D; lm.lda = (int64_t)L * D; lm.W = c->lm_head;
     lm.C = logits_dev + (int64_t)b0 * VS; lm.ldc = VS;
     lm.M = B; lm.N = (int)VS; lm.K = (int)D; lm.norm = true;  // final norm folded
-    lm.Wb = c->lm_headb; lm.norm_w = c->lm_headb ? c->final_norm : nullptr;
+    lm.Wb = c->lm_headb; lm.Wq = c->lm_headq; lm.wq_scale = c->lm_heads;
+    lm.norm_w = c->lm_headb || c->lm_headq ? c->final_norm : nullptr;
     lm.eps = c->d.norm_eps;
     return lm;
 }
@@ -1276,7 +1430,7 @@ static int forward_dev(l3_ctx* c, const int32_t* ids_dev, int B, int L, int star
         GemmArgs g = lm_head_args(c, n, L, logits_dev, first);
         g.wb_rows = c->wb_rows;
         g.wb_min_bytes = c->wb_rows_min_bytes;
-        return gemm_takes_bf16_rows(EPI_STORE, g);
+        return gemm_takes_bf16_rows(EPI_STORE, g) || gemm_takes_fp8_rows(EPI_STORE, g);
     };
     bool lm_parts = parts > 1 && !lm_rows(B, 0);
     const int lm_cfg = gemm_store_config(lm_head_args(c, B, L, logits_dev, 0));
@@ -2315,7 +2469,7 @@ static int ragged_step(l3_ctx* c, int B, int s_cap, int chunk) {
         g.eps = c->d.norm_eps;
         g.A = c->h; g.lda = D; g.W = Ly.wqkv; g.C = c->rag_qkv; g.ldc = c->qkvn;
         g.M = B; g.N = c->qkvn; g.K = D; g.norm = true;
-        g.Wb = Ly.wqkvb; g.norm_w = Ly.wqkvb ? Ly.n_attn : nullptr;
+        g.Wb = Ly.wqkvb; g.Wq = Ly.wqkvq; g.wq_scale = Ly.wqkvs; g.norm_w = Ly.wqkvb || Ly.wqkvq ? Ly.n_attn : nullptr;
         g.ws = c->skws; g.ws_cap = c->skws_cap;
         if (li == 0) { g.A = c->emb; g.a_rows = cur; }
         if (timed(c, L3_K_QKV, [&] { return gemm(c, EPI_STORE, g, s); })) return 1;
@@ -2333,7 +2487,7 @@ static int ragged_step(l3_ctx* c, int B, int s_cap, int chunk) {
             }))
             return 1;
         GemmArgs o{};  // O-proj + residual (layer 0: h = emb[cur_id] + attn . Wo^T)
-        o.A = c->attn; o.lda = c->qdim; o.W = Ly.wo; o.Wb = Ly.wob; o.C = c->h; o.ldc = D;
+        o.A = c->attn; o.lda = c->qdim; o.W = Ly.wo; o.Wb = Ly.wob; o.Wq = Ly.woq; o.wq_scale = Ly.wos; o.C = c->h; o.ldc = D;
         o.M = B; o.N = D; o.K = c->qdim; o.norm = false;
         o.ws = c->skws; o.ws_cap = c->skws_cap;
         if (li == 0) { o.res_src = c->emb; o.res_rows = cur; }
@@ -2341,9 +2495,9 @@ static int ragged_step(l3_ctx* c, int B, int s_cap, int chunk) {
         GemmArgs gu{};  // rmsnorm -> gate|up -> SwiGLU
         gu.A = c->h; gu.lda = D; gu.W = Ly.wgu; gu.C = c->hid; gu.ldc = FD;
         gu.M = B; gu.N = 2 * FD; gu.K = D; gu.norm = true; gu.eps = c->d.norm_eps;
-        gu.Wb = Ly.wgub; gu.norm_w = Ly.wgub ? Ly.n_ffn : nullptr;
+        gu.Wb = Ly.wgub; gu.Wq = Ly.wguq; gu.wq_scale = Ly.wgus; gu.norm_w = Ly.wgub || Ly.wguq ? Ly.n_ffn : nullptr;
         GemmArgs dn{};  // down + residual
-        dn.A = c->hid; dn.lda = FD; dn.W = Ly.wd; dn.Wb = Ly.wdb; dn.C = c->h; dn.ldc = D;
+        dn.A = c->hid; dn.lda = FD; dn.W = Ly.wd; dn.Wb = Ly.wdb; dn.Wq = Ly.wdq; dn.wq_scale = Ly.wds; dn.C = c->h; dn.ldc = D;
         dn.M = B; dn.N = D; dn.K = FD; dn.norm = false;
         gu.ws = dn.ws = c->skws; gu.ws_cap = dn.ws_cap = c->skws_cap;
         if (timed(c, L3_K_GATEUP, [&] { return gemm(c, EPI_SWIGLU, gu, s); })) return 1;
@@ -2462,7 +2616,7 @@ static int ragged_extend_layers(l3_ctx* c, int B, int Lmax, bool skinny) {
         g.eps = c->d.norm_eps;
         g.A = c->h; g.lda = D; g.W = Ly.wqkv; g.C = c->rag_ext_qkv; g.ldc = c->qkvn;
         g.M = T; g.N = c->qkvn; g.K = D; g.norm = true;
-        g.Wb = Ly.wqkvb; g.norm_w = Ly.wqkvb ? Ly.n_attn : nullptr;
+        g.Wb = Ly.wqkvb; g.Wq = Ly.wqkvq; g.wq_scale = Ly.wqkvs; g.norm_w = Ly.wqkvb || Ly.wqkvq ? Ly.n_attn : nullptr;
         g.ws = c->skws; g.ws_cap = c->skws_cap;
         if (li == 0) { g.A = c->emb; g.a_rows = c->ids; }
         g.force_skinny = skinny;
@@ -2475,7 +2629,7 @@ static int ragged_extend_layers(l3_ctx* c, int B, int Lmax, bool skinny) {
         a.q_scale = (float)(1.4426950408889634 / std::sqrt((double)c->HD));
         if (timed(c, L3_K_ATTN, [&] { return launch_attn_extend_ragged(a, s); })) return 1;
         GemmArgs o{};  // O-proj + residual (layer 0: h = emb[ids] + attn . Wo^T)
-        o.A = c->attn; o.lda = c->qdim; o.W = Ly.wo; o.W3 = Ly.wo3; o.Wb = Ly.wob; o.C = c->h; o.ldc = D;
+        o.A = c->attn; o.lda = c->qdim; o.W = Ly.wo; o.W3 = Ly.wo3; o.Wb = Ly.wob; o.Wq = Ly.woq; o.wq_scale = Ly.wos; o.C = c->h; o.ldc = D;
         o.M = T; o.N = D; o.K = c->qdim; o.norm = false;
         o.ws = c->skws; o.ws_cap = c->skws_cap;
         if (li == 0) { o.res_src = c->emb; o.res_rows = c->ids; }
@@ -2484,9 +2638,9 @@ static int ragged_extend_layers(l3_ctx* c, int B, int Lmax, bool skinny) {
         GemmArgs gu{};  // rmsnorm -> gate|up -> SwiGLU
         gu.A = c->h; gu.lda = D; gu.W = Ly.wgu; gu.W3 = Ly.wgu3; gu.C = c->hid; gu.ldc = FD;
         gu.M = T; gu.N = 2 * FD; gu.K = D; gu.norm = true; gu.eps = c->d.norm_eps;
-        gu.Wb = Ly.wgub; gu.norm_w = Ly.wgub ? Ly.n_ffn : nullptr;
+        gu.Wb = Ly.wgub; gu.Wq = Ly.wguq; gu.wq_scale = Ly.wgus; gu.norm_w = Ly.wgub || Ly.wguq ? Ly.n_ffn : nullptr;
         GemmArgs dn{};  // down + residual
-        dn.A = c->hid; dn.lda = FD; dn.W = Ly.wd; dn.W3 = Ly.wd3; dn.Wb = Ly.wdb; dn.C = c->h; dn.ldc = D;
+        dn.A = c->hid; dn.lda = FD; dn.W = Ly.wd; dn.W3 = Ly.wd3; dn.Wb = Ly.wdb; dn.Wq = Ly.wdq; dn.wq_scale = Ly.wds; dn.C = c->h; dn.ldc = D;
         dn.M = T; dn.N = D; dn.K = FD; dn.norm = false;
         gu.ws = dn.ws = c->skws; gu.ws_cap = dn.ws_cap = c->skws_cap;
         gu.force_skinny = dn.force_skinny = skinny;
@@ -2894,7 +3048,7 @@ extern "C" int l3_attention_forward_host(l3_ctx* c, int32_t layer, const float* 
     HIP_TRY(hipMemcpyAsync(c->h, x_host, T * D * 4, hipMemcpyHostToDevice, c->stream));
     GemmArgs g{};
     g.A = c->h; g.lda = D; g.W = Ly.wqkv; g.M = (int)T; g.N = c->qkvn; g.K = D; g.norm = false;
-    g.Wb = Ly.wqkvb;  // (no attention norm in this context: norm_w stays null)
+    g.Wb = Ly.wqkvb; g.Wq = Ly.wqkvq; g.wq_scale = Ly.wqkvs;  // (no attention norm in this context: norm_w stays null)
     g.q_out = c->q; g.cache_k = Ly.cache_k; g.cache_v = Ly.cache_v;
     g.rope_cos = c->rope_cos; g.rope_sin = c->rope_sin;
     g.L = L; g.start_pos = start_pos; g.H = c->d.n_heads; g.KVH = c->d.n_kv_heads; g.HD = c->HD;
@@ -2907,7 +3061,7 @@ extern "C" int l3_attention_forward_host(l3_ctx* c, int32_t layer, const float* 
     a.HD = c->HD; a.Smax = c->d.max_seq_len;
     if (timed(c, L3_K_ATTN, [&] { return launch_attention(a, c->stream); })) return 1;
     GemmArgs o{};
-    o.A = c->attn; o.lda = c->qdim; o.W = Ly.wo; o.Wb = Ly.wob; o.C = c->h; o.ldc = D;
+    o.A = c->attn; o.lda = c->qdim; o.W = Ly.wo; o.Wb = Ly.wob; o.Wq = Ly.woq; o.wq_scale = Ly.wos; o.C = c->h; o.ldc = D;
     o.M = (int)T; o.N = D; o.K = c->qdim; o.norm = false;
     if (timed(c, L3_K_OPROJ, [&] { return gemm(c, EPI_STORE, o, c->stream); })) return 1;
     HIP_TRY(hipMemcpyAsync(out_host, c->h, T * D * 4, hipMemcpyDeviceToHost, c->stream));
@@ -3347,6 +3501,139 @@ extern "C" int l3_op_linear_bf16_rows_host(l3_ctx* c, const float* x, int64_t ro
         return fail("l3_op_linear_bf16_rows: %d x %d x %d is not a shape of the bf16 rows kernel", g.M, K, N);
     c->wb_rows_launches += 1;
     HIP_TRY(launch_gemm(EPI_STORE, g, c->stream));
+    D2H(y, dy, rows * N);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// fp8 weight storage on plain arrays: the conversion kernel of l3_finalize, and the fp8 forms of
+// the GEMV and of the rows kernel with EPI_STORE
+extern "C" int l3_op_to_fp8_rows_host(l3_ctx* c, const float* x, int64_t rows, int32_t K, uint8_t* codes_out,
+                                      float* scale_out, int64_t* n_inexact) {
+    CHECK_CTX(c);
+    if (rows < 0 || K <= 0 || K % 4 || (rows > 0 && (!x || !codes_out || !scale_out)))
+        return fail("l3_op_to_fp8_rows: bad argument (rows = %lld, K = %d: a positive multiple of 4)", (long long)rows, K);
+    if (set_dev(c)) return 1;
+    Scratch S{c};
+    SCRATCH(dx, rows * K);
+    SCRATCH(dq, rows * K / 4);
+    SCRATCH(ds, rows);
+    SCRATCH(dn, 8);
+    H2D(dx, x, rows * K);
+    HIP_TRY(hipMemsetAsync(dn, 0, 32, c->stream));
+    HIP_TRY(launch_to_fp8_rows(dx, reinterpret_cast<unsigned char*>(dq), ds, rows, K, 0, false,
+                               reinterpret_cast<unsigned long long*>(dn), c->stream));
+    unsigned long long cnt[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(cnt, dn, 32, hipMemcpyDeviceToHost, c->stream));
+    if (rows > 0) {
+        HIP_TRY(hipMemcpyAsync(codes_out, dq, (size_t)rows * K, hipMemcpyDeviceToHost, c->stream));
+        D2H(scale_out, ds, rows);
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (cnt[2]) return fail("l3_op_to_fp8_rows: %llu elements are not finite", cnt[2]);
+    if (n_inexact) *n_inexact = (int64_t)cnt[0];
+    return 0;
+}
+
+// the operands of the two fp8 linear entries, checked on the host: no NaN code, scales that are
+// powers of two (normal fp32 values with a zero mantissa)
+static int check_fp8_operands(const char* who, const uint8_t* codes, const float* scale, int64_t N, int64_t K) {
+    for (int64_t i = 0; i < N * K; ++i)
+        if ((codes[i] & 0x7f) == 0x7f)
+            return fail("%s: code 0x%02x at row %lld, column %lld is a NaN of e4m3fn", who, codes[i], (long long)(i / K),
+                        (long long)(i % K));
+    for (int64_t n = 0; n < N; ++n) {
+        uint32_t u;
+        memcpy(&u, scale + n, 4);
+        const uint32_t ex = (u >> 23) & 0xff;
+        if ((u >> 31) || (u & 0x7fffff) || ex == 0 || ex == 255)
+            return fail("%s: scale[%lld] = %g is not a power of two", who, (long long)n, (double)scale[n]);
+    }
+    return 0;
+}
+
+static void route_out(int32_t* route) {
+    if (!route) return;
+    const GemmRoute r = gemm_last_route();
+    route[0] = r.family;
+    for (int i = 0; i < 5; ++i) route[1 + i] = r.v[i];
+}
+
+extern "C" int l3_op_linear_fp8_host(l3_ctx* c, const float* x, int64_t rows, int32_t K, int32_t N, const uint8_t* codes,
+                                     const float* scale, const float* norm_w, float eps, float* y, int32_t* route) {
+    CHECK_CTX(c);
+    if (!x || !codes || !scale || !y) return fail("l3_op_linear_fp8: null argument");
+    if (rows < 1 || rows > 8) return fail("l3_op_linear_fp8: rows = %lld outside [1, 8] (the GEMV's range)", (long long)rows);
+    if (K <= 0 || K % 32) return fail("l3_op_linear_fp8: K=%d must be a positive multiple of 32", K);
+    if (N <= 0 || N % 4) return fail("l3_op_linear_fp8: N=%d must be a positive multiple of 4", N);
+    if (check_fp8_operands("l3_op_linear_fp8", codes, scale, N, K)) return 1;
+    // rows per launch as in l3_op_linear_bf16_host: always on the GEMV, never another kernel
+    int per = 8;
+    while (per > 1 && (int64_t)per * K > 16384) per /= 2;
+    if (set_dev(c)) return 1;
+    Scratch S{c};
+    SCRATCH(dx, rows * K);
+    SCRATCH(dw, (int64_t)N * K / 4);
+    SCRATCH(ds, N);
+    SCRATCH(dg, K);
+    SCRATCH(dy, rows * N);
+    H2D(dx, x, rows * K);
+    HIP_TRY(hipMemcpyAsync(dw, codes, (size_t)N * K, hipMemcpyHostToDevice, c->stream));
+    H2D(ds, scale, N);
+    if (norm_w) H2D(dg, norm_w, K);
+    gemm_route_reset();
+    for (int64_t r0 = 0; r0 < rows; r0 += per) {
+        GemmArgs g{};
+        g.A = dx + r0 * K; g.lda = K; g.W = nullptr; g.Wq = reinterpret_cast<const unsigned char*>(dw); g.wq_scale = ds;
+        g.norm_w = norm_w ? dg : nullptr; g.norm = norm_w != nullptr; g.eps = eps;
+        g.C = dy + r0 * N; g.ldc = N;
+        g.M = (int)(rows - r0 < per ? rows - r0 : per); g.N = N; g.K = K;
+        if (!gemm_takes_fp8(EPI_STORE, g))
+            return fail("l3_op_linear_fp8: %d x %d x %d is not a shape of the weight-streaming GEMV", g.M, K, N);
+        c->wq_launches += 1;  // always the GEMV, whatever l3_set_weight_bf16_rows says
+        HIP_TRY(launch_gemm(EPI_STORE, g, c->stream));
+    }
+    route_out(route);
+    D2H(y, dy, rows * N);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// the rows kernel's fp8 form with EPI_STORE, one launch; the context's own rows setting plays no
+// part: the launch carries max_rows 64 and min_bytes 0
+extern "C" int l3_op_linear_fp8_rows_host(l3_ctx* c, const float* x, int64_t rows, int32_t K, int32_t N,
+                                          const uint8_t* codes, const float* scale, const float* norm_w, float eps,
+                                          float* y, int32_t* route) {
+    CHECK_CTX(c);
+    if (!x || !codes || !scale || !y) return fail("l3_op_linear_fp8_rows: null argument");
+    if (rows < 2 || rows > WB_ROWS_MAX)
+        return fail("l3_op_linear_fp8_rows: rows = %lld outside [2, %d] (the kernel's range)", (long long)rows, WB_ROWS_MAX);
+    if (K <= 0 || K % 32) return fail("l3_op_linear_fp8_rows: K=%d must be a positive multiple of 32", K);
+    if (N <= 0 || N % 4) return fail("l3_op_linear_fp8_rows: N=%d must be a positive multiple of 4", N);
+    if (check_fp8_operands("l3_op_linear_fp8_rows", codes, scale, N, K)) return 1;
+    if (set_dev(c)) return 1;
+    Scratch S{c};
+    SCRATCH(dx, rows * K);
+    SCRATCH(dw, (int64_t)N * K / 4);
+    SCRATCH(ds, N);
+    SCRATCH(dg, K);
+    SCRATCH(dy, rows * N);
+    H2D(dx, x, rows * K);
+    HIP_TRY(hipMemcpyAsync(dw, codes, (size_t)N * K, hipMemcpyHostToDevice, c->stream));
+    H2D(ds, scale, N);
+    if (norm_w) H2D(dg, norm_w, K);
+    GemmArgs g{};
+    g.A = dx; g.lda = K; g.W = nullptr; g.Wq = reinterpret_cast<const unsigned char*>(dw); g.wq_scale = ds;
+    g.norm_w = norm_w ? dg : nullptr; g.norm = norm_w != nullptr; g.eps = eps;
+    g.C = dy; g.ldc = N;
+    g.M = (int)rows; g.N = N; g.K = K;
+    g.wb_rows = WB_ROWS_MAX; g.wb_min_bytes = 0;
+    if (!gemm_takes_fp8_rows(EPI_STORE, g))
+        return fail("l3_op_linear_fp8_rows: %d x %d x %d is not a shape of the fp8 rows kernel", g.M, K, N);
+    c->wq_rows_launches += 1;
+    gemm_route_reset();
+    HIP_TRY(launch_gemm(EPI_STORE, g, c->stream));
+    route_out(route);
     D2H(y, dy, rows * N);
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
@@ -4159,7 +4446,7 @@ extern "C" int l3_group_create(int32_t ndev, const int32_t* devices, const l3_di
         c->nranks = ndev;
         c->rank = i;
         c->comm_mode = 1;  // the group's gathers are always serialized on the member streams
-        if (ndev > 1) c->weight_bf16 = 0;  // L3_WEIGHT_BF16 is for single-device contexts (l3_set_weight_bf16)
+        if (ndev > 1) c->weight_bf16 = c->weight_fp8 = 0;  // L3_WEIGHT_BF16 / L3_WEIGHT_FP8 are for single-device contexts
     }
     *out = g;
     return 0;

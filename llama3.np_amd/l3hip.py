@@ -108,6 +108,11 @@ _SIGNATURES = {
     "l3_weight_bf16_rows_info": (ctypes.c_int, [_P, _P, _P, _P]),
     "l3_op_linear_bf16_rows_host": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _P, _P, _F, _P]),
     "l3_op_to_bf16_host": (ctypes.c_int, [_P, _P, _I64, _P, _P]),
+    "l3_set_weight_fp8": (ctypes.c_int, [_P, _I32]),
+    "l3_weight_fp8_info": (ctypes.c_int, [_P, _P, _P, _P, _P]),
+    "l3_op_to_fp8_rows_host": (ctypes.c_int, [_P, _P, _I64, _I32, _P, _P, _P]),
+    "l3_op_linear_fp8_host": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _P, _P, _P, _F, _P, _P]),
+    "l3_op_linear_fp8_rows_host": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _P, _P, _P, _F, _P, _P]),
     "l3_op_linear_bf16_host": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _P, _P, _F, _P]),
     "l3_op_gemm_host": (ctypes.c_int, [_P, _P]),
     "l3_set_last_layer_rows": (ctypes.c_int, [_P, _I32]),
@@ -158,7 +163,7 @@ class GemmOp(ctypes.Structure):
 
 
 EPI_STORE, EPI_RESID, EPI_SWIGLU, EPI_QKV = range(4)
-GEMM_FAMILIES = ["none", "gemv", "gemv_bf16", "skinny", "splitk", "tiled", "x6", "rows_bf16"]
+GEMM_FAMILIES = ["none", "gemv", "gemv_bf16", "skinny", "splitk", "tiled", "x6", "rows_bf16", "gemv_fp8", "rows_fp8"]
 _ROUTE_FIELDS = {
     "gemv": ("rows_per_block", "lanes_per_unit", "nt", "row_blocks"),
     "gemv_bf16": ("rows_per_block", "lanes_per_unit", "nt", "row_blocks"),
@@ -167,6 +172,8 @@ _ROUTE_FIELDS = {
     "tiled": ("bm", "bn", "bk", "stages", "group_m"),
     "x6": ("bm", "bn", "bk", "waves", "group_m"),
     "rows_bf16": ("mt", "waves", "nt", "tn"),
+    "gemv_fp8": ("rows_per_block", "lanes_per_unit", "nt", "row_blocks"),
+    "rows_fp8": ("mt", "waves", "nt", "tn"),
     "none": (),
 }
 
@@ -713,6 +720,22 @@ class Context:
         check(lib().l3_weight_bf16_info(self._h, ctypes.byref(m), ctypes.byref(b), ctypes.byref(n)))
         return {"mode": m.value, "bytes": b.value, "gemv_launches": n.value}
 
+    def set_weight_fp8(self, mode: int) -> None:
+        """Extension (l3_set_weight_fp8): per-row power-of-two scaled fp8 e4m3 storage of the
+        projections and the lm_head for the 1 .. 64-row decode kernels — 0 off, 1 exact (every
+        element must equal ``utils.round_fp8_rows`` of itself, else ``finalize`` raises naming the
+        tensor), 2 round (the fp32 weights become those values too).  Before ``finalize``; not
+        together with ``set_weight_bf16``."""
+        check(lib().l3_set_weight_fp8(self._h, int(mode)))
+
+    def weight_fp8_info(self) -> dict:
+        """The mode, the bytes of the code and scale copies, and the launches issued on them by the
+        GEMV's fp8 form and by the rows kernel's."""
+        m, b, n, r = ctypes.c_int32(0), ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        check(lib().l3_weight_fp8_info(self._h, ctypes.byref(m), ctypes.byref(b), ctypes.byref(n), ctypes.byref(r)))
+        return {"mode": int(m.value), "bytes": int(b.value), "gemv_launches": int(n.value),
+                "rows_launches": int(r.value)}
+
     def set_weight_bf16_rows(self, max_rows: Optional[int] = None, min_bytes: Optional[int] = None) -> None:
         """Extension (l3_set_weight_bf16_rows): with bf16 weight storage on, launches of 2 ..
         ``max_rows`` rows (0: off; at most 64) against a weight of at least ``min_bytes`` bf16 bytes
@@ -941,6 +964,55 @@ class Context:
         check(lib().l3_op_linear_bf16_rows_host(self._h, ptr(x), x.shape[0], x.shape[1], w.shape[0], ptr(w),
                                                 ptr(g) if g is not None else None, float(eps), ptr(y)))
         return y
+
+    def op_to_fp8_rows(self, x: np.ndarray):
+        """(codes uint8 [rows, K], scale float32 [rows], count): the device conversion of
+        l3_set_weight_fp8 (``utils.quant_fp8_rows``'s rule) and how many elements differ from
+        ``scale * float(code)``."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.ndim != 2:
+            raise ValueError(f"x {x.shape} must be [rows, K]")
+        codes = np.empty(x.shape, np.uint8)
+        scale = np.empty(x.shape[0], np.float32)
+        n = ctypes.c_int64(0)
+        check(lib().l3_op_to_fp8_rows_host(self._h, ptr(x), x.shape[0], x.shape[1], ptr(codes), ptr(scale),
+                                           ctypes.byref(n)))
+        return codes, scale, int(n.value)
+
+    def _op_linear_fp8(self, fn, x, codes, scale, norm_w, eps, route):
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        w = np.ascontiguousarray(codes, dtype=np.uint8)
+        s = np.ascontiguousarray(scale, dtype=np.float32)
+        if x.ndim != 2 or w.ndim != 2 or w.shape[1] != x.shape[1]:
+            raise ValueError(f"x {x.shape} and codes {w.shape} must be [rows, K] and [N, K]")
+        if s.shape != (w.shape[0],):
+            raise ValueError(f"scale {s.shape} must be [N = {w.shape[0]}]")
+        g = None if norm_w is None else np.ascontiguousarray(norm_w, dtype=np.float32)
+        if g is not None and g.shape != (x.shape[1],):
+            raise ValueError(f"norm_w {g.shape} must be [K = {x.shape[1]}]")
+        y = np.empty((x.shape[0], w.shape[0]), np.float32)
+        rt = (ctypes.c_int32 * 6)()
+        check(fn(self._h, ptr(x), x.shape[0], x.shape[1], w.shape[0], ptr(w), ptr(s),
+                 ptr(g) if g is not None else None, float(eps), ptr(y), rt))
+        if not route:
+            return y
+        fam = GEMM_FAMILIES[rt[0]]
+        return y, {"family": fam, **dict(zip(_ROUTE_FIELDS[fam], list(rt)[1:]))}
+
+    def op_linear_fp8(self, x: np.ndarray, codes: np.ndarray, scale: np.ndarray,
+                      norm_w: Optional[np.ndarray] = None, eps: float = 0.0, route: bool = False):
+        """``x [rows <= 8, K] @ W_q.T`` with ``W_q[n, k] = scale[n] * e4m3fn(codes[n, k])`` (uint8
+        codes, power-of-two scales), on the GEMV's fp8 form (l3_op_linear_fp8_host); with ``norm_w``
+        the RMSNorm of x (weight norm_w, ``eps``) is applied first.  A shape that kernel does not
+        take, a NaN code or a scale that is no power of two raises.  ``route=True``: also the
+        launch's route report."""
+        return self._op_linear_fp8(lib().l3_op_linear_fp8_host, x, codes, scale, norm_w, eps, route)
+
+    def op_linear_fp8_rows(self, x: np.ndarray, codes: np.ndarray, scale: np.ndarray,
+                           norm_w: Optional[np.ndarray] = None, eps: float = 0.0, route: bool = False):
+        """The same product for ``2 <= rows <= 64`` on the fp8 form of the weight-streaming MFMA
+        kernel of ``set_weight_bf16_rows`` (l3_op_linear_fp8_rows_host), one launch."""
+        return self._op_linear_fp8(lib().l3_op_linear_fp8_rows_host, x, codes, scale, norm_w, eps, route)
 
     def op_linear_logprob(self, x: np.ndarray, w: np.ndarray, targets: np.ndarray):
         """The scoring lm_head on a plain product (l3_op_linear_logprob_host): for the rows of

@@ -52,8 +52,8 @@ _NPZ_READER = os.environ.get("L3_NPZ_READER", "threads")
 
 DEFAULT_DEVICE = int(os.environ.get("LLAMA3_HIP_DEVICE", "0"))
 
-# Llama(..., weight_dtype=...) -> l3_set_weight_bf16 mode
-_WEIGHT_DTYPES = {None: 0, "bf16": 1, "bf16-round": 2}
+# Llama(..., weight_dtype=...) -> l3_set_weight_bf16 mode, or l3_set_weight_fp8 mode
+_WEIGHT_DTYPES = {None: 0, "bf16": 1, "bf16-round": 2, "fp8-e4m3": 1, "fp8-e4m3-round": 2}
 
 
 # ---- module functions (reference llama3.py:22-83) ----------------------------
@@ -302,6 +302,10 @@ class Llama:
         against a large weight (batched and ragged decode, speculative chunks, continuations at the
         Llama-3 shape) stream the bf16 copies too; ``model.context.set_weight_bf16_rows`` moves
         the row and weight-size limits (DESIGN.md "bf16 weight storage for 2-64 rows").
+        ``"fp8-e4m3"`` / ``"fp8-e4m3-round"`` (DESIGN.md "fp8 weight storage") store them as
+        per-row power-of-two scaled OCP e4m3 codes instead, a quarter of the fp32 bytes per token on
+        the same launches: the first needs weights that already equal ``utils.round_fp8_rows`` of
+        themselves (``ValueError`` naming the tensor otherwise), the second rounds them.
 
         ``devices=[0, ..., N-1]``: one process drives N GPUs (``l3hip.Group``, the C ABI's
         l3_group_*).  Every call keeps the reference's signature and result: batch row r runs on
@@ -319,7 +323,8 @@ class Llama:
         if weight_dtype not in _WEIGHT_DTYPES:
             raise ValueError(f"weight_dtype {weight_dtype!r}: expected one of {sorted(map(str, _WEIGHT_DTYPES))}")
         if weight_dtype is not None and devices is not None and len(devices) > 1:
-            raise NotImplementedError("bf16 weight storage on a multi-device model: not implemented")
+            raise NotImplementedError(f"{weight_dtype.split('-')[0]} weight storage on a multi-device model: "
+                                      "not implemented")
         if ragged_split is not None and devices is not None and len(devices) > 1:
             raise NotImplementedError("ragged batches on a multi-device model: not implemented")
         keep = keep_host_weights
@@ -354,7 +359,9 @@ class Llama:
             self._group = None
             self._ctx = l3hip.Context(dims, DEFAULT_DEVICE if device is None else device)
             tgt = self._ctx
-        if weight_dtype is not None:
+        if weight_dtype is not None and weight_dtype.startswith("fp8"):
+            self._ctx.set_weight_fp8(_WEIGHT_DTYPES[weight_dtype])
+        elif weight_dtype is not None:
             self._ctx.set_weight_bf16(_WEIGHT_DTYPES[weight_dtype])
         if ragged_split is not None:
             self._ctx.set_ragged_attn_split(1, int(ragged_split))
@@ -375,7 +382,7 @@ class Llama:
         try:
             tgt.finalize()
         except RuntimeError as e:  # "bf16": a tensor that is not bf16 already (named in the message)
-            if "not bf16-representable" in str(e):
+            if "not bf16-representable" in str(e) or "weight_fp8" in str(e):
                 raise ValueError(str(e)) from None
             raise
         del weight, norm_w

@@ -44,6 +44,51 @@ def round_bf16(a) -> np.ndarray:
     return (bf16_bits(a).astype(np.uint32) << 16).view(np.float32)
 
 
+def fp8_e4m3_table() -> np.ndarray:
+    """The 256 values of OCP ``e4m3fn`` by code (float32): sign, four exponent bits of bias 7, three
+    mantissa bits; exponent 0 holds the subnormals m * 2^-9; 0x7f and 0xff are NaN; no infinities."""
+    c = np.arange(256, dtype=np.int64)
+    e, m = (c >> 3) & 15, c & 7
+    a = np.where(e == 0, m * 2.0 ** -9, (1 + m / 8.0) * 2.0 ** (e - 7.0))
+    a = np.where((c & 0x7F) == 0x7F, np.nan, a)
+    return np.where(c & 0x80, -a, a).astype(np.float32)
+
+
+def quant_fp8_rows(W):
+    """``(codes uint8 [N, K], scale float32 [N])`` of an fp32 matrix: per row n the scale
+    ``s_n = 2^e_n``, the smallest power of two with ``max_k |W[n, k]| / s_n <= 448`` (e_n clamped to
+    [-126, 127]; 1 for an all-zero row), and ``codes[n, k] = e4m3fn(W[n, k] / s_n)``,
+    round-to-nearest-even with subnormals rounded like any value and -0 kept.  Nothing saturates and
+    the NaN codes are never produced.  A non-finite element raises ``ValueError``.  The rule of the
+    library's conversion kernel (l3_set_weight_fp8)."""
+    W = np.ascontiguousarray(W, dtype=np.float32)
+    if W.ndim != 2:
+        raise ValueError(f"W {W.shape} must be [N, K]")
+    if not np.isfinite(W).all():
+        raise ValueError("quant_fp8_rows: W has non-finite elements")
+    amax = np.abs(W).max(axis=1) if W.shape[1] else np.zeros(W.shape[0], np.float32)
+    # amax = m 2^x with m in [0.5, 1), 448 = 0.875 * 2^9
+    m, x = np.frexp(amax.astype(np.float32))
+    e = np.where(m <= np.float32(0.875), x - 9, x - 8)
+    e = np.where(amax == 0, 0, np.clip(e, -126, 127)).astype(np.int32)
+    scale = np.ldexp(np.float32(1), e).astype(np.float32)
+    a = np.abs(W * np.ldexp(np.float32(1), -e).astype(np.float32)[:, None])  # exact: a power of two
+    b = a.view(np.uint32).astype(np.int64)
+    normal = ((b + 0x7FFFF + ((b >> 20) & 1)) >> 20) - (120 << 3)
+    sub = np.rint(a.astype(np.float64) * 512.0).astype(np.int64)  # below 2^-6: m * 2^-9, ties to even
+    codes = np.where(a < np.float32(2.0 ** -6), sub, normal)
+    codes |= (W.view(np.uint32).astype(np.int64) >> 24) & 0x80
+    return codes.astype(np.uint8), scale
+
+
+def round_fp8_rows(W) -> np.ndarray:
+    """fp32 values rounded to per-row scaled fp8 and widened back to fp32 (extension;
+    ``quant_fp8_rows``'s rule): ``scale[n] * table[codes[n, k]]``, an exact fp32 product — the
+    weights a ``Llama(..., weight_dtype="fp8-e4m3-round")`` computes with."""
+    codes, scale = quant_fp8_rows(W)
+    return (fp8_e4m3_table()[codes] * scale[:, None]).astype(np.float32)
+
+
 class StreamingNpz:
     """Extension: the streaming loader's view of an ``.npz``.
 
