@@ -67,11 +67,16 @@ enum l3_weight_kind {
  * since layer 0 gathers its input rows from the embedding table (llama3.py:287 fused into
  * its QKV and O-proj launches); the id is kept so the numbering stays stable.
  * L3_K_EMBED_QKV counts the table lookups that stand in for layer 0's QKV GEMM
- * (l3_set_embed_qkv), so L3_K_QKV stays the GEMM launches' alone. */
+ * (l3_set_embed_qkv), so L3_K_QKV stays the GEMM launches' alone.
+ * L3_K_FFN counts the launches of the fused FFN kernel (l3_set_ffn_fused).  Each of them also adds
+ * one count and 2/3 of its time to L3_K_GATEUP and one count and 1/3 of its time to L3_K_DOWN
+ * (the algorithmic FLOP ratio of the two GEMMs at any shape), so per-launch figures derived from
+ * those two ids are the fused kernel's own; the gateup, down and ffn bits of the l3_kernel_timing
+ * mask each turn its timer on. */
 enum l3_kernel_id {
     L3_K_EMBED = 0, L3_K_QKV = 1, L3_K_ATTN = 2, L3_K_OPROJ = 3, L3_K_GATEUP = 4,
     L3_K_DOWN = 5, L3_K_LMHEAD = 6, L3_K_ARGMAX = 7, L3_K_GATHER = 8, L3_K_EMBED_QKV = 9,
-    L3_K_COUNT = 10
+    L3_K_FFN = 10, L3_K_COUNT = 11
 };
 
 /* ---- errors / devices ---------------------------------------------------- */
@@ -238,6 +243,16 @@ int l3_weight_fp8_info(l3_ctx* ctx, int32_t* mode, int64_t* bytes, int64_t* gemv
  * on == 0, or a limit below an existing table's size, frees the table.  Its launches count under
  * L3_K_EMBED_QKV. */
 int l3_set_embed_qkv(l3_ctx* ctx, int32_t on, int64_t max_bytes);
+/* A block's FFN as one launch (extension; default on, env L3_FFN_FUSED=0 turns it off for new
+ * contexts).  Wherever the gate|up and down GEMMs of a block would both run as the tiled fp32
+ * kernel — more than 256 rows per batch part, dim 288, fp32 weights (l3_set_gemm_x6,
+ * l3_set_weight_bf16 and l3_set_weight_fp8 off): a model forward, score, ragged prefill or extend —
+ * one kernel keeps each row's residual panel and SwiGLU output in registers and streams the
+ * weights through LDS, so the hidden activations are never written to memory.  Every sum runs in
+ * the order of the two launches: logits and the residual stream are bit-identical.  Everything
+ * else (the pruned last block's B-row GEMMs, decode, other dims) runs the two launches as before.
+ * Its launches count under L3_K_FFN (see l3_kernel_id). */
+int l3_set_ffn_fused(l3_ctx* ctx, int32_t on);
 /* Same with device-resident ids (int32 [B, L]) and logits ([B, VS]); async. */
 int l3_forward_dev(l3_ctx* ctx, const int32_t* ids_dev, int32_t B, int32_t L,
                    int32_t start_pos, float* logits_dev);
@@ -511,6 +526,15 @@ int l3_op_attn_extend_ragged_host(l3_ctx* ctx, const float* qkv, float* cache_k,
 /* FeedForward.__call__ (llama3.py:97-103): x [rows, D], W as stored. */
 int l3_op_ffn_host(l3_ctx* ctx, const float* x, int64_t rows, int32_t dim, int32_t hidden,
                    const float* w_gate, const float* w_up, const float* w_down, float* y);
+/* One block's FFN with its RMSNorm factor and residual (llama3.py:256-259 without the norm
+ * weight): y = x + down(SwiGLU(f(x) * x @ Wgu^T)), f(x) = 1 / sqrt(mean(x^2) + eps) per row when
+ * norm != 0 (eps: the context's norm_eps), else 1; more than 256 rows, hidden % 16 == 0.
+ * fused != 0: the fused kernel of l3_set_ffn_fused, an error if it does not take the shape (dim
+ * 288) — the two launches never stand in.  fused == 0: the two tiled fp32 launches (a hidden of
+ * 16 mod 32 is padded with 16 zero units, which add exact zeros to every sum). */
+int l3_op_ffn_block_host(l3_ctx* ctx, const float* x, int64_t rows, int32_t dim, int32_t hidden,
+                         const float* w_gate, const float* w_up, const float* w_down, int32_t norm,
+                         int32_t fused, float* y);
 /* y [rows, N] = x [rows, K] @ W[N, K]^T (the reference's `x @ W.T`). */
 int l3_op_linear_host(l3_ctx* ctx, const float* x, int64_t rows, int32_t K, int32_t N,
                       const float* w, float* y);

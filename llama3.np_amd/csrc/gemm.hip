@@ -5,6 +5,7 @@
 #include "gemm_kernel.h"
 #include "gemm_x6.h"
 #include "embed_qkv.h"
+#include "ffn_fused.h"
 
 namespace l3 {
 
@@ -525,6 +526,44 @@ hipError_t launch_embed_qkv(const EmbedQkvArgs& a, hipStream_t s) {
     if (nq <= 64) return launch_embed_qkv_cpb<64>(a, nq, s);
     if (nq <= 128) return launch_embed_qkv_cpb<128>(a, nq, s);
     return launch_embed_qkv_cpb<256>(a, nq, s);
+}
+
+// The fused FFN (ffn_fused.h).  More than 64 KB of dynamic LDS needs the function attribute, set
+// once per device and instantiation.
+template <int NW, int TM, bool SPLIT>
+static hipError_t launch_ffn_cfg(const FfnArgs& a, hipStream_t s) {
+    constexpr int KD = 18;
+    constexpr int lds = ffn_fused_lds_bytes<KD, SPLIT>();
+    auto* kern = ffn_fused_kernel<KD, NW, TM, SPLIT>;
+    static bool attr_set[64] = {};
+    int dev = 0;
+    if (const hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
+    if (dev < 0 || dev >= 64 || !attr_set[dev]) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (e != hipSuccess) return e;
+        if (dev >= 0 && dev < 64) attr_set[dev] = true;
+    }
+    constexpr int BM = NW * TM * 16;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((a.M + BM - 1) / BM)), dim3(64 * NW), lds, s, a);
+    return hipGetLastError();
+}
+
+bool ffn_fused_takes(int64_t M, int D, int FD) { return M > 256 && M <= INT32_MAX && D == 288 && FD >= 16 && FD % 16 == 0; }
+
+// Block shape and staging (DESIGN.md "Fused FFN", interleaved A/B of the C3 step): eight waves x 16
+// rows with wgu and wd staged separately.  L3_FFN_CFG re-runs the A/B (every configuration gives the
+// same bits): 1 the same block with a whole group per stage (+0.4 % step time), 2 four waves x 16
+// rows staged separately, two blocks per CU (+0.8 %).  Waves of 32 rows (TM = 2, 256 VGPRs + 162
+// AGPRs, one wave per SIMD) measured +3.7 % with either staging and are not instantiated.
+hipError_t launch_ffn_fused(const FfnArgs& a, hipStream_t s) {
+    if (!ffn_fused_takes(a.M, a.D, a.FD) || !a.h || !a.wgu || !a.wd) return hipErrorInvalidValue;
+    static const int cfg = env_knob("L3_FFN_CFG", 0);
+    switch (cfg) {
+        case 1: return launch_ffn_cfg<8, 1, false>(a, s);
+        case 2: return launch_ffn_cfg<4, 1, true>(a, s);
+        default: return launch_ffn_cfg<8, 1, true>(a, s);
+    }
 }
 
 hipError_t dcheck_collect_gemm(unsigned* out) { return dcheck_collect(out); }

@@ -13,6 +13,7 @@ namespace l3 {
 //                L3_DECODE_GRAPH (1), L3_COMM_MODE (1), L3_COMM_PRIORITY (1), L3_GROUP_MULTI_PATH (0),
 //                L3_DECODE_PERSIST (1 persistent step; 0 graph), L3_DECODE_ROWS_AMAX (1),
 //                L3_EMBED_QKV (1 layer-0 QKV of a prefill from the table; 0 its GEMM),
+//                L3_FFN_FUSED (1 gate|up + down of a prefill past 256 rows as one launch; 0 the two GEMMs),
 //                L3_SPEC_SKINNY (1 speculative chunks of 2 .. 8 rows on the skinny MFMA kernel; 0 launch_gemm's choice)
 //   test knobs   L3_DECODE_PERSIST_MAX_CUS (cap the CUs the persistent step sees), L3_DECODE_PERSIST_FAULT
 //                (a workgroup gives up in the step at that position; L3_DECODE_PERSIST_FAULT_WG which),
@@ -20,7 +21,8 @@ namespace l3 {
 //                L3_DECODE_PERSIST_STAMPS=<file> (diagnostic timeline, tools/persist_stamps.py)
 //   gemm.hip     L3_SPLITK (1), L3_SPLITK_CFG (0), L3_SPLITK_BLOCKS (1024), L3_SPLITK_MINKT (8),
 //                L3_GEMV_NT (1), L3_GEMV_LPU (0 = by shape), L3_GEMV_MR (by shape), L3_SKINNY (1),
-//                L3_SKINNY_MIN (9), L3_SKINNY_CH (2), L3_SKINNY_TN2_MIN (256), L3_GEMM_GROUP_M (8)
+//                L3_SKINNY_MIN (9), L3_SKINNY_CH (2), L3_SKINNY_TN2_MIN (256), L3_GEMM_GROUP_M (8),
+//                L3_FFN_CFG (the fused FFN's block shape and staging, launch_ffn_fused)
 inline int env_knob(const char* name, int def) {
     const char* e = getenv(name);
     return e && *e ? atoi(e) : def;
@@ -610,6 +612,22 @@ int decode_persist_grid(const DecodePersistArgs& a);
 hipError_t launch_decode_persist(const DecodePersistArgs& a, int grid, hipStream_t s);
 
 hipError_t launch_gemm(int epi, const GemmArgs& a, hipStream_t s);
+
+// The FFN of a block as one launch (ffn_fused.h; DESIGN.md "Fused FFN"): h += down(SwiGLU(
+// rowfactor(h) * h * Wgu^T)), bit for bit what the tiled fp32 gate|up and down launches give
+struct FfnArgs {
+    float* h;          // [M, D] residual stream, updated in place
+    const float* wgu;  // [2 FD, D] gate / up interleaved by 16 rows, RMSNorm weight folded
+    const float* wd;   // [D, FD]
+    int M, D, FD;
+    bool norm;
+    float eps;
+};
+// the shapes the kernel is built for: more than 256 rows (where launch_gemm reaches the tiled
+// kernel for both GEMMs), D = 288, FD a multiple of 16
+bool ffn_fused_takes(int64_t M, int D, int FD);
+// hipErrorInvalidValue for any other shape: nothing else stands in
+hipError_t launch_ffn_fused(const FfnArgs& a, hipStream_t s);
 
 // Layer 0's QKV as a table lookup (embed_qkv.h; DESIGN.md "Layer-0 QKV table"): row r of that
 // GEMM before the rotation depends on the token id and the weights only, so a prefill gathers it

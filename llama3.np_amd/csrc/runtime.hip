@@ -138,6 +138,9 @@ struct l3_ctx {
     // stream, if its bytes fit embed_qkv_cap; a refused allocation is not retried
     static constexpr int64_t EMBED_QKV_CAP_DEFAULT = (int64_t)256 << 20;
     bool embed_qkv = true;
+    // gate|up + down of a block past 256 rows as one launch (ffn_fused.h, l3_set_ffn_fused,
+    // L3_FFN_FUSED): bit-identical to the two tiled launches
+    bool ffn_fused = true;
     int64_t embed_qkv_cap = EMBED_QKV_CAP_DEFAULT;
     float* embed_tab = nullptr;      // [vocab_size, qkvn]
     bool embed_tab_failed = false;
@@ -345,7 +348,9 @@ static int spec_resolve(l3_ctx* c);  // undo of a speculative decode step (below
 template <typename F>
 static int timed_on(l3_ctx* c, int kind, hipStream_t s, F&& launch) {
     Timer* t = nullptr;
-    if (c->timing && (c->timing_mask >> kind & 1u)) {
+    // a fused FFN launch (L3_K_FFN) is timed when any of the gateup, down or ffn bits asks
+    const unsigned bits = kind == L3_K_FFN ? 1u << L3_K_FFN | 1u << L3_K_GATEUP | 1u << L3_K_DOWN : 1u << kind;
+    if (c->timing && (c->timing_mask & bits)) {
         if (c->timer_used == c->timers.size()) {
             Timer nt{};
             HIP_TRY(hipEventCreate(&nt.a));
@@ -375,6 +380,14 @@ static int harvest_timers(l3_ctx* c) {
         HIP_TRY(hipEventElapsedTime(&ms, c->timers[i].a, c->timers[i].b));
         c->tot_ms[c->timers[i].kind] += ms;
         c->cnt[c->timers[i].kind] += 1;
+        if (c->timers[i].kind == L3_K_FFN) {
+            // also as a gate|up and a down launch, split 2 : 1 — the algorithmic FLOP ratio at any
+            // shape — so the rates read from those two entries are the fused kernel's own
+            c->tot_ms[L3_K_GATEUP] += (double)ms * 2.0 / 3.0;
+            c->tot_ms[L3_K_DOWN] += (double)ms / 3.0;
+            c->cnt[L3_K_GATEUP] += 1;
+            c->cnt[L3_K_DOWN] += 1;
+        }
     }
     c->timer_used = 0;
     return 0;
@@ -530,6 +543,7 @@ extern "C" int l3_create(int32_t device, const l3_dims* dims, l3_ctx** out) {
         }
     }
     c->embed_qkv = env_knob("L3_EMBED_QKV", 1) != 0;
+    c->ffn_fused = env_knob("L3_FFN_FUSED", 1) != 0;
     {  // split-KV ragged decode attention defaults for new contexts (values out of range: ignored)
         c->rag_split_mode = env_knob("L3_RAGGED_SPLIT", 0) == 1 ? 1 : 0;
         const int ch = env_knob("L3_RAGGED_SPLIT_CHUNK", 0);
@@ -818,6 +832,12 @@ static bool embed_table(l3_ctx* c, bool may_build) {
 
 // the launches that read the table are all ordered before the end of c->stream's queue (a batch
 // split's parts are joined there), so the table is freed after a synchronize
+extern "C" int l3_set_ffn_fused(l3_ctx* c, int32_t on) {
+    CHECK_CTX(c);
+    c->ffn_fused = on != 0;
+    return 0;
+}
+
 extern "C" int l3_set_embed_qkv(l3_ctx* c, int32_t on, int64_t max_bytes) {
     CHECK_CTX(c);
     if (set_dev(c)) return 1;
@@ -881,6 +901,35 @@ static hipError_t gemm(l3_ctx* c, int epi, const GemmArgs& g_in, hipStream_t s) 
     else if (gemm_takes_fp8_rows(epi, g)) c->wq_rows_launches += 1;
     else if (gemm_takes_fp8(epi, g)) c->wq_launches += 1;
     return launch_gemm(epi, g, s);
+}
+
+// gate|up + SwiGLU, then down + residual, of one block: the fused kernel (ffn_fused.h) exactly
+// when both launches would reach the tiled fp32 gemm_lds_kernel without split-K — more than 256
+// rows of fp32 weights (no x6 pieces, no bf16 / fp8 storage), none of the decode, gather or
+// partial-row arguments, down reading gate|up's output and adding into gate|up's input in place,
+// D = 288 — else the two launches as ever.  Bit-identical either way.
+static bool ffn_fused_ok(const l3_ctx* c, const GemmArgs& gu, const GemmArgs& dn) {
+    if (!c->ffn_fused || gu.M != dn.M || !ffn_fused_takes(gu.M, gu.K, dn.K)) return false;
+    if (gu.N != 2 * dn.K || dn.N != gu.K || dn.K % 32 != 0) return false;
+    if (gu.W3 || dn.W3 || gu.Wb || dn.Wb || gu.Wq || dn.Wq) return false;
+    if (gu.parts || dn.parts || gu.x_out || gu.a_rows || dn.a_rows || gu.res_src || dn.res_src || dn.res_rows)
+        return false;
+    if (gu.amax_part || dn.amax_part || gu.amax_rows || dn.amax_rows || gu.amax_in || dn.amax_in || gu.lse_rows ||
+        dn.lse_rows || gu.pos_dev || dn.pos_dev || gu.pos_adv || dn.pos_adv || gu.kv_bak || dn.kv_bak)
+        return false;
+    if (gu.force_skinny || dn.force_skinny || gu.force_tiled || dn.force_tiled) return false;
+    return gu.lda == gu.K && gu.ldc == dn.K && dn.lda == dn.K && dn.ldc == gu.K && gu.C == dn.A && dn.C == gu.A &&
+           gu.C && dn.C;
+}
+static int ffn_pair(l3_ctx* c, const GemmArgs& gu, const GemmArgs& dn, hipStream_t s) {
+    if (ffn_fused_ok(c, gu, dn)) {
+        FfnArgs f{};
+        f.h = dn.C; f.wgu = gu.W; f.wd = dn.W;
+        f.M = gu.M; f.D = gu.K; f.FD = dn.K; f.norm = gu.norm; f.eps = gu.eps;
+        return timed_on(c, L3_K_FFN, s, [&] { return launch_ffn_fused(f, s); });
+    }
+    if (timed_on(c, L3_K_GATEUP, s, [&] { return gemm(c, EPI_SWIGLU, gu, s); })) return 1;
+    return timed_on(c, L3_K_DOWN, s, [&] { return gemm(c, EPI_RESID, dn, s); });
 }
 
 // ---- fp8 weight storage (DESIGN.md "fp8 weight storage") --------------------------------------
@@ -1308,9 +1357,7 @@ static int run_layer(l3_ctx* c, int li, int B, int L, int start_pos, const int* 
         if (emb_ids) { o.res_src = c->emb; o.res_rows = emb_ids; }  // h = emb[ids] + attn . Wo^T
         if (timed_on(c, L3_K_OPROJ, s, [&] { return gemm(c, EPI_RESID, o, s); })) return 1;
     }
-    if (timed_on(c, L3_K_GATEUP, s, [&] { return gemm(c, EPI_SWIGLU, gu, s); })) return 1;
-    if (timed_on(c, L3_K_DOWN, s, [&] { return gemm(c, EPI_RESID, dn, s); })) return 1;
-    return 0;
+    return ffn_pair(c, gu, dn, s);
 }
 
 // final RMSNorm + lm_head on the last position of rows [b0, b0 + B) (llama3.py:304-307)
@@ -2500,8 +2547,7 @@ static int ragged_step(l3_ctx* c, int B, int s_cap, int chunk) {
         dn.A = c->hid; dn.lda = FD; dn.W = Ly.wd; dn.Wb = Ly.wdb; dn.Wq = Ly.wdq; dn.wq_scale = Ly.wds; dn.C = c->h; dn.ldc = D;
         dn.M = B; dn.N = D; dn.K = FD; dn.norm = false;
         gu.ws = dn.ws = c->skws; gu.ws_cap = dn.ws_cap = c->skws_cap;
-        if (timed(c, L3_K_GATEUP, [&] { return gemm(c, EPI_SWIGLU, gu, s); })) return 1;
-        if (timed(c, L3_K_DOWN, [&] { return gemm(c, EPI_RESID, dn, s); })) return 1;
+        if (ffn_pair(c, gu, dn, s)) return 1;
     }
     const GemmArgs lm = lm_head_args(c, B, 1, c->logits, 0);
     return timed(c, L3_K_LMHEAD, [&] { return gemm(c, EPI_STORE, lm, s); });
@@ -2644,8 +2690,7 @@ static int ragged_extend_layers(l3_ctx* c, int B, int Lmax, bool skinny) {
         dn.M = T; dn.N = D; dn.K = FD; dn.norm = false;
         gu.ws = dn.ws = c->skws; gu.ws_cap = dn.ws_cap = c->skws_cap;
         gu.force_skinny = dn.force_skinny = skinny;
-        if (timed(c, L3_K_GATEUP, [&] { return gemm(c, EPI_SWIGLU, gu, s); })) return 1;
-        if (timed(c, L3_K_DOWN, [&] { return gemm(c, EPI_RESID, dn, s); })) return 1;
+        if (ffn_pair(c, gu, dn, s)) return 1;
     }
     return 0;
 }
@@ -3660,6 +3705,63 @@ extern "C" int l3_op_ffn_host(l3_ctx* c, const float* x, int64_t rows, int32_t d
     HIP_TRY(hipMemsetAsync(dy, 0, rows * dim * 4, c->stream));
     if (op_linear(c, EPI_RESID, dh, rows, hidden, dim, dd, dy, false)) return 1;
     D2H(y, dy, rows * dim);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// One FFN block on host arrays: y = x + down(SwiGLU(rowfactor(x) * x * Wgu^T)), rowfactor the
+// RMSNorm factor (norm) or 1.  fused: the fused kernel (ffn_fused.h), an error where it does not
+// take the shape — the pair never stands in; else the two tiled fp32 launches (more than 256 rows,
+// so launch_gemm reaches gemm_lds_kernel for both).  The pair needs whole 32-deep k-tiles of
+// hidden: a hidden of 16 mod 32 runs it with 16 zero hidden units appended (zero gate / up rows
+// and zero down columns), which add exact zeros at the end of every down sum.
+extern "C" int l3_op_ffn_block_host(l3_ctx* c, const float* x, int64_t rows, int32_t dim, int32_t hidden,
+                                    const float* w_gate, const float* w_up, const float* w_down, int32_t norm,
+                                    int32_t fused, float* y) {
+    CHECK_CTX(c);
+    const char* who = "l3_op_ffn_block";
+    if (!x || !w_gate || !w_up || !w_down || !y) return fail("%s: null argument", who);
+    if (rows <= 256 || rows > INT32_MAX / 4096) return fail("%s: %lld rows: the tiled kernels take more than 256", who, (long long)rows);
+    if (dim <= 0 || dim % 32 || hidden <= 0 || hidden % 16) return fail("%s: dim %d must be a multiple of 32 and hidden %d of 16", who, dim, hidden);
+    if (fused && !ffn_fused_takes(rows, dim, hidden))
+        return fail("%s: the fused kernel does not take %lld x %d x %d", who, (long long)rows, dim, hidden);
+    if (set_dev(c)) return 1;
+    const int32_t hp = fused ? hidden : (hidden + 31) / 32 * 32;  // the pair's hidden
+    Scratch S{c};
+    SCRATCH(dx, rows * dim);
+    SCRATCH(dgu, 2LL * hp * dim);
+    SCRATCH(dd, (int64_t)dim * hp);
+    SCRATCH(dh, rows * hp);
+    H2D(dx, x, rows * dim);
+    if (hp != hidden) {
+        HIP_TRY(hipMemsetAsync(dgu, 0, 2LL * hp * dim * 4, c->stream));
+        HIP_TRY(hipMemsetAsync(dd, 0, (int64_t)dim * hp * 4, c->stream));
+    }
+    HIP_TRY(hipMemcpy2DAsync(dgu, 32LL * dim * 4, w_gate, 16LL * dim * 4, 16LL * dim * 4, hidden / 16,
+                             hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpy2DAsync(dgu + 16LL * dim, 32LL * dim * 4, w_up, 16LL * dim * 4, 16LL * dim * 4,
+                             hidden / 16, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpy2DAsync(dd, (size_t)hp * 4, w_down, (size_t)hidden * 4, (size_t)hidden * 4, dim,
+                             hipMemcpyHostToDevice, c->stream));
+    if (fused) {
+        FfnArgs f{};
+        f.h = dx; f.wgu = dgu; f.wd = dd; f.M = (int)rows; f.D = dim; f.FD = hidden; f.norm = norm != 0;
+        f.eps = c->d.norm_eps;
+        HIP_TRY(launch_ffn_fused(f, c->stream));
+    } else {
+        GemmArgs gu{};
+        gu.A = dx; gu.lda = dim; gu.W = dgu; gu.C = dh; gu.ldc = hp;
+        gu.M = (int)rows; gu.N = 2 * hp; gu.K = dim; gu.norm = norm != 0; gu.eps = c->d.norm_eps;
+        GemmArgs dn{};
+        dn.A = dh; dn.lda = hp; dn.W = dd; dn.C = dx; dn.ldc = dim;
+        dn.M = (int)rows; dn.N = dim; dn.K = hp; dn.norm = false;
+        gemm_route_reset();
+        HIP_TRY(launch_gemm(EPI_SWIGLU, gu, c->stream));
+        if (gemm_last_route().family != ROUTE_TILED) return fail("%s: gate|up did not take the tiled kernel", who);
+        HIP_TRY(launch_gemm(EPI_RESID, dn, c->stream));
+        if (gemm_last_route().family != ROUTE_TILED) return fail("%s: down did not take the tiled kernel", who);
+    }
+    D2H(y, dx, rows * dim);
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }

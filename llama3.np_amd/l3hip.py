@@ -23,7 +23,7 @@ HEADER = os.path.join(os.path.dirname(HERE), "include", "llama3hip.h")
 # weight kinds / kernel ids (mirror the enums in include/llama3hip.h)
 W_EMBED, W_Q, W_K, W_V, W_O, W_GATE, W_UP, W_DOWN = range(8)
 W_ATTN_NORM, W_FFN_NORM, W_FINAL_NORM, W_LM_HEAD = 8, 9, 10, 11
-KERNELS = ["embed", "qkv", "attn", "oproj", "gateup", "down", "lmhead", "argmax", "gather", "embed_qkv"]
+KERNELS = ["embed", "qkv", "attn", "oproj", "gateup", "down", "lmhead", "argmax", "gather", "embed_qkv", "ffn"]
 
 
 class Dims(ctypes.Structure):
@@ -102,6 +102,8 @@ _SIGNATURES = {
     "l3_set_batch_split": (ctypes.c_int, [_P, _I32, _I64]),
     "l3_set_gemm_x6": (ctypes.c_int, [_P, _I32]),
     "l3_set_embed_qkv": (ctypes.c_int, [_P, _I32, _I64]),
+    "l3_set_ffn_fused": (ctypes.c_int, [_P, _I32]),
+    "l3_op_ffn_block_host": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _P, _P, _P, _I32, _I32, _P]),
     "l3_set_weight_bf16": (ctypes.c_int, [_P, _I32]),
     "l3_weight_bf16_info": (ctypes.c_int, [_P, _P, _P, _P]),
     "l3_set_weight_bf16_rows": (ctypes.c_int, [_P, _I32, _I64]),
@@ -708,6 +710,12 @@ class Context:
         table is built at first use if it fits max_bytes (0 keeps the limit, 256 MB by default)."""
         check(lib().l3_set_embed_qkv(self._h, int(bool(on)), int(max_bytes)))
 
+    def set_ffn_fused(self, on: bool) -> None:
+        """Extension (l3_set_ffn_fused): gate|up + down of a block past 256 rows (dim 288, fp32
+        weights) as one launch that keeps the hidden activations in registers (bit-identical to
+        the two GEMMs; on by default)."""
+        check(lib().l3_set_ffn_fused(self._h, int(bool(on))))
+
     def set_weight_bf16(self, mode: int) -> None:
         """Extension (l3_set_weight_bf16): bf16 storage of the projections and the lm_head for the
         weight-streaming decode GEMVs — 0 off, 1 exact (every element must be a bf16 value, else
@@ -1131,6 +1139,20 @@ class Context:
             route[name] = int(op.route[1 + i])
         out["route"] = route
         return out
+
+    def op_ffn_block(self, x: np.ndarray, wg: np.ndarray, wu: np.ndarray, wd: np.ndarray, norm: bool,
+                     fused: bool) -> np.ndarray:
+        """Extension (l3_op_ffn_block_host): x + down(SwiGLU(f(x) * x @ Wgu.T)) over more than 256
+        rows, f the RMSNorm row factor (norm) or 1, on the fused kernel (an error where it does
+        not take the shape) or on the two tiled fp32 launches."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        D = x.shape[-1]
+        FD = wg.shape[0]
+        y = np.empty_like(x)
+        wg, wu, wd = (np.ascontiguousarray(a, dtype=np.float32) for a in (wg, wu, wd))
+        check(lib().l3_op_ffn_block_host(self._h, ptr(x), x.size // D, D, FD, ptr(wg), ptr(wu), ptr(wd),
+                                         int(bool(norm)), int(bool(fused)), ptr(y)))
+        return y
 
     def op_ffn(self, x: np.ndarray, wg: np.ndarray, wu: np.ndarray, wd: np.ndarray) -> np.ndarray:
         x = np.ascontiguousarray(x, dtype=np.float32)

@@ -33,6 +33,8 @@ def flops(name, T):
             return ("O-proj (+residual)", 2.0 * T * D * D) if oproj else ("down (+residual)", 2.0 * T * FD * D)
         if epi == 0:
             return "lm_head (+final RMSNorm, last row)", 2.0 * (T // L) * D * VS
+    if "ffn_fused_kernel" in name:
+        return "fused FFN (gate|up, SwiGLU, down, +residual)", 2.0 * T * D * 3 * FD
     if "attn_fwd_kernel" in name:
         return "causal attention (useful half)", 2.0 * 2 * H * HD * L * (L + 1) / 2 * (T // L)
     return name.split("(")[0], None
