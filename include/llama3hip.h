@@ -90,6 +90,21 @@ const char* l3_source_hash(void);
 /* ---- context (replaces Llama.__init__, llama3.py:265-283) ---------------- */
 /* n_layers may be 0 (op-only context); ctx owns all device memory. */
 int l3_create(int32_t device, const l3_dims* dims, l3_ctx** out);
+/* l3_create with a KV-cache storage type (extension; DESIGN.md "bf16 KV-cache storage"), fixed for
+ * the context's life.  L3_KV_F32: l3_create exactly.  L3_KV_BF16: every layer's K and V cache is
+ * allocated at two bytes per element (no fp32 allocation is made first); K (after RoPE) and V are
+ * rounded to bf16, round-to-nearest-even, as they enter their slot, and widened in registers by
+ * the kernels that read them — queries, scores, softmax and P.V stay fp32, and a step's own token
+ * is used as rounded.  Such a context serves the ragged entry points (l3_ragged_*,
+ * l3_cache_copy_rows, l3_reset_cache); every entry point whose kernels read or write an fp32 cache
+ * (l3_forward_*, l3_greedy_*, l3_score_host, l3_layer_forward_host, l3_attention_forward_host)
+ * returns an error naming kv_dtype before it allocates or launches anything.  An l3_group's
+ * members are fp32 contexts.  Errors: as l3_create; any other kv_dtype. */
+enum l3_kv_dtype { L3_KV_F32 = 0, L3_KV_BF16 = 1 };
+int l3_create_kv(int32_t device, const l3_dims* dims, int32_t kv_dtype, l3_ctx** out);
+/* The context's KV-cache storage type and the bytes of all layers' K and V allocations (either
+ * pointer may be NULL). */
+int l3_kv_info(l3_ctx* ctx, int32_t* dtype, int64_t* bytes);
 int l3_destroy(l3_ctx* ctx);
 /* Upload one tensor (host fp32, [rows, cols] row-major).  layer is ignored for
  * EMBED/FINAL_NORM/LM_HEAD.  Replaces the weight.get(...) calls of
@@ -411,6 +426,13 @@ int l3_ragged_generate_from_host(l3_ctx* ctx, const int64_t* ids_host, const int
  * [0, max_batch_size), src_row among dst_rows, n_dst > max_batch_size, n_slots outside
  * [0, max_seq_len], a member of a multi-device l3_group. */
 int l3_cache_copy_rows(l3_ctx* ctx, int32_t src_row, const int32_t* dst_rows, int32_t n_dst, int32_t n_slots);
+/* Slots [slot0, slot0 + n_slots) of cache row `row` of one layer, read to the host after the
+ * context's queued work: k_out and v_out are [n_kv_heads, n_slots, head_dim] fp32 — the stored
+ * floats of an fp32 cache, the stored bf16 values widened exactly of a bf16 one.  The cache is not
+ * changed (there is no write direction).  Errors: a layer, row or slot range outside the context's,
+ * a null output. */
+int l3_cache_read_host(l3_ctx* ctx, int32_t layer, int32_t row, int32_t slot0, int32_t n_slots, float* k_out,
+                       float* v_out);
 
 /* ---- speculative decoding with lookup drafts (extension; DESIGN.md "Speculative decoding") ---- */
 /* l3_ragged_generate_host (starts NULL) or l3_ragged_generate_from_host (starts given) with the
@@ -523,6 +545,19 @@ int l3_op_attn_extend_ragged_host(l3_ctx* ctx, const float* qkv, float* cache_k,
                                   const float* rope_cos, const float* rope_sin, const int32_t* starts,
                                   const int32_t* lens, int32_t B, int32_t Lq, int32_t H, int32_t KVH,
                                   int32_t HD, int32_t Smax, float* out);
+/* The two ops above with the caches' element type (enum l3_kv_dtype): L3_KV_F32, caches of float
+ * — the calls above; L3_KV_BF16, caches of uint16 bf16 bit patterns, copied in and back out as
+ * such: the appended K (after RoPE) and V are rounded to bf16 (round-to-nearest-even), every cached
+ * key / value is widened in registers, and the decode kernels use the step's own key / value as
+ * rounded.  Everything else as above.  Errors: as above; any other kv_dtype. */
+int l3_op_attn_decode_ragged_kv_host(l3_ctx* ctx, const float* qkv, void* cache_k, void* cache_v, int32_t kv_dtype,
+                                     const float* rope_cos, const float* rope_sin, const int32_t* pos,
+                                     const int32_t* finished, int32_t B, int32_t H, int32_t KVH, int32_t HD,
+                                     int32_t Smax, int32_t s_cap, int32_t split, float* out);
+int l3_op_attn_extend_ragged_kv_host(l3_ctx* ctx, const float* qkv, void* cache_k, void* cache_v, int32_t kv_dtype,
+                                     const float* rope_cos, const float* rope_sin, const int32_t* starts,
+                                     const int32_t* lens, int32_t B, int32_t Lq, int32_t H, int32_t KVH,
+                                     int32_t HD, int32_t Smax, float* out);
 /* FeedForward.__call__ (llama3.py:97-103): x [rows, D], W as stored. */
 int l3_op_ffn_host(l3_ctx* ctx, const float* x, int64_t rows, int32_t dim, int32_t hidden,
                    const float* w_gate, const float* w_up, const float* w_down, float* y);

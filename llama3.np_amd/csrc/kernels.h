@@ -458,10 +458,28 @@ struct RaggedState {
     int n_stop;
     int32_t* live;         // [1] rows still running after the last ragged_advance_kernel
 };
+// KV-cache storage (DESIGN.md "bf16 KV-cache storage"): the element type of the cache pointers of
+// RaggedAttnArgs / ExtendAttnArgs and of the cache helpers below (the codes of l3_create_kv).
+// KV_BF16: K (after RoPE) and V are rounded once, as they enter their slot (kv_bf16_rne), stored as
+// unsigned short and widened in registers by the kernels that read them; arithmetic stays fp32.
+enum KvDtype : int { KV_F32 = 0, KV_BF16 = 1 };
+inline bool kv_dtype_ok(int dt) { return dt == KV_F32 || dt == KV_BF16; }
+inline int kv_elem_bytes(int dt) { return dt == KV_BF16 ? 2 : 4; }
+// fp32 -> bf16 bits, round-to-nearest-even on the top 16 bits (misc.hip bf16_rne and utils.bf16_bits
+// on finite values; NaN / Inf are unspecified here)
+__device__ __forceinline__ unsigned kv_bf16_rne(float x) {
+    const unsigned u = __float_as_uint(x);
+    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+}
+// the two bf16 values of a 32-bit word, widened exactly: element 2i in the low half
+__device__ __forceinline__ float kv_bf16_lo(unsigned w) { return __uint_as_float(w << 16); }
+__device__ __forceinline__ float kv_bf16_hi(unsigned w) { return __uint_as_float(w & 0xffff0000u); }
+
 struct RaggedAttnArgs {
     const float* qkv;      // [B, (H + 2 KVH) * HD] the step's raw [q | k | v] rows (no RoPE, no scale)
-    float* cache_k;        // [maxB, KVH, Smax, HD]; slot pos[b] of row b is appended
-    float* cache_v;
+    void* cache_k;         // [maxB, KVH, Smax, HD] of kv_dtype's element; slot pos[b] of row b is appended
+    void* cache_v;
+    int kv_dtype;          // KvDtype (0, the zero-initialised default: fp32)
     float* out;            // [B, H * HD]
     const float* rope_cos; const float* rope_sin;  // [Smax, HD/2]
     const int32_t* pos;    // RaggedState::pos
@@ -493,9 +511,9 @@ inline int64_t attn_decode_split_ws_floats(int64_t B, int H, int HD, int n_split
 }
 // two launches on s: the chunk kernel on grid (n_split, KVH, B), then the combine on (H, B)
 hipError_t launch_attn_decode_ragged_split(const RaggedAttnArgs& a, hipStream_t s);
-// cache[b][h][len[b] .. Lmax) = 0 for b < B, h < KVH, in both caches
-hipError_t launch_ragged_zero_tail(float* cache_k, float* cache_v, const int32_t* len, int B, int KVH, int Smax,
-                                   int HD, int Lmax, hipStream_t s);
+// cache[b][h][len[b] .. Lmax) = 0 for b < B, h < KVH, in both caches (elements of kv_dtype; +0 in both)
+hipError_t launch_ragged_zero_tail(void* cache_k, void* cache_v, int kv_dtype, const int32_t* len, int B, int KVH,
+                                   int Smax, int HD, int Lmax, hipStream_t s);
 // u[b] = the sampling uniform of (seed, b, pos[b])
 hipError_t launch_ragged_uniform(const SampleParams* prm, const int32_t* pos, float* u, int B, hipStream_t s);
 // end of a step: tok[b] recorded, stop / budget, position advance (ragged.hip)
@@ -506,8 +524,9 @@ hipError_t dcheck_collect_ragged(unsigned* out);
 // tokens sit at positions [starts[b], starts[b] + lens[b]) and attend to that row's cache
 struct ExtendAttnArgs {
     const float* qkv;      // [B, Lq, (H + 2 KVH) * HD] raw [q | k | v] rows (no RoPE, no scale); pads never read
-    float* cache_k;        // [maxB, KVH, Smax, HD]; slots [starts[b], starts[b] + lens[b]) of row b are written
-    float* cache_v;
+    void* cache_k;         // [maxB, KVH, Smax, HD] of kv_dtype's element; slots [starts[b], starts[b] + lens[b])
+    void* cache_v;         //   of row b are written
+    int kv_dtype;          // KvDtype (0, the zero-initialised default: fp32)
     float* out;            // [B, Lq, H * HD]; pad rows get zeros
     const float* rope_cos; const float* rope_sin;  // [Smax, HD/2]
     const int32_t* starts; // [B]
@@ -519,12 +538,12 @@ struct ExtendAttnArgs {
 // (ceil(Lq / (64 / n_rep)), KVH, B); head shapes: attn_decode_ragged_shape_ok
 hipError_t launch_attn_extend_ragged(const ExtendAttnArgs& a, hipStream_t s);
 // cache[dst[i]][h][0 .. n_slots) = cache[src][h][0 .. n_slots) for i < n_dst, h < KVH, in both
-// caches (dst: device memory; n_rows: rows of the caches)
-hipError_t launch_cache_copy_rows(float* cache_k, float* cache_v, int src, const int32_t* dst, int n_dst, int KVH,
-                                  int Smax, int HD, int n_slots, int n_rows, hipStream_t s);
-// cache[b][h][len[b]] = 0 for b < B with budget[b] > 0, h < KVH, in both caches
-hipError_t launch_ragged_zero_slot(float* cache_k, float* cache_v, const int32_t* len, const int32_t* budget, int B,
-                                   int KVH, int Smax, int HD, hipStream_t s);
+// caches (dst: device memory; n_rows: rows of the caches; elements of kv_dtype, copied as bits)
+hipError_t launch_cache_copy_rows(void* cache_k, void* cache_v, int kv_dtype, int src, const int32_t* dst, int n_dst,
+                                  int KVH, int Smax, int HD, int n_slots, int n_rows, hipStream_t s);
+// cache[b][h][len[b]] = 0 for b < B with budget[b] > 0, h < KVH, in both caches (elements of kv_dtype)
+hipError_t launch_ragged_zero_slot(void* cache_k, void* cache_v, int kv_dtype, const int32_t* len,
+                                   const int32_t* budget, int B, int KVH, int Smax, int HD, hipStream_t s);
 hipError_t dcheck_collect_extend(unsigned* out);
 
 // Speculative decoding with lookup drafts (spec.hip; DESIGN.md "Speculative decoding")

@@ -13,6 +13,104 @@ namespace l3 {
 namespace {
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
+using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
+
+// Cache access by element type KT (kernels.h KvDtype): float, or unsigned short holding bf16 bits.
+// kv_load_key: the HD elements of one key as HD/4 float4s — HD/4 16-byte loads of floats, or HD/8
+// 16-byte loads of bf16 widened in registers; the loads are independent, so all are in flight.
+template <int HD, typename KT>
+__device__ __forceinline__ void kv_load_key(const KT* key, f32x4 (&kv)[HD / 4]) {
+    if constexpr (sizeof(KT) == 4) {
+#pragma unroll
+        for (int i = 0; i < HD / 4; ++i) kv[i] = reinterpret_cast<const f32x4*>(key)[i];
+    } else {
+        u32x4 raw[HD / 8];
+#pragma unroll
+        for (int i = 0; i < HD / 8; ++i) raw[i] = reinterpret_cast<const u32x4*>(key)[i];
+#pragma unroll
+        for (int i = 0; i < HD / 8; ++i) {
+            kv[2 * i] = f32x4{kv_bf16_lo(raw[i].x), kv_bf16_hi(raw[i].x), kv_bf16_lo(raw[i].y), kv_bf16_hi(raw[i].y)};
+            kv[2 * i + 1] = f32x4{kv_bf16_lo(raw[i].z), kv_bf16_hi(raw[i].z), kv_bf16_lo(raw[i].w), kv_bf16_hi(raw[i].w)};
+        }
+    }
+}
+// elements [4 * d4, 4 * d4 + 4) of a value row of floats: one 16-byte load (bf16 rows: pv_bf16)
+__device__ __forceinline__ f32x4 kv_load4(const float* row, int d4) { return reinterpret_cast<const f32x4*>(row)[d4]; }
+// The append of the step's own pair (elements 2i, 2i + 1) to its slot.  Returns what the slot now
+// holds, widened: the value itself for floats, its bf16 rounding otherwise — the LDS copy the owner
+// workgroup scores and accumulates from must be the value every later step reads from the cache.
+template <typename KT>
+__device__ __forceinline__ float2 kv_append2(KT* slot, int i, float2 x) {
+    if constexpr (sizeof(KT) == 4) {
+        *reinterpret_cast<float2*>(slot + 2 * i) = x;
+        return x;
+    } else {
+        const unsigned w = kv_bf16_rne(x.x) | (kv_bf16_rne(x.y) << 16);
+        *reinterpret_cast<unsigned*>(slot + 2 * i) = w;
+        return float2{kv_bf16_lo(w), kv_bf16_hi(w)};
+    }
+}
+
+// P.V of the decode kernels over a bf16 cache: a thread owns 8 columns of one key group, so a V row
+// is HD/8 16-byte loads (kv_load4's 8-byte loads would leave half of every load instruction unused)
+// and there are R8 = 2 R key groups.  The partials region `red` holds R groups ([n_rep][R][HD], the
+// footprint both storages share): the even groups store, the odd ones add to their neighbour's
+// partial after a barrier.  keys: cached keys [0, nkeys) of V (slot 0 = V), their weights
+// sc[r * stride + k]; has_new: the step's own value vn (rounded, LDS) with weight index new_idx.
+// Ends with the workgroup past a barrier, `red` complete.
+template <int HD>
+__device__ __forceinline__ void pv_bf16(const unsigned short* V, const float* sc, int stride, int nkeys,
+                                        bool has_new, int new_idx, const float* vn, float* red, int n_rep,
+                                        int tid) {
+    constexpr int D8 = HD / 8, D4 = HD / 4, R = 256 / D4, R8 = 2 * R;
+    const int rg = tid / D8, d8 = tid - rg * D8;
+    f32x4 acc[RAGGED_MAX_REP][2];
+#pragma unroll
+    for (int r = 0; r < RAGGED_MAX_REP; ++r) acc[r][0] = acc[r][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (rg < R8) {
+        for (int k = rg; k < nkeys; k += R8) {
+            const u32x4 w = reinterpret_cast<const u32x4*>(V + (int64_t)k * HD)[d8];
+            const f32x4 v0 = {kv_bf16_lo(w.x), kv_bf16_hi(w.x), kv_bf16_lo(w.y), kv_bf16_hi(w.y)};
+            const f32x4 v1 = {kv_bf16_lo(w.z), kv_bf16_hi(w.z), kv_bf16_lo(w.w), kv_bf16_hi(w.w)};
+#pragma unroll
+            for (int r = 0; r < RAGGED_MAX_REP; ++r)
+                if (r < n_rep) {
+                    const float pk = sc[r * stride + k];
+                    acc[r][0] += pk * v0;
+                    acc[r][1] += pk * v1;
+                }
+        }
+        if (has_new && rg == 0) {  // the new value, from LDS
+            const f32x4 v0 = reinterpret_cast<const f32x4*>(vn)[2 * d8], v1 = reinterpret_cast<const f32x4*>(vn)[2 * d8 + 1];
+#pragma unroll
+            for (int r = 0; r < RAGGED_MAX_REP; ++r)
+                if (r < n_rep) {
+                    const float pk = sc[r * stride + new_idx];
+                    acc[r][0] += pk * v0;
+                    acc[r][1] += pk * v1;
+                }
+        }
+    }
+    f32x4* red4 = reinterpret_cast<f32x4*>(red);
+    if (rg < R8 && !(rg & 1)) {
+#pragma unroll
+        for (int r = 0; r < RAGGED_MAX_REP; ++r)
+            if (r < n_rep) {
+                red4[(r * R + (rg >> 1)) * D4 + 2 * d8] = acc[r][0];
+                red4[(r * R + (rg >> 1)) * D4 + 2 * d8 + 1] = acc[r][1];
+            }
+    }
+    __syncthreads();
+    if (rg < R8 && (rg & 1)) {
+#pragma unroll
+        for (int r = 0; r < RAGGED_MAX_REP; ++r)
+            if (r < n_rep) {
+                red4[(r * R + (rg >> 1)) * D4 + 2 * d8] += acc[r][0];
+                red4[(r * R + (rg >> 1)) * D4 + 2 * d8 + 1] += acc[r][1];
+            }
+    }
+    __syncthreads();
+}
 
 // Decode attention over rows at their own positions (llama3.py:163-211 for one new token per
 // row; the cache slice :186-187 ends at the row's pos).  One workgroup per (KV head, row): the
@@ -32,7 +130,11 @@ using f32x4 = __attribute__((ext_vector_type(4))) float;
 // writes zeros to its output rows and touches nothing else.
 // LDS floats: [n_rep][HD] q, [HD] k, [HD] v, [8] row sums, [n_rep][R][HD] partials,
 // [n_rep][s_cap] scores (attn_decode_ragged_lds).
-template <int HD>
+// KT: the cache's element (above).  With bf16 a thread's key is HD/8 16-byte loads widened in
+// registers, P.V runs in pv_bf16's 2 R key groups of 16-byte loads, and the new k / v are rounded as
+// they are stored while LDS keeps the rounded values (kv_append2), so the step's own token is used as
+// every later step will read it.
+template <int HD, typename KT>
 __global__ void __launch_bounds__(256) attn_decode_ragged_kernel(RaggedAttnArgs p) {
     constexpr int D4 = HD / 4, R = 256 / D4, HALF = HD / 2;
     extern __shared__ __attribute__((aligned(16))) float dsm[];
@@ -61,6 +163,8 @@ __global__ void __launch_bounds__(256) attn_decode_ragged_kernel(RaggedAttnArgs 
     const float* cs = p.rope_cos + (int64_t)pos * HALF;
     const float* sn = p.rope_sin + (int64_t)pos * HALF;
     const int64_t kv_base = ((int64_t)b * p.KVH + kvh) * p.Smax * HD;
+    KT* Kc = static_cast<KT*>(p.cache_k) + kv_base;  // the (row, KV head)'s keys and values, slot 0
+    KT* Vc = static_cast<KT*>(p.cache_v) + kv_base;
     // (0) the step's q, k, v
     for (int t = tid; t < n_rep * HALF; t += 256) {
         const int r = t / HALF, i = t - r * HALF;
@@ -74,23 +178,18 @@ __global__ void __launch_bounds__(256) attn_decode_ragged_kernel(RaggedAttnArgs 
         const float2 v = *reinterpret_cast<const float2*>(row + qdim + kvh * HD + 2 * i);
         const float c = cs[i], s = sn[i];
         const float2 k2 = float2{v.x * c - v.y * s, v.x * s + v.y * c};
-        *reinterpret_cast<float2*>(kn + 2 * i) = k2;
-        *reinterpret_cast<float2*>(p.cache_k + kv_base + (int64_t)pos * HD + 2 * i) = k2;
+        *reinterpret_cast<float2*>(kn + 2 * i) = kv_append2(Kc + (int64_t)pos * HD, i, k2);
     } else if (tid < HD) {
         const int i = tid - HALF;
         const float2 v2 = *reinterpret_cast<const float2*>(row + qdim + kvdim + kvh * HD + 2 * i);
-        *reinterpret_cast<float2*>(vn + 2 * i) = v2;
-        *reinterpret_cast<float2*>(p.cache_v + kv_base + (int64_t)pos * HD + 2 * i) = v2;
+        *reinterpret_cast<float2*>(vn + 2 * i) = kv_append2(Vc + (int64_t)pos * HD, i, v2);
     }
     __syncthreads();
-    const f32x4* K4 = reinterpret_cast<const f32x4*>(p.cache_k + kv_base);
-    const f32x4* V4 = reinterpret_cast<const f32x4*>(p.cache_v + kv_base);
     const f32x4* q4 = reinterpret_cast<const f32x4*>(qs);
     // (1) scores of the cached keys [0, pos): each K row loaded once for the n_rep heads
     for (int k = tid; k < pos; k += 256) {
         f32x4 kv[D4];
-#pragma unroll
-        for (int i = 0; i < D4; ++i) kv[i] = K4[(int64_t)k * D4 + i];
+        kv_load_key<HD>(Kc + (int64_t)k * HD, kv);
 #pragma unroll
         for (int r = 0; r < RAGGED_MAX_REP; ++r) {
             if (r < n_rep) {
@@ -132,13 +231,16 @@ __global__ void __launch_bounds__(256) attn_decode_ragged_kernel(RaggedAttnArgs 
     }
     __syncthreads();
     // (3) P.V: each V row loaded once for the n_rep heads
+    if constexpr (sizeof(KT) == 2) {
+        pv_bf16<HD>(Vc, sc, p.s_cap, pos, true, pos, vn, red, n_rep, tid);
+    } else {
     const int rg = tid / D4, d4 = tid - rg * D4;
     if (rg < R) {
         f32x4 acc[RAGGED_MAX_REP];
 #pragma unroll
         for (int r = 0; r < RAGGED_MAX_REP; ++r) acc[r] = f32x4{0.f, 0.f, 0.f, 0.f};
         for (int k = rg; k < pos; k += R) {
-            const f32x4 v = V4[(int64_t)k * D4 + d4];
+            const f32x4 v = kv_load4(Vc + (int64_t)k * HD, d4);
 #pragma unroll
             for (int r = 0; r < RAGGED_MAX_REP; ++r)
                 if (r < n_rep) acc[r] += sc[r * p.s_cap + k] * v;
@@ -154,6 +256,7 @@ __global__ void __launch_bounds__(256) attn_decode_ragged_kernel(RaggedAttnArgs 
             if (r < n_rep) reinterpret_cast<f32x4*>(red)[(r * R + rg) * D4 + d4] = acc[r];
     }
     __syncthreads();
+    }
     for (int t = tid; t < n_rep * D4; t += 256) {
         const int r = t / D4, d = t - r * D4;
         f32x4 o = {0.f, 0.f, 0.f, 0.f};
@@ -179,8 +282,8 @@ __global__ void __launch_bounds__(256) attn_decode_ragged_kernel(RaggedAttnArgs 
 // (row, head, chunk), to the workspace: the unnormalised o[HD], m and l — plain stores, no
 // atomics, no flags: attn_decode_combine_kernel is the next launch on the stream.
 // LDS floats: [n_rep][HD] q, [HD] k, [HD] v, [8] row sums, [n_rep][R][HD] partials, [n_rep][CH]
-// scores (attn_decode_split_lds).
-template <int HD>
+// scores (attn_decode_split_lds).  KT: as in the kernel above; the workspace and the combine are fp32.
+template <int HD, typename KT>
 __global__ void __launch_bounds__(256) attn_decode_split_kernel(RaggedAttnArgs p) {
     constexpr int D4 = HD / 4, R = 256 / D4, HALF = HD / 2;
     extern __shared__ __attribute__((aligned(16))) float dsm[];
@@ -211,6 +314,8 @@ __global__ void __launch_bounds__(256) attn_decode_split_kernel(RaggedAttnArgs p
     const float* cs = p.rope_cos + (int64_t)pos * HALF;
     const float* sn = p.rope_sin + (int64_t)pos * HALF;
     const int64_t kv_base = ((int64_t)b * p.KVH + kvh) * p.Smax * HD;
+    KT* Kr = static_cast<KT*>(p.cache_k) + kv_base;  // the (row, KV head)'s keys and values, slot 0
+    KT* Vr = static_cast<KT*>(p.cache_v) + kv_base;
     // (0) the step's q; in the owner also k, v and their append to slot pos
     for (int t = tid; t < n_rep * HALF; t += 256) {
         const int r = t / HALF, i = t - r * HALF;
@@ -225,24 +330,21 @@ __global__ void __launch_bounds__(256) attn_decode_split_kernel(RaggedAttnArgs p
             const float2 v = *reinterpret_cast<const float2*>(row + qdim + kvh * HD + 2 * i);
             const float cc = cs[i], s = sn[i];
             const float2 k2 = float2{v.x * cc - v.y * s, v.x * s + v.y * cc};
-            *reinterpret_cast<float2*>(kn + 2 * i) = k2;
-            *reinterpret_cast<float2*>(p.cache_k + kv_base + (int64_t)pos * HD + 2 * i) = k2;
+            *reinterpret_cast<float2*>(kn + 2 * i) = kv_append2(Kr + (int64_t)pos * HD, i, k2);
         } else if (tid < HD) {
             const int i = tid - HALF;
             const float2 v2 = *reinterpret_cast<const float2*>(row + qdim + kvdim + kvh * HD + 2 * i);
-            *reinterpret_cast<float2*>(vn + 2 * i) = v2;
-            *reinterpret_cast<float2*>(p.cache_v + kv_base + (int64_t)pos * HD + 2 * i) = v2;
+            *reinterpret_cast<float2*>(vn + 2 * i) = kv_append2(Vr + (int64_t)pos * HD, i, v2);
         }
     }
     __syncthreads();
-    const f32x4* K4 = reinterpret_cast<const f32x4*>(p.cache_k + kv_base) + (int64_t)k0 * D4;
-    const f32x4* V4 = reinterpret_cast<const f32x4*>(p.cache_v + kv_base) + (int64_t)k0 * D4;
+    const KT* Kc = Kr + (int64_t)k0 * HD;  // the chunk's first key / value
+    const KT* Vc = Vr + (int64_t)k0 * HD;
     const f32x4* q4 = reinterpret_cast<const f32x4*>(qs);
     // (1) scores of the chunk's cached keys: each K row loaded once for the n_rep heads
     for (int k = tid; k < nc; k += 256) {
         f32x4 kv[D4];
-#pragma unroll
-        for (int i = 0; i < D4; ++i) kv[i] = K4[(int64_t)k * D4 + i];
+        kv_load_key<HD>(Kc + (int64_t)k * HD, kv);
 #pragma unroll
         for (int r = 0; r < RAGGED_MAX_REP; ++r) {
             if (r < n_rep) {
@@ -288,13 +390,16 @@ __global__ void __launch_bounds__(256) attn_decode_split_kernel(RaggedAttnArgs p
     }
     __syncthreads();
     // (3) P.V: each V row loaded once for the n_rep heads
+    if constexpr (sizeof(KT) == 2) {
+        pv_bf16<HD>(Vc, sc, CH, nc, own, nc, vn, red, n_rep, tid);
+    } else {
     const int rg = tid / D4, d4 = tid - rg * D4;
     if (rg < R) {
         f32x4 acc[RAGGED_MAX_REP];
 #pragma unroll
         for (int r = 0; r < RAGGED_MAX_REP; ++r) acc[r] = f32x4{0.f, 0.f, 0.f, 0.f};
         for (int k = rg; k < nc; k += R) {
-            const f32x4 v = V4[(int64_t)k * D4 + d4];
+            const f32x4 v = kv_load4(Vc + (int64_t)k * HD, d4);
 #pragma unroll
             for (int r = 0; r < RAGGED_MAX_REP; ++r)
                 if (r < n_rep) acc[r] += sc[r * CH + k] * v;
@@ -310,6 +415,7 @@ __global__ void __launch_bounds__(256) attn_decode_split_kernel(RaggedAttnArgs p
             if (r < n_rep) reinterpret_cast<f32x4*>(red)[(r * R + rg) * D4 + d4] = acc[r];
     }
     __syncthreads();
+    }
     for (int t = tid; t < n_rep * D4; t += 256) {
         const int r = t / D4, d = t - r * D4;
         f32x4 o = {0.f, 0.f, 0.f, 0.f};
@@ -355,7 +461,8 @@ __global__ void __launch_bounds__(64) attn_decode_combine_kernel(RaggedAttnArgs 
 
 // After a right-padded prefill at position 0 (llama3.py:285-308 on [B, Lmax]): slots
 // [len[b], Lmax) of row b hold the pads' K / V; a row run alone would have left them zero
-// (slot len[b] is the one the reference's loop never writes, :312-318).  grid (KVH, B)
+// (slot len[b] is the one the reference's loop never writes, :312-318).  grid (KVH, B).  HD: floats
+// per slot, i.e. half the head size for a bf16 cache (launch_ragged_zero_tail)
 __global__ void __launch_bounds__(256) ragged_zero_tail_kernel(float* __restrict__ ck, float* __restrict__ cv,
                                                                const int32_t* __restrict__ len, int KVH, int Smax,
                                                                int HD, int Lmax) {
@@ -414,13 +521,20 @@ __global__ void __launch_bounds__(256) ragged_advance_kernel(RaggedState st, con
 
 template <int HD>
 hipError_t launch_ragged_hd(const RaggedAttnArgs& a, size_t lds, hipStream_t s) {
-    hipLaunchKernelGGL((attn_decode_ragged_kernel<HD>), dim3(a.KVH, a.B), dim3(256), lds, s, a);
+    if (a.kv_dtype == KV_BF16)
+        hipLaunchKernelGGL((attn_decode_ragged_kernel<HD, unsigned short>), dim3(a.KVH, a.B), dim3(256), lds, s, a);
+    else
+        hipLaunchKernelGGL((attn_decode_ragged_kernel<HD, float>), dim3(a.KVH, a.B), dim3(256), lds, s, a);
     return hipGetLastError();
 }
 
 template <int HD>
 hipError_t launch_split_hd(const RaggedAttnArgs& a, int n_split, size_t lds, hipStream_t s) {
-    hipLaunchKernelGGL((attn_decode_split_kernel<HD>), dim3(n_split, a.KVH, a.B), dim3(256), lds, s, a);
+    if (a.kv_dtype == KV_BF16)
+        hipLaunchKernelGGL((attn_decode_split_kernel<HD, unsigned short>), dim3(n_split, a.KVH, a.B), dim3(256), lds,
+                           s, a);
+    else
+        hipLaunchKernelGGL((attn_decode_split_kernel<HD, float>), dim3(n_split, a.KVH, a.B), dim3(256), lds, s, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((attn_decode_combine_kernel<HD>), dim3(a.H, a.B), dim3(64), 0, s, a, n_split);
@@ -457,6 +571,7 @@ int attn_decode_split_chunk(int H, int KVH, int HD, int want) {
 hipError_t launch_attn_decode_ragged_split(const RaggedAttnArgs& a, hipStream_t s) {
     if (a.B <= 0) return hipSuccess;
     if (!attn_decode_ragged_shape_ok(a.H, a.KVH, a.HD) || a.s_cap <= 0 || !a.ws) return hipErrorInvalidValue;
+    if (!kv_dtype_ok(a.kv_dtype)) return hipErrorInvalidValue;
     if (a.chunk < RAGGED_CHUNK_MIN || a.chunk > RAGGED_CHUNK_MAX || a.chunk % 64) return hipErrorInvalidValue;
     const size_t lds = attn_decode_split_lds(a.H, a.KVH, a.HD, a.chunk);
     if (lds > RAGGED_LDS_BYTES || a.B > 65535 || a.KVH > 65535) return hipErrorInvalidValue;
@@ -474,7 +589,7 @@ hipError_t launch_attn_decode_ragged_split(const RaggedAttnArgs& a, hipStream_t 
 
 hipError_t launch_attn_decode_ragged(const RaggedAttnArgs& a, hipStream_t s) {
     if (a.B <= 0) return hipSuccess;
-    if (!attn_decode_ragged_ok(a.H, a.KVH, a.HD, a.s_cap)) return hipErrorInvalidValue;
+    if (!attn_decode_ragged_ok(a.H, a.KVH, a.HD, a.s_cap) || !kv_dtype_ok(a.kv_dtype)) return hipErrorInvalidValue;
     const size_t lds = attn_decode_ragged_lds(a.H, a.KVH, a.HD, a.s_cap);
     switch (a.HD) {
         case 16: return launch_ragged_hd<16>(a, lds, s);
@@ -487,11 +602,16 @@ hipError_t launch_attn_decode_ragged(const RaggedAttnArgs& a, hipStream_t s) {
     }
 }
 
-hipError_t launch_ragged_zero_tail(float* cache_k, float* cache_v, const int32_t* len, int B, int KVH, int Smax,
-                                   int HD, int Lmax, hipStream_t s) {
+hipError_t launch_ragged_zero_tail(void* cache_k, void* cache_v, int kv_dtype, const int32_t* len, int B, int KVH,
+                                   int Smax, int HD, int Lmax, hipStream_t s) {
     if (B <= 0 || Lmax <= 1) return hipSuccess;  // Lmax 1: every len is 1, no tail
+    if (!kv_dtype_ok(kv_dtype) || HD * kv_elem_bytes(kv_dtype) % 16) return hipErrorInvalidValue;
+    // the kernel clears 16-byte words of zero bits (+0 in either type): a slot of HD elements is
+    // HD * bytes / 4 floats to it
+    HD = HD * kv_elem_bytes(kv_dtype) / 4;
     if (Lmax > Smax || HD % 4) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(ragged_zero_tail_kernel, dim3(KVH, B), dim3(256), 0, s, cache_k, cache_v, len, KVH, Smax, HD, Lmax);
+    hipLaunchKernelGGL(ragged_zero_tail_kernel, dim3(KVH, B), dim3(256), 0, s, static_cast<float*>(cache_k),
+                       static_cast<float*>(cache_v), len, KVH, Smax, HD, Lmax);
     return hipGetLastError();
 }
 

@@ -6,6 +6,8 @@
 // one slot a continued generate loop never writes.
 #include <math.h>
 
+#include <type_traits>
+
 #include "kernels.h"
 
 namespace l3 {
@@ -13,6 +15,8 @@ namespace l3 {
 namespace {
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
+using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
+using u32x2 = __attribute__((ext_vector_type(2))) unsigned;
 
 // the row's chunk: len new tokens at positions [start, start + len); a chunk that does not lie in
 // the cache is counted by the check build and runs as an empty one (nothing read, nothing written)
@@ -32,8 +36,10 @@ __device__ __forceinline__ int extend_len(const ExtendAttnArgs& p, int b, int* s
 // and v to slot pos of the cache, 16 bytes per store.  grid (ceil(Lq / EXT_TA), KVH, B); a thread
 // moves one float4 of k and of v.  Pads (t >= len[b]) write nothing: every slot outside
 // [start[b], start[b] + len[b]) stays bit for bit as it was.
+// KT (kernels.h KvDtype): float, or unsigned short — RoPE in fp32 as above, then each of the four
+// elements rounded to bf16 (kv_bf16_rne) and stored as 8 bytes.
 constexpr int EXT_TA = 16;
-template <int HD>
+template <int HD, typename KT>
 __global__ void __launch_bounds__(256) ragged_extend_append_kernel(ExtendAttnArgs p) {
     constexpr int D4 = HD / 4, HALF = HD / 2;
     const int kvh = blockIdx.y, b = blockIdx.z;
@@ -52,8 +58,17 @@ __global__ void __launch_bounds__(256) ragged_extend_append_kernel(ExtendAttnArg
         const float2 c = *reinterpret_cast<const float2*>(p.rope_cos + (int64_t)pos * HALF + d / 2);
         const float2 s = *reinterpret_cast<const float2*>(p.rope_sin + (int64_t)pos * HALF + d / 2);
         const f32x4 kr = {k.x * c.x - k.y * s.x, k.x * s.x + k.y * c.x, k.z * c.y - k.w * s.y, k.z * s.y + k.w * c.y};
-        *reinterpret_cast<f32x4*>(p.cache_k + kv_base + (int64_t)pos * HD + d) = kr;
-        *reinterpret_cast<f32x4*>(p.cache_v + kv_base + (int64_t)pos * HD + d) = v;
+        KT* kdst = static_cast<KT*>(p.cache_k) + kv_base + (int64_t)pos * HD + d;
+        KT* vdst = static_cast<KT*>(p.cache_v) + kv_base + (int64_t)pos * HD + d;
+        if constexpr (sizeof(KT) == 4) {
+            *reinterpret_cast<f32x4*>(kdst) = kr;
+            *reinterpret_cast<f32x4*>(vdst) = v;
+        } else {
+            *reinterpret_cast<u32x2*>(kdst) =
+                u32x2{kv_bf16_rne(kr.x) | (kv_bf16_rne(kr.y) << 16), kv_bf16_rne(kr.z) | (kv_bf16_rne(kr.w) << 16)};
+            *reinterpret_cast<u32x2*>(vdst) =
+                u32x2{kv_bf16_rne(v.x) | (kv_bf16_rne(v.y) << 16), kv_bf16_rne(v.z) | (kv_bf16_rne(v.w) << 16)};
+        }
     }
 }
 
@@ -80,12 +95,19 @@ __global__ void __launch_bounds__(256) ragged_extend_append_kernel(ExtendAttnArg
 // start[b] + len[b] on are never read, whatever they hold; a pad or idle query row computes on a
 // copy of the tile's last real token and is never stored.  Pad rows of a live tile and every row
 // of a tile past len[b] get zeros.
+//
+// KT (kernels.h KvDtype): float, or unsigned short holding bf16 bits.  A 16-byte global load is a
+// piece of EPP = 16 / sizeof(KT) elements, HD / EPP pieces per key; a bf16 piece is widened as it is
+// stored (u << 16, u & 0xffff0000) into the same fp32 LDS image, so everything from the fragment
+// reads on is the same for both: half the global bytes and half the staging registers, same LDS.
 constexpr int EXT_KT = 32;
-template <int HD>
+template <int HD, typename KT>
 __global__ void __launch_bounds__(256) attn_extend_ragged_kernel(ExtendAttnArgs p) {
     constexpr int ND = HD / 16, KG = EXT_KT / 16, D4 = HD / 4, HALF = HD / 2;
     constexpr int KSTR = HD + 8, VSTR = HD + 4;  // attn_kernel.h: conflict-free fragment reads
-    constexpr int K_F4 = EXT_KT * D4, K_IT = (K_F4 + 255) / 256;
+    constexpr int EPP = 16 / (int)sizeof(KT), DP = HD / EPP;  // elements per piece, pieces per key
+    constexpr int K_F4 = EXT_KT * DP, K_IT = (K_F4 + 255) / 256;
+    using Piece = typename std::conditional<sizeof(KT) == 4, f32x4, u32x4>::type;
     __shared__ __attribute__((aligned(16))) float Ks[EXT_KT][KSTR];
     __shared__ __attribute__((aligned(16))) float Vs[EXT_KT][VSTR];
 
@@ -140,27 +162,39 @@ __global__ void __launch_bounds__(256) attn_extend_ragged_kernel(ExtendAttnArgs 
     float m_run = -INFINITY, l_run = 0.f;
 
     const int64_t kv_base = ((int64_t)b * p.KVH + kvh) * p.Smax;
-    f32x4 rk[K_IT], rv[K_IT];
+    const KT* ck = static_cast<const KT*>(p.cache_k);
+    const KT* cv = static_cast<const KT*>(p.cache_v);
+    Piece rk[K_IT], rv[K_IT];
     auto gload = [&](int tile) {
 #pragma unroll
         for (int i = 0; i < K_IT; ++i) {
             const int f = tid + 256 * i;
-            const int row = f / D4, c = (f % D4) * 4;
+            const int row = f / DP, c = (f % DP) * EPP;
             const int key = min(tile * EXT_KT + row, key_end - 1);
             if (K_F4 % 256 == 0 || f < K_F4) {
-                rk[i] = *reinterpret_cast<const f32x4*>(p.cache_k + (kv_base + key) * HD + c);
-                rv[i] = *reinterpret_cast<const f32x4*>(p.cache_v + (kv_base + key) * HD + c);
+                rk[i] = *reinterpret_cast<const Piece*>(ck + (kv_base + key) * HD + c);
+                rv[i] = *reinterpret_cast<const Piece*>(cv + (kv_base + key) * HD + c);
             }
         }
+    };
+    auto widen = [](unsigned a, unsigned b) {
+        return f32x4{kv_bf16_lo(a), kv_bf16_hi(a), kv_bf16_lo(b), kv_bf16_hi(b)};
     };
     auto sstore = [&]() {
 #pragma unroll
         for (int i = 0; i < K_IT; ++i) {
             const int f = tid + 256 * i;
             if (K_F4 % 256 == 0 || f < K_F4) {
-                const int row = f / D4, c = (f % D4) * 4;
-                *reinterpret_cast<f32x4*>(&Ks[row][c]) = rk[i];
-                *reinterpret_cast<f32x4*>(&Vs[row][c]) = rv[i];
+                const int row = f / DP, c = (f % DP) * EPP;
+                if constexpr (sizeof(KT) == 4) {
+                    *reinterpret_cast<f32x4*>(&Ks[row][c]) = rk[i];
+                    *reinterpret_cast<f32x4*>(&Vs[row][c]) = rv[i];
+                } else {
+                    *reinterpret_cast<f32x4*>(&Ks[row][c]) = widen(rk[i].x, rk[i].y);
+                    *reinterpret_cast<f32x4*>(&Ks[row][c + 4]) = widen(rk[i].z, rk[i].w);
+                    *reinterpret_cast<f32x4*>(&Vs[row][c]) = widen(rv[i].x, rv[i].y);
+                    *reinterpret_cast<f32x4*>(&Vs[row][c + 4]) = widen(rv[i].z, rv[i].w);
+                }
             }
         }
     };
@@ -244,7 +278,8 @@ __global__ void __launch_bounds__(256) attn_extend_ragged_kernel(ExtendAttnArgs 
 
 // Fork of a cache row (l3_cache_copy_rows): slots [0, n_slots) of K and V of row src to every row
 // of dst, one layer per launch.  grid (KVH, n_dst, ceil(n_slots / COPY_SLOTS)): a workgroup copies
-// COPY_SLOTS consecutive slots of one head, a contiguous run.
+// COPY_SLOTS consecutive slots of one head, a contiguous run.  HD: floats per slot, i.e. half the
+// head size for a bf16 cache (launch_cache_copy_rows): the copy is of bits.
 constexpr int COPY_SLOTS = 64;
 __global__ void __launch_bounds__(256) cache_copy_rows_kernel(float* __restrict__ ck, float* __restrict__ cv, int src,
                                                               const int32_t* __restrict__ dst, int KVH, int Smax,
@@ -264,7 +299,8 @@ __global__ void __launch_bounds__(256) cache_copy_rows_kernel(float* __restrict_
 
 // Before the decode steps of a continued generate loop: slot T_b = len[b] of every row with a
 // budget is the one the reference's loop never writes (llama3.py:312-318) but every later step
-// attends; a row run alone finds zero there.  grid (KVH, B)
+// attends; a row run alone finds zero there.  grid (KVH, B).  HD: floats per slot (as above; zero
+// bits are +0 in both element types)
 __global__ void __launch_bounds__(64) ragged_zero_slot_kernel(float* __restrict__ ck, float* __restrict__ cv,
                                                               const int32_t* __restrict__ len,
                                                               const int32_t* __restrict__ budget, int KVH, int Smax,
@@ -281,15 +317,20 @@ __global__ void __launch_bounds__(64) ragged_zero_slot_kernel(float* __restrict_
     }
 }
 
-template <int HD>
-hipError_t launch_extend_hd(const ExtendAttnArgs& a, hipStream_t s) {
+template <int HD, typename KT>
+hipError_t launch_extend_kt(const ExtendAttnArgs& a, hipStream_t s) {
     const int TQ = 64 / (a.H / a.KVH);
-    hipLaunchKernelGGL((ragged_extend_append_kernel<HD>), dim3((a.Lq + EXT_TA - 1) / EXT_TA, a.KVH, a.B), dim3(256), 0,
-                       s, a);
+    hipLaunchKernelGGL((ragged_extend_append_kernel<HD, KT>), dim3((a.Lq + EXT_TA - 1) / EXT_TA, a.KVH, a.B),
+                       dim3(256), 0, s, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((attn_extend_ragged_kernel<HD>), dim3((a.Lq + TQ - 1) / TQ, a.KVH, a.B), dim3(256), 0, s, a);
+    hipLaunchKernelGGL((attn_extend_ragged_kernel<HD, KT>), dim3((a.Lq + TQ - 1) / TQ, a.KVH, a.B), dim3(256), 0, s, a);
     return hipGetLastError();
+}
+
+template <int HD>
+hipError_t launch_extend_hd(const ExtendAttnArgs& a, hipStream_t s) {
+    return a.kv_dtype == KV_BF16 ? launch_extend_kt<HD, unsigned short>(a, s) : launch_extend_kt<HD, float>(a, s);
 }
 
 }  // namespace
@@ -297,7 +338,7 @@ hipError_t launch_extend_hd(const ExtendAttnArgs& a, hipStream_t s) {
 hipError_t launch_attn_extend_ragged(const ExtendAttnArgs& a, hipStream_t s) {
     if (a.B <= 0 || a.Lq <= 0) return hipSuccess;
     if (!attn_decode_ragged_shape_ok(a.H, a.KVH, a.HD) || a.Smax <= 0) return hipErrorInvalidValue;
-    if (a.B > 65535 || a.KVH > 65535) return hipErrorInvalidValue;
+    if (a.B > 65535 || a.KVH > 65535 || !kv_dtype_ok(a.kv_dtype)) return hipErrorInvalidValue;
     switch (a.HD) {
         case 16: return launch_extend_hd<16>(a, s);
         case 32: return launch_extend_hd<32>(a, s);
@@ -309,22 +350,27 @@ hipError_t launch_attn_extend_ragged(const ExtendAttnArgs& a, hipStream_t s) {
     }
 }
 
-hipError_t launch_cache_copy_rows(float* cache_k, float* cache_v, int src, const int32_t* dst, int n_dst, int KVH,
-                                  int Smax, int HD, int n_slots, int n_rows, hipStream_t s) {
+hipError_t launch_cache_copy_rows(void* cache_k, void* cache_v, int kv_dtype, int src, const int32_t* dst, int n_dst,
+                                  int KVH, int Smax, int HD, int n_slots, int n_rows, hipStream_t s) {
     if (n_dst <= 0 || n_slots <= 0) return hipSuccess;
+    if (!kv_dtype_ok(kv_dtype) || HD * kv_elem_bytes(kv_dtype) % 16) return hipErrorInvalidValue;
+    HD = HD * kv_elem_bytes(kv_dtype) / 4;  // floats per slot
     if (n_slots > Smax || HD % 4 || src < 0 || src >= n_rows || n_dst > 65535) return hipErrorInvalidValue;
     const dim3 grid(KVH, n_dst, (n_slots + COPY_SLOTS - 1) / COPY_SLOTS);
     if (grid.z > 65535) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(cache_copy_rows_kernel, grid, dim3(256), 0, s, cache_k, cache_v, src, dst, KVH, Smax, HD,
-                       n_slots, n_rows);
+    hipLaunchKernelGGL(cache_copy_rows_kernel, grid, dim3(256), 0, s, static_cast<float*>(cache_k),
+                       static_cast<float*>(cache_v), src, dst, KVH, Smax, HD, n_slots, n_rows);
     return hipGetLastError();
 }
 
-hipError_t launch_ragged_zero_slot(float* cache_k, float* cache_v, const int32_t* len, const int32_t* budget, int B,
-                                   int KVH, int Smax, int HD, hipStream_t s) {
+hipError_t launch_ragged_zero_slot(void* cache_k, void* cache_v, int kv_dtype, const int32_t* len,
+                                   const int32_t* budget, int B, int KVH, int Smax, int HD, hipStream_t s) {
     if (B <= 0) return hipSuccess;
+    if (!kv_dtype_ok(kv_dtype) || HD * kv_elem_bytes(kv_dtype) % 16) return hipErrorInvalidValue;
+    HD = HD * kv_elem_bytes(kv_dtype) / 4;  // floats per slot
     if (HD % 4) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(ragged_zero_slot_kernel, dim3(KVH, B), dim3(64), 0, s, cache_k, cache_v, len, budget, KVH, Smax, HD);
+    hipLaunchKernelGGL(ragged_zero_slot_kernel, dim3(KVH, B), dim3(64), 0, s, static_cast<float*>(cache_k),
+                       static_cast<float*>(cache_v), len, budget, KVH, Smax, HD);
     return hipGetLastError();
 }
 

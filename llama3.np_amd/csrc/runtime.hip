@@ -10,6 +10,8 @@
 //              wd   [D, FD]
 //              n_attn / n_ffn [D]            RMSNorm weights, applied inside the GEMMs
 //              cache_k / cache_v [maxB, KVH, M, HD]  zero-initialised, persistent
+//                                            (fp32, or bf16 at two bytes per element in a context
+//                                            of l3_create_kv(L3_KV_BF16): ragged paths only)
 //   lm_head    [VS, D], final_norm [D]       (vocab_size 0: layer-only context, no tables)
 //   rope cos/sin [M, HD/2] fp32 (computed in double exactly as llama3.py:31-38, then rounded)
 //   workspace  h [T, D] residual stream, q [T, H*HD], attn [T, H*HD], hidden [T, FD],
@@ -73,6 +75,9 @@ struct Layer {
     float* wd = nullptr;
     float* n_attn = nullptr;
     float* n_ffn = nullptr;
+    // [maxB, KVH, Smax, HD] of the context's kv_dtype.  In a bf16 context (l3_create_kv) the
+    // allocations hold unsigned short and are half the size: only the ragged paths, which pass
+    // kv_dtype to their kernels, may touch them; every fp32-cache entry point refuses first (kv_f32_only)
     float* cache_k = nullptr;
     float* cache_v = nullptr;
     unsigned have = 0;  // bitmask of uploaded kinds
@@ -148,6 +153,7 @@ struct l3_ctx {
                                      // (l3_set_last_layer_rows, L3_LAST_LAYER_ALL_ROWS)
     int64_t split_min_tokens = 8192; // a part must hold at least this many tokens
     l3_dims d{};
+    int kv_dtype = L3_KV_F32;        // KV-cache element (l3_create_kv), fixed for the context's life
     int HD = 0, qdim = 0, kvdim = 0, qkvn = 0;
     float* emb = nullptr;
     float* lm_head = nullptr;
@@ -501,8 +507,28 @@ static int launch_decode_graph(l3_ctx* c, hipGraphExec_t g, hipEvent_t before = 
     return 0;
 }
 
+// bytes of one layer's K (or V) allocation
+static int64_t kv_cache_bytes(const l3_ctx* c) {
+    return (int64_t)c->d.max_batch_size * c->d.n_kv_heads * c->d.max_seq_len * c->HD * kv_elem_bytes(c->kv_dtype);
+}
+
+// The entry points whose kernels read or write the cache as fp32 (the equal-length prefill, the
+// captured and persistent decode steps, scoring, the module-level calls): refused in a bf16 context
+// before anything is allocated or launched — they would read bf16 bits as floats
+static int kv_f32_only(const l3_ctx* c, const char* who) {
+    if (c->kv_dtype == L3_KV_F32) return 0;
+    return fail("%s: this context stores its KV cache as bf16 (kv_dtype); %s reads and writes an fp32 cache — use "
+                "the ragged entry points", who, who);
+}
+
 extern "C" int l3_create(int32_t device, const l3_dims* dims, l3_ctx** out) {
+    return l3_create_kv(device, dims, L3_KV_F32, out);
+}
+
+extern "C" int l3_create_kv(int32_t device, const l3_dims* dims, int32_t kv_dtype, l3_ctx** out) {
     if (!dims || !out) return fail("l3_create: null argument");
+    if (kv_dtype != L3_KV_F32 && kv_dtype != L3_KV_BF16)
+        return fail("l3_create_kv: kv_dtype %d (L3_KV_F32 = 0, L3_KV_BF16 = 1)", kv_dtype);
     const l3_dims& d = *dims;
     if (d.dim <= 0 || d.n_heads <= 0 || d.n_kv_heads <= 0 || d.dim % d.n_heads)
         return fail("l3_create: bad dims (dim %d, heads %d)", d.dim, d.n_heads);
@@ -518,6 +544,7 @@ extern "C" int l3_create(int32_t device, const l3_dims* dims, l3_ctx** out) {
     l3_ctx* c = new l3_ctx();
     c->device = device;
     c->d = d;
+    c->kv_dtype = kv_dtype;
     c->prune_last = env_knob("L3_LAST_LAYER_ALL_ROWS", 0) == 0;
     c->gemm_x6 = env_knob("L3_GEMM_X6", 0) != 0;
     {
@@ -570,7 +597,7 @@ extern "C" int l3_create(int32_t device, const l3_dims* dims, l3_ctx** out) {
     c->layers.resize(d.n_layers > 0 ? d.n_layers : 0);
     if (d.n_layers > 0) {
         const int64_t D = d.dim, FD = d.hidden_dim;
-        const int64_t cache = (int64_t)d.max_batch_size * d.n_kv_heads * d.max_seq_len * HD * 4;
+        const int64_t cache = kv_cache_bytes(c);  // at the element size: no fp32 allocation first
         for (auto& L : c->layers) {
             if (hipMalloc(&L.wqkv, c->qkvn * D * 4) || hipMalloc(&L.wo, D * c->qdim * 4) ||
                 hipMalloc(&L.wgu, 2 * FD * D * 4) || hipMalloc(&L.wd, D * FD * 4) ||
@@ -1184,7 +1211,7 @@ extern "C" int l3_reset_cache(l3_ctx* c) {
     c->spec_q.clear();
     c->spec_base = c->spec_end = 0;
     c->dec_pos_mirror = -1;
-    const int64_t cache = (int64_t)c->d.max_batch_size * c->d.n_kv_heads * c->d.max_seq_len * c->HD * 4;
+    const int64_t cache = kv_cache_bytes(c);  // zero bits: +0 in both element types
     for (auto& L : c->layers) {
         HIP_TRY(hipMemsetAsync(L.cache_k, 0, cache, c->stream));
         HIP_TRY(hipMemsetAsync(L.cache_v, 0, cache, c->stream));
@@ -1608,6 +1635,7 @@ extern "C" int l3_set_last_layer_rows(l3_ctx* c, int32_t all_rows) {
 extern "C" int l3_forward_dev(l3_ctx* c, const int32_t* ids_dev, int32_t B, int32_t L,
                               int32_t start_pos, float* logits_dev) {
     CHECK_CTX(c);
+    if (kv_f32_only(c, "l3_forward_dev")) return 1;
     if (need_model(c) || check_call(c, B, L, start_pos) || set_dev(c, false) || spec_resolve(c) || ensure_ws(c, B, L))
         return 1;
     return forward_dev(c, ids_dev, B, L, start_pos, logits_dev);
@@ -1616,6 +1644,7 @@ extern "C" int l3_forward_dev(l3_ctx* c, const int32_t* ids_dev, int32_t B, int3
 extern "C" int l3_forward_host(l3_ctx* c, const int64_t* ids_host, int32_t B, int32_t L,
                                int32_t start_pos, float* logits_host) {
     CHECK_CTX(c);
+    if (kv_f32_only(c, "l3_forward_host")) return 1;
     if (need_model(c) || check_call(c, B, L, start_pos) || set_dev(c) || spec_resolve(c) || ensure_ws(c, B, L))
         return 1;
     if (upload_ids(c, ids_host, (int64_t)B * L)) return 1;
@@ -2117,6 +2146,7 @@ extern "C" int l3_sample_uniform(uint64_t seed, int32_t row, int32_t pos, float*
 extern "C" int l3_greedy_step_host(l3_ctx* c, const int64_t* ids_host, int32_t B, int32_t L,
                                    int32_t start_pos, int64_t* next_ids_host, float* logits_host) {
     CHECK_CTX(c);
+    if (kv_f32_only(c, "l3_greedy_step_host")) return 1;
     if (need_model(c) || check_call(c, B, L, start_pos) || set_dev(c) || ensure_ws(c, B, L) || persist_settle(c))
         return 1;
     if (!c->dec_ids) {
@@ -2347,12 +2377,14 @@ static int greedy_generate(l3_ctx* c, const int64_t* ids_host, int B, int L, int
 extern "C" int l3_greedy_generate_host(l3_ctx* c, const int64_t* ids_host, int32_t B, int32_t L,
                                        int32_t max_new_tokens, int64_t* out_ids_host) {
     CHECK_CTX(c);
+    if (kv_f32_only(c, "l3_greedy_generate_host")) return 1;
     return greedy_generate(c, ids_host, B, L, max_new_tokens, out_ids_host, nullptr);
 }
 
 extern "C" int l3_greedy_generate_values_host(l3_ctx* c, const int64_t* ids_host, int32_t B, int32_t L,
                                               int32_t max_new_tokens, int64_t* out_ids_host, float* out_vals) {
     CHECK_CTX(c);
+    if (kv_f32_only(c, "l3_greedy_generate_values_host")) return 1;
     if (!out_vals) return fail("l3_greedy_generate_values_host: null out_vals");
     return greedy_generate(c, ids_host, B, L, max_new_tokens, out_ids_host, out_vals);
 }
@@ -2482,18 +2514,28 @@ static int ragged_prefill(l3_ctx* c, const int64_t* ids_host, const int32_t* len
     lm.a_rows = rag_word(c, RAG_ROWS);
     if (timed(c, L3_K_LMHEAD, [&] { return gemm(c, EPI_STORE, lm, c->stream); })) return 1;
     for (auto& Ly : c->layers)
-        HIP_TRY(launch_ragged_zero_tail(Ly.cache_k, Ly.cache_v, rag_word(c, RAG_LEN), B, c->d.n_kv_heads,
+        HIP_TRY(launch_ragged_zero_tail(Ly.cache_k, Ly.cache_v, c->kv_dtype, rag_word(c, RAG_LEN), B, c->d.n_kv_heads,
                                         c->d.max_seq_len, c->HD, Lmax, c->stream));
     return 0;
 }
+
+static int ragged_shape_check(const l3_ctx* c, const char* who);
+static int ragged_extend_ws(l3_ctx* c, const char* who, int64_t rows);
+static int ragged_prefill_kv(l3_ctx* c, const int64_t* ids_host, const int32_t* lens, int B, int Lmax,
+                             int max_new_tokens);
 
 extern "C" int l3_ragged_forward_host(l3_ctx* c, const int64_t* ids_host, const int32_t* lens, int32_t B,
                                       int32_t Lmax, float* logits_host) {
     CHECK_CTX(c);
     if (!logits_host) return fail("l3_ragged_forward_host: null argument");
-    if (ragged_check(c, "l3_ragged_forward_host", ids_host, lens, B, Lmax)) return 1;
-    if (set_dev(c) || spec_resolve(c) || ensure_ws(c, B, Lmax) || ragged_bufs(c)) return 1;
-    if (ragged_prefill(c, ids_host, lens, B, Lmax, 0)) return 1;
+    const char* who = "l3_ragged_forward_host";
+    const bool kv = c->kv_dtype != L3_KV_F32;  // a bf16 cache: the prefill as an extend from 0 (ragged_prefill_kv)
+    if (ragged_check(c, who, ids_host, lens, B, Lmax)) return 1;
+    if (kv && ragged_shape_check(c, who)) return 1;
+    if (set_dev(c) || spec_resolve(c)) return 1;
+    if (kv && ragged_extend_ws(c, who, (int64_t)B * Lmax)) return 1;
+    if (ensure_ws(c, B, Lmax) || ragged_bufs(c)) return 1;
+    if (kv ? ragged_prefill_kv(c, ids_host, lens, B, Lmax, 0) : ragged_prefill(c, ids_host, lens, B, Lmax, 0)) return 1;
     HIP_TRY(hipMemcpyAsync(logits_host, c->logits, (size_t)B * c->d.vocab_size * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
@@ -2521,7 +2563,7 @@ static int ragged_step(l3_ctx* c, int B, int s_cap, int chunk) {
         if (li == 0) { g.A = c->emb; g.a_rows = cur; }
         if (timed(c, L3_K_QKV, [&] { return gemm(c, EPI_STORE, g, s); })) return 1;
         RaggedAttnArgs a{};
-        a.qkv = c->rag_qkv; a.cache_k = Ly.cache_k; a.cache_v = Ly.cache_v; a.out = c->attn;
+        a.qkv = c->rag_qkv; a.cache_k = Ly.cache_k; a.cache_v = Ly.cache_v; a.kv_dtype = c->kv_dtype; a.out = c->attn;
         a.rope_cos = c->rope_cos; a.rope_sin = c->rope_sin;
         a.pos = rag_word(c, RAG_POS); a.finished = rag_word(c, RAG_FIN);
         a.B = B; a.H = c->d.n_heads; a.KVH = c->d.n_kv_heads; a.HD = c->HD; a.Smax = c->d.max_seq_len;
@@ -2668,7 +2710,7 @@ static int ragged_extend_layers(l3_ctx* c, int B, int Lmax, bool skinny) {
         g.force_skinny = skinny;
         if (timed(c, L3_K_QKV, [&] { return gemm(c, EPI_STORE, g, s); })) return 1;
         ExtendAttnArgs a{};
-        a.qkv = c->rag_ext_qkv; a.cache_k = Ly.cache_k; a.cache_v = Ly.cache_v; a.out = c->attn;
+        a.qkv = c->rag_ext_qkv; a.cache_k = Ly.cache_k; a.cache_v = Ly.cache_v; a.kv_dtype = c->kv_dtype; a.out = c->attn;
         a.rope_cos = c->rope_cos; a.rope_sin = c->rope_sin;
         a.starts = rag_word(c, RAG_EXT_START); a.lens = rag_word(c, RAG_EXT_LEN);
         a.B = B; a.Lq = Lmax; a.H = c->d.n_heads; a.KVH = c->d.n_kv_heads; a.HD = c->HD; a.Smax = c->d.max_seq_len;
@@ -2692,6 +2734,20 @@ static int ragged_extend_layers(l3_ctx* c, int B, int Lmax, bool skinny) {
         gu.force_skinny = dn.force_skinny = skinny;
         if (ffn_pair(c, gu, dn, s)) return 1;
     }
+    return 0;
+}
+
+// The prefill at position 0 in a bf16 context.  run_layer's fused QKV epilogue writes, and
+// attn_fwd_kernel reads, fp32 caches, so the prefill runs as the extend with every start 0; the
+// pads' slots are then cleared, which leaves the fp32 prefill's cache contract: slots [0, lens[b])
+// written, [lens[b], Lmax) zero.  The caller has made the extend's workspace (ragged_extend_ws).
+static int ragged_prefill_kv(l3_ctx* c, const int64_t* ids_host, const int32_t* lens, int B, int Lmax,
+                             int max_new_tokens) {
+    const std::vector<int32_t> starts((size_t)B, 0);
+    if (ragged_extend_run(c, ids_host, lens, starts.data(), B, Lmax, max_new_tokens)) return 1;
+    for (auto& Ly : c->layers)
+        HIP_TRY(launch_ragged_zero_tail(Ly.cache_k, Ly.cache_v, c->kv_dtype, rag_word(c, RAG_LEN), B, c->d.n_kv_heads,
+                                        c->d.max_seq_len, c->HD, Lmax, c->stream));
     return 0;
 }
 
@@ -2774,7 +2830,8 @@ static int ragged_generate(l3_ctx* c, const char* who, const int64_t* ids_host, 
     if (set_dev(c) || spec_resolve(c)) return 1;
     if (split && ragged_split_ws(c, who, attn_decode_split_n(s_cap, chunk))) return 1;
     const int Lq = sp ? 1 + sp->draft_len : 0;  // rows of a speculative chunk
-    const int Lrows = starts && Lmax > Lq ? Lmax : Lq;
+    const bool kv = c->kv_dtype != L3_KV_F32;  // a bf16 cache: the prefill as an extend from 0 (ragged_prefill_kv)
+    const int Lrows = (starts || kv) && Lmax > Lq ? Lmax : Lq;
     if (Lrows && ragged_extend_ws(c, who, (int64_t)B * Lrows)) return 1;
     if (sp && draft_ws_ensure(c, who, (int64_t)B * Lq, (int64_t)B * ((sp->lookup ? sp->Lk : 0) + Lmax + cap), B)) return 1;
     if (ensure_ws(c, B, Lmax > Lq ? Lmax : Lq) || ragged_bufs(c)) return 1;
@@ -2804,14 +2861,17 @@ static int ragged_generate(l3_ctx* c, const char* who, const int64_t* ids_host, 
     }
     HIP_TRY(hipMemsetAsync(c->rag_out, 0xFF, (size_t)n_out_ids * 4, c->stream));  // -1
     if (!starts) {
-        if (ragged_prefill(c, ids_host, lens, B, Lmax, max_new_tokens)) return 1;
+        if (kv ? ragged_prefill_kv(c, ids_host, lens, B, Lmax, max_new_tokens)
+               : ragged_prefill(c, ids_host, lens, B, Lmax, max_new_tokens))
+            return 1;
     } else {
         if (ragged_extend_run(c, ids_host, lens, starts, B, Lmax, max_new_tokens)) return 1;
         // slot T_b, which the loop never writes and every later step attends: a row run alone on a
         // cache that is zero past its frontier finds zero there, whatever an earlier call left
         for (auto& Ly : c->layers)
-            HIP_TRY(launch_ragged_zero_slot(Ly.cache_k, Ly.cache_v, rag_word(c, RAG_LEN), rag_word(c, RAG_BUDGET), B,
-                                            c->d.n_kv_heads, c->d.max_seq_len, c->HD, c->stream));
+            HIP_TRY(launch_ragged_zero_slot(Ly.cache_k, Ly.cache_v, c->kv_dtype, rag_word(c, RAG_LEN),
+                                            rag_word(c, RAG_BUDGET), B, c->d.n_kv_heads, c->d.max_seq_len, c->HD,
+                                            c->stream));
     }
     RaggedState st{};
     st.pos = rag_word(c, RAG_POS); st.cur_id = rag_word(c, RAG_CUR); st.finished = rag_word(c, RAG_FIN);
@@ -3063,6 +3123,7 @@ extern "C" int l3_ragged_verify_host(l3_ctx* c, const int64_t* ids_host, const i
 extern "C" int l3_layer_forward_host(l3_ctx* c, int32_t layer, const float* x_host, int32_t B,
                                      int32_t L, int32_t start_pos, float* out_host) {
     CHECK_CTX(c);
+    if (kv_f32_only(c, "l3_layer_forward_host")) return 1;
     if (layer < 0 || layer >= (int)c->layers.size()) return fail("layer %d out of range", layer);
     if (need_layer(c, layer, NEED_LAYER) || check_call(c, B, L, start_pos) || set_dev(c) ||
         spec_resolve(c) || ensure_ws(c, B, L))
@@ -3080,6 +3141,7 @@ extern "C" int l3_layer_forward_host(l3_ctx* c, int32_t layer, const float* x_ho
 extern "C" int l3_attention_forward_host(l3_ctx* c, int32_t layer, const float* x_host, int32_t B,
                                          int32_t L, int32_t start_pos, float* out_host) {
     CHECK_CTX(c);
+    if (kv_f32_only(c, "l3_attention_forward_host")) return 1;
     if (layer < 0 || layer >= (int)c->layers.size()) return fail("layer %d out of range", layer);
     if (need_layer(c, layer, NEED_ATTN) || check_call(c, B, L, start_pos) || set_dev(c) ||
         spec_resolve(c) || ensure_ws(c, B, L))
@@ -3284,13 +3346,16 @@ extern "C" int l3_op_rope_host(l3_ctx* c, const float* x, int32_t B, int32_t L, 
 
 // One ragged decode-attention launch on plain arrays (ragged.hip): split 0 the single-pass kernel,
 // else the split-KV form at that chunk length — the A/B between the two on identical inputs.
-// cache_k / cache_v [B, KVH, Smax, HD] are copied in and, with slot pos[b] appended, back out.
-extern "C" int l3_op_attn_decode_ragged_host(l3_ctx* c, const float* qkv, float* cache_k, float* cache_v,
-                                             const float* rope_cos, const float* rope_sin, const int32_t* pos,
-                                             const int32_t* finished, int32_t B, int32_t H, int32_t KVH, int32_t HD,
-                                             int32_t Smax, int32_t s_cap, int32_t split, float* out) {
+// cache_k / cache_v [B, KVH, Smax, HD] are copied in and, with slot pos[b] appended, back out:
+// floats for L3_KV_F32, uint16 bf16 bit patterns for L3_KV_BF16.
+extern "C" int l3_op_attn_decode_ragged_kv_host(l3_ctx* c, const float* qkv, void* cache_k, void* cache_v,
+                                                int32_t kv_dtype, const float* rope_cos, const float* rope_sin,
+                                                const int32_t* pos, const int32_t* finished, int32_t B, int32_t H,
+                                                int32_t KVH, int32_t HD, int32_t Smax, int32_t s_cap, int32_t split,
+                                                float* out) {
     CHECK_CTX(c);
     const char* who = "l3_op_attn_decode_ragged";
+    if (!kv_dtype_ok(kv_dtype)) return fail("%s: kv_dtype %d (L3_KV_F32 = 0, L3_KV_BF16 = 1)", who, kv_dtype);
     if (!qkv || !cache_k || !cache_v || !rope_cos || !rope_sin || !pos || !finished || !out)
         return fail("%s: null argument", who);
     if (B < 1 || B > 65535 || Smax < 1 || s_cap < 1 || s_cap > Smax)
@@ -3311,8 +3376,9 @@ extern "C" int l3_op_attn_decode_ragged_host(l3_ctx* c, const float* qkv, float*
     const int n_split = split ? attn_decode_split_n(s_cap, split) : 0;
     Scratch S{c};
     SCRATCH(dq, nq);
-    SCRATCH(dk, nc);
-    SCRATCH(dv, nc);
+    const size_t cb = (size_t)nc * kv_elem_bytes(kv_dtype);  // bytes of a cache
+    SCRATCH(dk, (int64_t)((cb + 3) / 4));
+    SCRATCH(dv, (int64_t)((cb + 3) / 4));
     SCRATCH(dc, nt);
     SCRATCH(ds, nt);
     SCRATCH(dp, B);
@@ -3320,14 +3386,14 @@ extern "C" int l3_op_attn_decode_ragged_host(l3_ctx* c, const float* qkv, float*
     SCRATCH(dout, no);
     SCRATCH(dws, attn_decode_split_ws_floats(B, H, HD, n_split));
     H2D(dq, qkv, nq);
-    H2D(dk, cache_k, nc);
-    H2D(dv, cache_v, nc);
+    HIP_TRY(hipMemcpyAsync(dk, cache_k, cb, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dv, cache_v, cb, hipMemcpyHostToDevice, c->stream));
     H2D(dc, rope_cos, nt);
     H2D(ds, rope_sin, nt);
     H2D(dp, pos, B);
     H2D(df, finished, B);
     RaggedAttnArgs a{};
-    a.qkv = dq; a.cache_k = dk; a.cache_v = dv; a.out = dout; a.rope_cos = dc; a.rope_sin = ds;
+    a.qkv = dq; a.cache_k = dk; a.cache_v = dv; a.kv_dtype = kv_dtype; a.out = dout; a.rope_cos = dc; a.rope_sin = ds;
     a.pos = reinterpret_cast<const int32_t*>(dp); a.finished = reinterpret_cast<const int32_t*>(df);
     a.B = B; a.H = H; a.KVH = KVH; a.HD = HD; a.Smax = Smax; a.s_cap = s_cap;
     a.q_scale = (float)(1.4426950408889634 / std::sqrt((double)HD));
@@ -3338,8 +3404,8 @@ extern "C" int l3_op_attn_decode_ragged_host(l3_ctx* c, const float* qkv, float*
         }))
         return 1;
     D2H(out, dout, no);
-    D2H(cache_k, dk, nc);
-    D2H(cache_v, dv, nc);
+    HIP_TRY(hipMemcpyAsync(cache_k, dk, cb, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(cache_v, dv, cb, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -3347,12 +3413,14 @@ extern "C" int l3_op_attn_decode_ragged_host(l3_ctx* c, const float* qkv, float*
 // The two launches of a ragged extend on plain arrays (ragged_extend.hip): the append of the new
 // keys / values, then the attention.  cache_k / cache_v [B, KVH, Smax, HD] are copied in and, with
 // slots [starts[b], starts[b] + lens[b]) written, back out; lens[b] may be 0 (an all-pad row).
-extern "C" int l3_op_attn_extend_ragged_host(l3_ctx* c, const float* qkv, float* cache_k, float* cache_v,
-                                             const float* rope_cos, const float* rope_sin, const int32_t* starts,
-                                             const int32_t* lens, int32_t B, int32_t Lq, int32_t H, int32_t KVH,
-                                             int32_t HD, int32_t Smax, float* out) {
+// Floats for L3_KV_F32, uint16 bf16 bit patterns for L3_KV_BF16.
+extern "C" int l3_op_attn_extend_ragged_kv_host(l3_ctx* c, const float* qkv, void* cache_k, void* cache_v,
+                                                int32_t kv_dtype, const float* rope_cos, const float* rope_sin,
+                                                const int32_t* starts, const int32_t* lens, int32_t B, int32_t Lq,
+                                                int32_t H, int32_t KVH, int32_t HD, int32_t Smax, float* out) {
     CHECK_CTX(c);
     const char* who = "l3_op_attn_extend_ragged";
+    if (!kv_dtype_ok(kv_dtype)) return fail("%s: kv_dtype %d (L3_KV_F32 = 0, L3_KV_BF16 = 1)", who, kv_dtype);
     if (!qkv || !cache_k || !cache_v || !rope_cos || !rope_sin || !starts || !lens || !out)
         return fail("%s: null argument", who);
     if (B < 1 || B > 65535 || Lq < 1 || Smax < 1)
@@ -3372,31 +3440,49 @@ extern "C" int l3_op_attn_extend_ragged_host(l3_ctx* c, const float* qkv, float*
     const int64_t nt = (int64_t)Smax * (HD / 2), no = (int64_t)B * Lq * H * HD;
     Scratch S{c};
     SCRATCH(dq, nq);
-    SCRATCH(dk, nc);
-    SCRATCH(dv, nc);
+    const size_t cb = (size_t)nc * kv_elem_bytes(kv_dtype);  // bytes of a cache
+    SCRATCH(dk, (int64_t)((cb + 3) / 4));
+    SCRATCH(dv, (int64_t)((cb + 3) / 4));
     SCRATCH(dc, nt);
     SCRATCH(ds, nt);
     SCRATCH(dst, B);
     SCRATCH(dl, B);
     SCRATCH(dout, no);
     H2D(dq, qkv, nq);
-    H2D(dk, cache_k, nc);
-    H2D(dv, cache_v, nc);
+    HIP_TRY(hipMemcpyAsync(dk, cache_k, cb, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dv, cache_v, cb, hipMemcpyHostToDevice, c->stream));
     H2D(dc, rope_cos, nt);
     H2D(ds, rope_sin, nt);
     H2D(dst, starts, B);
     H2D(dl, lens, B);
     ExtendAttnArgs a{};
-    a.qkv = dq; a.cache_k = dk; a.cache_v = dv; a.out = dout; a.rope_cos = dc; a.rope_sin = ds;
+    a.qkv = dq; a.cache_k = dk; a.cache_v = dv; a.kv_dtype = kv_dtype; a.out = dout; a.rope_cos = dc; a.rope_sin = ds;
     a.starts = reinterpret_cast<const int32_t*>(dst); a.lens = reinterpret_cast<const int32_t*>(dl);
     a.B = B; a.Lq = Lq; a.H = H; a.KVH = KVH; a.HD = HD; a.Smax = Smax;
     a.q_scale = (float)(1.4426950408889634 / std::sqrt((double)HD));
     if (timed(c, L3_K_ATTN, [&] { return launch_attn_extend_ragged(a, c->stream); })) return 1;
     D2H(out, dout, no);
-    D2H(cache_k, dk, nc);
-    D2H(cache_v, dv, nc);
+    HIP_TRY(hipMemcpyAsync(cache_k, dk, cb, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(cache_v, dv, cb, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
+}
+
+// the two ops above on fp32 caches
+extern "C" int l3_op_attn_decode_ragged_host(l3_ctx* c, const float* qkv, float* cache_k, float* cache_v,
+                                             const float* rope_cos, const float* rope_sin, const int32_t* pos,
+                                             const int32_t* finished, int32_t B, int32_t H, int32_t KVH, int32_t HD,
+                                             int32_t Smax, int32_t s_cap, int32_t split, float* out) {
+    return l3_op_attn_decode_ragged_kv_host(c, qkv, cache_k, cache_v, L3_KV_F32, rope_cos, rope_sin, pos, finished, B,
+                                            H, KVH, HD, Smax, s_cap, split, out);
+}
+
+extern "C" int l3_op_attn_extend_ragged_host(l3_ctx* c, const float* qkv, float* cache_k, float* cache_v,
+                                             const float* rope_cos, const float* rope_sin, const int32_t* starts,
+                                             const int32_t* lens, int32_t B, int32_t Lq, int32_t H, int32_t KVH,
+                                             int32_t HD, int32_t Smax, float* out) {
+    return l3_op_attn_extend_ragged_kv_host(c, qkv, cache_k, cache_v, L3_KV_F32, rope_cos, rope_sin, starts, lens, B,
+                                            Lq, H, KVH, HD, Smax, out);
 }
 
 // The fork of a cache row (DESIGN.md "Ragged continuation"): slots [0, n_slots) of K and V in every
@@ -3426,9 +3512,51 @@ extern "C" int l3_cache_copy_rows(l3_ctx* c, int32_t src_row, const int32_t* dst
     int32_t* dst_dev = rag_word(c, RAG_TOK);  // free between calls: a step's token choice writes it
     HIP_TRY(hipMemcpyAsync(dst_dev, dst_rows, (size_t)n_dst * 4, hipMemcpyHostToDevice, c->stream));
     for (auto& Ly : c->layers)
-        HIP_TRY(launch_cache_copy_rows(Ly.cache_k, Ly.cache_v, src_row, dst_dev, n_dst, c->d.n_kv_heads,
+        HIP_TRY(launch_cache_copy_rows(Ly.cache_k, Ly.cache_v, c->kv_dtype, src_row, dst_dev, n_dst, c->d.n_kv_heads,
                                        c->d.max_seq_len, c->HD, n_slots, mb, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));  // dst_rows is the caller's: read before the return
+    return 0;
+}
+
+extern "C" int l3_kv_info(l3_ctx* c, int32_t* dtype, int64_t* bytes) {
+    CHECK_CTX(c);
+    if (dtype) *dtype = c->kv_dtype;
+    if (bytes) *bytes = 2 * (int64_t)c->layers.size() * kv_cache_bytes(c);
+    return 0;
+}
+
+// Slots [slot0, slot0 + n_slots) of one cache row of one layer, every KV head, as fp32 on the host:
+// one strided copy per cache (a head's run of slots is contiguous), then a bf16 cache widened
+// exactly (bits << 16)
+extern "C" int l3_cache_read_host(l3_ctx* c, int32_t layer, int32_t row, int32_t slot0, int32_t n_slots, float* k_out,
+                                  float* v_out) {
+    CHECK_CTX(c);
+    const char* who = "l3_cache_read_host";
+    if (!k_out || !v_out) return fail("%s: null argument", who);
+    if (layer < 0 || layer >= (int)c->layers.size()) return fail("%s: layer %d outside [0, %d)", who, layer, (int)c->layers.size());
+    if (row < 0 || row >= c->d.max_batch_size) return fail("%s: row %d outside [0, %d)", who, row, c->d.max_batch_size);
+    if (slot0 < 0 || n_slots < 0 || (int64_t)slot0 + n_slots > c->d.max_seq_len)
+        return fail("%s: slots [%d, %lld) outside [0, %d]", who, slot0, (long long)slot0 + n_slots, c->d.max_seq_len);
+    if (set_dev(c) || spec_resolve(c)) return 1;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (n_slots == 0) return 0;
+    const int KVH = c->d.n_kv_heads, HD = c->HD, eb = kv_elem_bytes(c->kv_dtype);
+    const size_t run = (size_t)n_slots * HD * eb, pitch = (size_t)c->d.max_seq_len * HD * eb;
+    const size_t off = (((size_t)row * KVH) * c->d.max_seq_len + slot0) * HD * eb;
+    const Layer& Ly = c->layers[(size_t)layer];
+    const int64_t n = (int64_t)KVH * n_slots * HD;
+    float* outs[2] = {k_out, v_out};
+    const float* caches[2] = {Ly.cache_k, Ly.cache_v};
+    std::vector<uint16_t> bits(c->kv_dtype == L3_KV_BF16 ? (size_t)n : 0);
+    for (int i = 0; i < 2; ++i) {
+        const char* src = reinterpret_cast<const char*>(caches[i]) + off;
+        void* dst = bits.empty() ? (void*)outs[i] : (void*)bits.data();
+        HIP_TRY(hipMemcpy2D(dst, run, src, pitch, run, (size_t)KVH, hipMemcpyDeviceToHost));
+        for (int64_t j = 0; j < (int64_t)bits.size(); ++j) {
+            const uint32_t w = (uint32_t)bits[(size_t)j] << 16;
+            memcpy(outs[i] + j, &w, 4);
+        }
+    }
     return 0;
 }
 
@@ -4009,6 +4137,7 @@ static int check_targets(const char* who, const Tgt* t, int64_t T, int64_t N) {
 extern "C" int l3_score_host(l3_ctx* c, const int64_t* ids_host, const int64_t* targets_host, int32_t B, int32_t L,
                              int32_t start_pos, float* logprobs_host, int32_t* argmax_host) {
     CHECK_CTX(c);
+    if (kv_f32_only(c, "l3_score_host")) return 1;
     if (need_model(c) || check_call(c, B, L, start_pos)) return 1;
     if (!ids_host || !targets_host || !logprobs_host) return fail("l3_score_host: null argument");
     if (c->group && group_members(c->group) > 1)
@@ -4517,6 +4646,7 @@ extern "C" int l3_group_create(int32_t ndev, const int32_t* devices, const l3_di
     local.max_batch_size = (dims->max_batch_size + ndev - 1) / ndev;
     g->m.assign((size_t)ndev, nullptr);
     for (int i = 0; i < ndev; ++i)
+        // (members are fp32-cache contexts: no l3_group entry point meets a bf16 cache)
         if (l3_create(devices[i], &local, &g->m[(size_t)i])) {
             const std::string e = g_err;
             l3_group_destroy(g);

@@ -54,6 +54,13 @@ _SIGNATURES = {
     "l3_host_alloc": (ctypes.c_int, [_SZ, _P]),
     "l3_host_free": (ctypes.c_int, [_P]),
     "l3_create": (ctypes.c_int, [_I32, _P, _P]),
+    "l3_create_kv": (ctypes.c_int, [_I32, _P, _I32, _P]),
+    "l3_kv_info": (ctypes.c_int, [_P, _P, _P]),
+    "l3_cache_read_host": (ctypes.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P]),
+    "l3_op_attn_decode_ragged_kv_host": (ctypes.c_int, [_P, _P, _P, _P, _I32, _P, _P, _P, _P, _I32, _I32, _I32, _I32,
+                                                        _I32, _I32, _I32, _P]),
+    "l3_op_attn_extend_ragged_kv_host": (ctypes.c_int, [_P, _P, _P, _P, _I32, _P, _P, _P, _P, _I32, _I32, _I32, _I32,
+                                                        _I32, _I32, _P]),
     "l3_destroy": (ctypes.c_int, [_P]),
     "l3_upload_weight": (ctypes.c_int, [_P, _I32, _I32, _P, _I64, _I64]),
     "l3_finalize": (ctypes.c_int, [_P]),
@@ -342,12 +349,40 @@ def device_count() -> int:
     return n.value
 
 
-class Context:
-    """Owns one device context (weights, KV caches, workspace) on one GPU."""
+# KV-cache storage types (enum l3_kv_dtype) by the name ``Context(..., kv_dtype=...)`` takes
+KV_DTYPES = {None: 0, "bf16": 1}
 
-    def __init__(self, dims: Dims, device: int = 0):
+
+def kv_dtype_code(kv_dtype) -> int:
+    """The ``l3_kv_dtype`` code of ``kv_dtype`` (None: fp32, "bf16"); ValueError for anything else."""
+    if not (kv_dtype is None or isinstance(kv_dtype, str)) or kv_dtype not in KV_DTYPES:
+        raise ValueError(f"kv_dtype {kv_dtype!r}: None (fp32) or 'bf16'")
+    return KV_DTYPES[kv_dtype]
+
+
+def _kv_caches(cache_k, cache_v):
+    """Contiguous copies of an op's caches and their l3_kv_dtype code: uint16 arrays are bf16 bit
+    patterns, anything else is taken as fp32."""
+    bf = np.asarray(cache_k).dtype == np.uint16
+    if bf != (np.asarray(cache_v).dtype == np.uint16):
+        raise ValueError("cache_k and cache_v must both be uint16 (bf16 bits) or both fp32")
+    dt = np.uint16 if bf else np.float32
+    return np.array(cache_k, dtype=dt, order="C"), np.array(cache_v, dtype=dt, order="C"), int(bf)
+
+
+class Context:
+    """Owns one device context (weights, KV caches, workspace) on one GPU.  ``kv_dtype`` (extension;
+    DESIGN.md "bf16 KV-cache storage"): None, the fp32 caches; "bf16", caches of two bytes per
+    element that only the ragged entry points serve (l3_create_kv)."""
+
+    def __init__(self, dims: Dims, device: int = 0, kv_dtype=None):
+        code = kv_dtype_code(kv_dtype)
         self._h = ctypes.c_void_p()
-        check(lib().l3_create(device, ctypes.byref(dims), ctypes.byref(self._h)))
+        if code:
+            check(lib().l3_create_kv(device, ctypes.byref(dims), code, ctypes.byref(self._h)))
+        else:
+            check(lib().l3_create(device, ctypes.byref(dims), ctypes.byref(self._h)))
+        self.kv_dtype = kv_dtype
         self.dims = dims
         self.device = device
         self._owned = True
@@ -358,6 +393,7 @@ class Context:
         which keeps the group alive)."""
         c = cls.__new__(cls)
         c._h, c.dims, c.device, c._owned, c._group = handle, dims, device, False, group
+        c.kv_dtype = None  # a group's members are fp32 contexts
         return c
 
     @property
@@ -386,6 +422,21 @@ class Context:
 
     def reset_cache(self) -> None:
         check(lib().l3_reset_cache(self._h))
+
+    def kv_info(self) -> dict:
+        """The KV-cache storage type (None or "bf16") and the bytes of all layers' K and V
+        allocations (l3_kv_info)."""
+        dt, n = ctypes.c_int32(0), ctypes.c_int64(0)
+        check(lib().l3_kv_info(self._h, ctypes.byref(dt), ctypes.byref(n)))
+        return {"dtype": {v: k for k, v in KV_DTYPES.items()}[dt.value], "bytes": n.value}
+
+    def cache_read(self, layer: int, row: int, slot0: int, n: int):
+        """Slots ``[slot0, slot0 + n)`` of cache row ``row`` of one layer (l3_cache_read_host):
+        (k, v), each [n_kv_heads, n, head_dim] fp32 — a bf16 cache's values widened exactly."""
+        shape = (self.dims.n_kv_heads, max(int(n), 0), self.dims.dim // self.dims.n_heads)
+        k, v = np.empty(shape, np.float32), np.empty(shape, np.float32)
+        check(lib().l3_cache_read_host(self._h, int(layer), int(row), int(slot0), int(n), ptr(k), ptr(v)))
+        return k, v
 
     # ---- forward ----
     def forward(self, ids: np.ndarray, start_pos: int) -> np.ndarray:
@@ -590,9 +641,9 @@ class Context:
         ``qkv`` [B, Lq, (H + 2 KVH) * HD] raw rows, ``cache_k`` / ``cache_v`` [B, KVH, Smax, HD],
         ``rope_cos`` / ``rope_sin`` [Smax, HD/2], ``starts`` / ``lens`` [B].  Returns
         (out [B, Lq, H * HD], cache_k, cache_v) — the caches are copies with slots
-        ``[starts[b], starts[b] + lens[b])`` written."""
-        ck = np.array(cache_k, dtype=np.float32, order="C")
-        cv = np.array(cache_v, dtype=np.float32, order="C")
+        ``[starts[b], starts[b] + lens[b])`` written.  uint16 caches are bf16 bit patterns
+        (l3_op_attn_extend_ragged_kv_host): the new K / V are rounded as they are stored."""
+        ck, cv, kv = _kv_caches(cache_k, cache_v)
         if ck.ndim != 4 or cv.shape != ck.shape:
             raise ValueError(f"cache_k {ck.shape} / cache_v {cv.shape} must be [B, KVH, Smax, HD]")
         B, KVH, Smax, HD = ck.shape
@@ -609,6 +660,10 @@ class Context:
             raise ValueError(f"starts {starts.shape} and lens {lens.shape} must be [{B}]")
         Lq = qkv.shape[1]
         out = np.empty((B, Lq, H * HD), np.float32)
+        if kv:
+            check(lib().l3_op_attn_extend_ragged_kv_host(self._h, ptr(qkv), ptr(ck), ptr(cv), kv, ptr(c), ptr(s),
+                                                         ptr(starts), ptr(lens), B, Lq, H, KVH, HD, Smax, ptr(out)))
+            return out, ck, cv
         check(lib().l3_op_attn_extend_ragged_host(self._h, ptr(qkv), ptr(ck), ptr(cv), ptr(c), ptr(s), ptr(starts),
                                                   ptr(lens), B, Lq, H, KVH, HD, Smax, ptr(out)))
         return out, ck, cv
@@ -633,9 +688,10 @@ class Context:
         ``qkv`` [B, (H + 2 KVH) * HD] raw rows, ``cache_k`` / ``cache_v`` [B, KVH, Smax, HD],
         ``rope_cos`` / ``rope_sin`` [Smax, HD/2], ``pos`` / ``finished`` [B]; ``split`` 0 runs the
         single-pass kernel, else the split-KV form at that chunk length.  Returns
-        (out [B, H * HD], cache_k, cache_v) — the caches are copies with slot ``pos[b]`` appended."""
-        ck = np.array(cache_k, dtype=np.float32, order="C")
-        cv = np.array(cache_v, dtype=np.float32, order="C")
+        (out [B, H * HD], cache_k, cache_v) — the caches are copies with slot ``pos[b]`` appended.
+        uint16 caches are bf16 bit patterns (l3_op_attn_decode_ragged_kv_host): the new k / v are
+        rounded as they are stored, and used as rounded."""
+        ck, cv, kv = _kv_caches(cache_k, cache_v)
         if ck.ndim != 4 or cv.shape != ck.shape:
             raise ValueError(f"cache_k {ck.shape} / cache_v {cv.shape} must be [B, KVH, Smax, HD]")
         B, KVH, Smax, HD = ck.shape
@@ -650,6 +706,11 @@ class Context:
         if pos.shape != (B,) or fin.shape != (B,):
             raise ValueError(f"pos {pos.shape} and finished {fin.shape} must be [{B}]")
         out = np.empty((B, H * HD), np.float32)
+        if kv:
+            check(lib().l3_op_attn_decode_ragged_kv_host(self._h, ptr(qkv), ptr(ck), ptr(cv), kv, ptr(c), ptr(s),
+                                                         ptr(pos), ptr(fin), B, H, KVH, HD, Smax, int(s_cap), int(split),
+                                                         ptr(out)))
+            return out, ck, cv
         check(lib().l3_op_attn_decode_ragged_host(self._h, ptr(qkv), ptr(ck), ptr(cv), ptr(c), ptr(s), ptr(pos),
                                                   ptr(fin), B, H, KVH, HD, Smax, int(s_cap), int(split), ptr(out)))
         return out, ck, cv

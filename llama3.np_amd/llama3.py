@@ -130,6 +130,14 @@ def _dims(args: ModelArgs, hidden_dim: int, n_layers: int, vocab_size: int) -> l
                       max_batch_size=args.max_batch_size, norm_eps=args.norm_eps)
 
 
+def _kv_f32_only(ctx, what: str) -> None:
+    """The module-level calls run the fp32-cache kernels: refused on a ``kv_dtype="bf16"`` model."""
+    kv = getattr(ctx, "kv_dtype", None)
+    if kv is not None:
+        raise NotImplementedError(f"{what} on a model with kv_dtype={kv!r}: its kernels read and write an fp32 KV "
+                                  "cache; use the model's ragged calls")
+
+
 def _check_freqs(freqs_cos, freqs_sin, L: int, head_dim: int) -> None:
     for f in (freqs_cos, freqs_sin):
         if f is not None and np.shape(f) != (L, head_dim // 2):
@@ -221,6 +229,7 @@ class Attention:
 
     def __call__(self, x, start_pos: int, mask, freqs_cos, freqs_sin):
         x = np.asarray(x)
+        _kv_f32_only(self._ctx, "Attention.__call__")
         _check_freqs(freqs_cos, freqs_sin, x.shape[1], self.head_dim)
         return self._ctx.attention_forward(self._layer, x, start_pos)
 
@@ -268,6 +277,7 @@ class TransformerBlock:
 
     def __call__(self, x, start_pos: int, mask, freqs_cos, freqs_sin):
         x = np.asarray(x)
+        _kv_f32_only(self._ctx, "TransformerBlock.__call__")
         _check_freqs(freqs_cos, freqs_sin, x.shape[1], self._head_dim)
         return self._ctx.layer_forward(self._layer, x, start_pos)
 
@@ -284,9 +294,23 @@ class Llama:
 
     def __init__(self, model_path: str, args: ModelArgs, device: Optional[int] = None,
                  keep_host_weights: bool = True, devices: Optional[Sequence[int]] = None,
-                 weight_dtype: Optional[str] = None, ragged_split: Optional[int] = None):
-        """``device`` / ``keep_host_weights`` / ``devices`` / ``weight_dtype`` / ``ragged_split``
-        are extensions.
+                 weight_dtype: Optional[str] = None, ragged_split: Optional[int] = None,
+                 kv_dtype: Optional[str] = None):
+        """``device`` / ``keep_host_weights`` / ``devices`` / ``weight_dtype`` / ``ragged_split`` /
+        ``kv_dtype`` are extensions.
+
+        ``kv_dtype`` (DESIGN.md "bf16 KV-cache storage"): ``None`` keeps the fp32 KV cache and
+        every path as it is; ``"bf16"`` stores K (after RoPE) and V at two bytes per element —
+        rounded to nearest-even once, as they enter the cache, and widened in registers by the
+        attention kernels, whose arithmetic stays fp32 — so a cached token costs half the memory
+        and a long-context decode step reads half the bytes.  The model computed is the one whose
+        keys and values are the rounded ones, on every path, the step's own token included.  Such
+        a model runs on the ragged kernels only: ``forward_ragged``, ``extend_ragged``,
+        ``generate_ragged`` (speculative or not), ``verify_ragged`` and ``fork_cache`` work as
+        documented, ``__call__`` / ``generate`` / ``generate_all`` are routed through them (see
+        there), and ``score`` and the module-level ``TransformerBlock`` / ``Attention`` calls raise
+        ``NotImplementedError``.  Anything but ``None`` / ``"bf16"`` raises ``ValueError``; not with
+        more than one device.
 
         ``ragged_split`` (DESIGN.md "Split-KV decode attention"): ``None`` leaves
         ``generate_ragged``'s decode attention on auto (the split-KV kernels only where the
@@ -327,6 +351,10 @@ class Llama:
                                       "not implemented")
         if ragged_split is not None and devices is not None and len(devices) > 1:
             raise NotImplementedError("ragged batches on a multi-device model: not implemented")
+        l3hip.kv_dtype_code(kv_dtype)  # ValueError before anything is read or allocated
+        if kv_dtype is not None and devices is not None and len(devices) > 1:
+            raise NotImplementedError(f"kv_dtype={kv_dtype!r} on a multi-device model: not implemented")
+        self.kv_dtype = kv_dtype
         keep = keep_host_weights
         pool = None
         if isinstance(model_path, Mapping):
@@ -349,7 +377,7 @@ class Llama:
                                                                args.max_seq_len)
         hidden = weight.get("model.layers.0.mlp.gate_proj.weight").shape[0]
         dims = _dims(args, hidden, args.n_layers, args.vocab_size)
-        if devices is not None:
+        if devices is not None and (kv_dtype is None or len(devices) > 1):
             if device is not None:
                 raise ValueError("pass device or devices, not both")
             self._group = l3hip.Group(dims, devices)
@@ -357,7 +385,11 @@ class Llama:
             tgt = self._group  # uploads go to every device; calls shard the batch rows
         else:
             self._group = None
-            self._ctx = l3hip.Context(dims, DEFAULT_DEVICE if device is None else device)
+            if devices is not None:  # kv_dtype with devices=[d]: a plain context on that device
+                if device is not None:
+                    raise ValueError("pass device or devices, not both")
+                device = devices[0]
+            self._ctx = l3hip.Context(dims, DEFAULT_DEVICE if device is None else device, kv_dtype=kv_dtype)
             tgt = self._ctx
         if weight_dtype is not None and weight_dtype.startswith("fp8"):
             self._ctx.set_weight_fp8(_WEIGHT_DTYPES[weight_dtype])
@@ -403,6 +435,8 @@ class Llama:
         ids = np.asarray(input_ids)
         if ids.ndim != 2:
             raise ValueError(f"input_ids must be [B, L], got shape {ids.shape}")
+        if self.kv_dtype is not None:  # the ragged extend of the rows, all at start_pos
+            return self.extend_ragged(list(ids), [int(start_pos)] * ids.shape[0])
         logits = self._target.forward(ids, int(start_pos))
         return logits[:, None, :]
 
@@ -432,6 +466,9 @@ class Llama:
         a long text can be scored piece by piece.  Not for a model on more than one device."""
         if self._group is not None and self._group.n > 1:
             raise NotImplementedError("scoring on a multi-device model: sharding it is not implemented")
+        if self.kv_dtype is not None:
+            raise NotImplementedError(f"scoring on a model with kv_dtype={self.kv_dtype!r}: its kernels read and "
+                                      "write an fp32 KV cache")
         ids = np.asarray(input_ids)
         if ids.ndim != 2:
             raise ValueError(f"input_ids must be [B, L], got shape {ids.shape}")
@@ -461,9 +498,15 @@ class Llama:
         reference's: the device may run up to 16 steps ahead of the consumer (never past
         max_new_tokens), and a schedule left early is undone before any later call.
         After ``set_sampling`` with a temperature above 0 the tokens are sampled, not the
-        argmax; the schedule, the laziness and the run-ahead are the same."""
+        argmax; the schedule, the laziness and the run-ahead are the same.  On a
+        ``kv_dtype="bf16"`` model the tokens are ``generate_ragged``'s (no stop ids), computed in
+        full before the first one is yielded: not lazy."""
         ids = np.asarray(input_ids)
         _, L = ids.shape
+        if self.kv_dtype is not None:
+            for col in self.generate_all(ids, max_new_tokens).T:
+                yield col.reshape(-1, 1)
+            return
         self._target.set_decode_horizon(max_new_tokens)
         next_id = None
         for i, curr_pos in enumerate(range(L, max_new_tokens)):
@@ -482,8 +525,12 @@ class Llama:
         runs, so use it when the caller consumes all tokens.  On a multi-device model a batch of
         more than one row steps through ``Group.greedy_step`` (each device its rows, the ids
         gathered) instead of the single-device graph loop.  After ``set_sampling`` the ids are
-        the sampled ones, identical to ``generate``'s for the same seed."""
+        the sampled ones, identical to ``generate``'s for the same seed.  On a ``kv_dtype="bf16"``
+        model: ``generate_ragged``'s ids of the rows (no stop ids)."""
         ids = np.asarray(input_ids)
+        if self.kv_dtype is not None:
+            rows = self.generate_ragged(list(ids), int(max_new_tokens))
+            return np.stack(rows).astype(np.int64)
         if self._group is None or self._group.n == 1 or ids.shape[0] == 1:
             return self._ctx.greedy_generate(ids, max_new_tokens)
         B, L = ids.shape
