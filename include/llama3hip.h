@@ -671,6 +671,37 @@ typedef struct l3_gemm_op {
     int32_t route[8];
 } l3_gemm_op;
 int l3_op_gemm_host(l3_ctx* ctx, l3_gemm_op* op);
+/* One dense attention launch on plain host arrays (tests/test_gpu_attn_dense.py): llama3.py:186-210
+ * for B sequences of L new tokens at positions start_pos + t, through exactly one call of the
+ * library's attention dispatcher, and a report of the kernel it chose.  Works on an op-only
+ * context.
+ *   q        [B * L, H * HD], as the kernels take it: already multiplied by log2(e) / sqrt(HD)
+ *   cache_k / cache_v  [B, KVH, Smax, HD] fp32, copied in; read-only for the launch, not copied back
+ *   mode     bit 0: 0 the full launch (every query row), 1 the last-rows launch of a pruned last
+ *            block (rows [max(0, L - QW), L) of each sequence, QW = 16 * 4 / G queries, G = the
+ *            largest of 4, 2, 1 that divides H / KVH; bit for bit the full launch's rows).
+ *            bit 1: the launch reads start_pos from a device word (the captured decode graph's
+ *            form) and its start_pos argument holds another value
+ *   wo       NULL, or [D, H * HD]: the decode launch with the O-proj fused (L == 1, Smax <= 8192,
+ *            D % 4 == 0); out is then parts [B, H, D], parts[b][h] = wo[:, h*HD:(h+1)*HD] . o[b][h]
+ *   out      in/out, out_rows >= B * L + 1 rows of H * HD floats (with wo: of H * D floats): all of
+ *            it is uploaded before the launch and downloaded after it, so every row the launch does
+ *            not own — the guard rows from B * L on, and with mode bit 0 the rows before the last
+ *            QW of each sequence — keeps the caller's bits
+ *   route    (out, may be NULL) int32[8]: [0] kernel (0 prefill, 1 decode, 2 decode + O-proj),
+ *            [1] HD, [2] QBW (16-query blocks per wave), [3] G (heads per workgroup), [4] KT (keys
+ *            per tile) — 0 for the decode kernels — [5..7] grid x, y, z
+ * Keys [0, start_pos + L) of each sequence are read; the prefill kernel also loads the rest of the
+ * last 16-key group it enters, [start_pos + L, roundup16(start_pos + L)), and multiplies it by a
+ * probability of exactly 0, so those slots must hold finite values (DESIGN.md "Dense attention at
+ * kernel level").
+ * Errors, each by name, out untouched and no other kernel standing in: a head size without an
+ * instantiation (16, 32, 48, 64, 96, 128); H % KVH != 0; wo with L != 1 or Smax > 8192; D % 4 != 0;
+ * mode bit 0 with wo or with bit 1; start_pos < 0 or start_pos + L > Smax; a null array,
+ * out_rows < B * L + 1. */
+int l3_op_attention_host(l3_ctx* ctx, const float* q, const float* cache_k, const float* cache_v, int32_t B,
+                         int32_t L, int32_t start_pos, int32_t H, int32_t KVH, int32_t HD, int32_t Smax,
+                         int32_t mode, const float* wo, int32_t D, float* out, int64_t out_rows, int32_t* route);
 /* The scoring path of l3_score_host (llama3.py:285-308 with the logits reduced in the lm_head's
  * epilogue) on a plain product: for z = x [rows, K] @ W[N, K]^T (no norm) and targets int32 [rows]
  * (-1: no target; else in [0, N)), logprob [rows], and optionally lse [rows] and argmax int32

@@ -668,8 +668,18 @@ hipError_t launch_qkv_table(const GemmArgs& a, hipStream_t s);
 hipError_t launch_embed_qkv(const EmbedQkvArgs& a, hipStream_t s);
 // W [rows][K] fp32 -> W3 [rows][3][K] bf16 pieces for the x6 path (gemm_x6.h)
 hipError_t launch_split_planes(const float* w, unsigned short* w3, int64_t rows, int K, hipStream_t s);
-hipError_t launch_attention(const AttnArgs& a, hipStream_t s);
-hipError_t launch_attention_last(const AttnArgs& a, hipStream_t s);
+// Which kernel an attention launch took (a host-side record filled where the template is chosen,
+// read by l3_op_attention_host; the GemmRoute precedent).  kernel: attn_fwd_kernel (ATTN_PREFILL:
+// HD, QBW, G, KT are its template arguments), attn_decode_kernel without / with the fused O-proj
+// (QBW = G = KT = 0).  ATTN_NONE: nothing was launched (a refusal, or B or L of 0)
+enum AttnRouteKernel : int { ATTN_NONE = -1, ATTN_PREFILL = 0, ATTN_DECODE = 1, ATTN_DECODE_OPROJ = 2 };
+struct AttnRoute {
+    int kernel = ATTN_NONE;
+    int HD = 0, QBW = 0, G = 0, KT = 0;
+    int grid[3] = {0, 0, 0};
+};
+hipError_t launch_attention(const AttnArgs& a, hipStream_t s, AttnRoute* route = nullptr);
+hipError_t launch_attention_last(const AttnArgs& a, hipStream_t s, AttnRoute* route = nullptr);
 hipError_t launch_argmax(const float* logits, int64_t rows, int n, int32_t* out, hipStream_t s,
                          DecState* st = nullptr);
 // the same result from the lm_head's partials: rows x nparts (GemmArgs::amax_part, one row;

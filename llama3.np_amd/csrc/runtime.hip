@@ -4055,6 +4055,86 @@ extern "C" int l3_op_gemm_host(l3_ctx* c, l3_gemm_op* op) {
     return 0;
 }
 
+// One launch_attention / launch_attention_last call on plain host arrays (include/llama3hip.h).
+// Only what would take an index outside a buffer is checked ahead of the dispatcher (null arrays,
+// sizes, the key range); every shape rule is the dispatcher's own, and what it refuses is named
+// here afterwards — no other kernel stands in, and out is not written.
+extern "C" int l3_op_attention_host(l3_ctx* c, const float* q, const float* cache_k, const float* cache_v, int32_t B,
+                                    int32_t L, int32_t start_pos, int32_t H, int32_t KVH, int32_t HD, int32_t Smax,
+                                    int32_t mode, const float* wo, int32_t D, float* out, int64_t out_rows,
+                                    int32_t* route) {
+    CHECK_CTX(c);
+    const char* who = "l3_op_attention";
+    if (route)
+        for (int i = 0; i < 8; ++i) route[i] = 0;
+    if (!q || !cache_k || !cache_v || !out) return fail("%s: null argument", who);
+    if (mode < 0 || mode > 3) return fail("%s: mode %d outside [0, 3]", who, mode);
+    const bool last = mode & 1, pos_dev = mode & 2;
+    if (B < 1 || B > 65535 || L < 1 || H < 1 || H > 65535 || KVH < 1 || HD < 4 || HD % 4 || Smax < 1)
+        return fail("%s: bad shape (B %d, L %d, H %d, KVH %d, head size %d, Smax %d)", who, B, L, H, KVH, HD, Smax);
+    if (start_pos < 0 || (int64_t)start_pos + L > Smax)
+        return fail("%s: keys [0, %lld) exceed Smax %d (start_pos %d + L %d)", who, (long long)start_pos + L, Smax,
+                    start_pos, L);
+    if (wo && D < 1) return fail("%s: D = %d with wo", who, D);
+    const int64_t width = wo ? (int64_t)H * D : (int64_t)H * HD;
+    const int64_t nq = (int64_t)B * L * H * HD, nc = (int64_t)B * KVH * Smax * HD, no = out_rows * width;
+    if (out_rows < (int64_t)B * L + 1)
+        return fail("%s: out must hold B * L + 1 = %lld rows (one of guard space)", who, (long long)B * L + 1);
+    if (nq > INT32_MAX || nc > INT32_MAX || no > INT32_MAX) return fail("%s: arrays of more than 2^31 elements", who);
+    if (set_dev(c)) return 1;
+    Scratch S{c};
+    SCRATCH(dq, nq);
+    SCRATCH(dk, nc);
+    SCRATCH(dv, nc);
+    SCRATCH(dout, no);
+    SCRATCH(dpos, 1);
+    H2D(dq, q, nq);
+    H2D(dk, cache_k, nc);
+    H2D(dv, cache_v, nc);
+    H2D(dout, out, no);
+    AttnArgs a{};
+    a.q = dq; a.cache_k = dk; a.cache_v = dv;
+    a.B = B; a.L = L; a.start_pos = start_pos; a.H = H; a.KVH = KVH; a.HD = HD; a.Smax = Smax;
+    if (wo) {
+        SCRATCH(dwo, (int64_t)D * H * HD);
+        H2D(dwo, wo, (int64_t)D * H * HD);
+        a.wo = dwo; a.parts = dout; a.D = D;
+    } else {
+        a.out = dout;
+    }
+    if (pos_dev) {
+        // the position travels in the device word; the argument holds another (in-range) one, so a
+        // kernel that read the argument would attend over the wrong keys
+        H2D(dpos, &start_pos, 1);
+        a.pos_dev = reinterpret_cast<const int*>(dpos);
+        a.start_pos = start_pos > 0 ? 0 : (L < Smax ? 1 : 0);
+    }
+    AttnRoute rt;
+    const hipError_t e = last ? launch_attention_last(a, c->stream, &rt) : launch_attention(a, c->stream, &rt);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(c->stream);
+        if (e != hipErrorInvalidValue) return fail("%s: the launch failed: %s", who, hipGetErrorString(e));
+        // the dispatcher's refusals, in its own order
+        if (H % KVH) return fail("%s: n_heads %% n_kv_heads != 0 (H %d, KVH %d)", who, H, KVH);
+        if (last && (wo || pos_dev))
+            return fail("%s: the last-rows launch takes neither wo nor a device position (mode %d)", who, mode);
+        if (wo && (L != 1 || Smax > 8192))
+            return fail("%s: the fused O-proj is a decode launch: L == 1 and Smax <= 8192 (L %d, Smax %d)", who, L, Smax);
+        if (HD != 16 && HD != 32 && HD != 48 && HD != 64 && HD != 96 && HD != 128)
+            return fail("%s: head size %d has no attention instantiation (16, 32, 48, 64, 96, 128)", who, HD);
+        if (wo && D % 4) return fail("%s: D %d must be a multiple of 4 with wo", who, D);
+        return fail("%s: the dispatcher refused the launch (no other kernel stands in)", who);
+    }
+    if (rt.kernel == ATTN_NONE) return fail("%s: the dispatcher launched nothing", who);
+    D2H(out, dout, no);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (route) {
+        route[0] = rt.kernel; route[1] = rt.HD; route[2] = rt.QBW; route[3] = rt.G; route[4] = rt.KT;
+        for (int i = 0; i < 3; ++i) route[5 + i] = rt.grid[i];
+    }
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------
 // Teacher-forced scoring (extension of Llama.__call__, llama3.py:285-308; DESIGN.md "Scoring"):
 // the lm_head over every row with the lse_rows epilogue, in row chunks against the bounded

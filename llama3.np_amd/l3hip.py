@@ -124,6 +124,8 @@ _SIGNATURES = {
     "l3_op_linear_fp8_rows_host": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _P, _P, _P, _F, _P, _P]),
     "l3_op_linear_bf16_host": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _P, _P, _F, _P]),
     "l3_op_gemm_host": (ctypes.c_int, [_P, _P]),
+    "l3_op_attention_host": (ctypes.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I32,
+                                            _P, _I64, _P]),
     "l3_set_last_layer_rows": (ctypes.c_int, [_P, _I32]),
     "l3_kernel_timing": (ctypes.c_int, [_P, _I32]),
     "l3_kernel_stats": (ctypes.c_int, [_P, _P, _P]),
@@ -194,6 +196,15 @@ def gemm_sentinel(shape, salt: int = 0) -> np.ndarray:
     i = np.arange(n, dtype=np.uint64) + np.uint64(salt) * np.uint64(1000003)
     bits = np.uint32(0x40800000) + ((i * np.uint64(2654435761)) & np.uint64(0x3FFFFF)).astype(np.uint32)
     return bits.view(np.float32).reshape(shape)
+
+
+ATTN_KERNELS = ["prefill", "decode", "decode_oproj"]  # l3_op_attention_host route[0]
+
+
+def attn_scale_q(q: np.ndarray, hd: int) -> np.ndarray:
+    """q * log2(e) / sqrt(hd) in fp32: the queries as the dense attention kernels take them (the
+    QKV epilogue's q_scale), so that p = exp2(q~ . k - max)."""
+    return np.asarray(q, np.float32) * np.float32(1.4426950408889634 / np.sqrt(float(hd)))
 
 
 def interleave_gate_up(wg: np.ndarray, wu: np.ndarray) -> np.ndarray:
@@ -1200,6 +1211,57 @@ class Context:
             route[name] = int(op.route[1 + i])
         out["route"] = route
         return out
+
+    def op_attention(self, q, cache_k, cache_v, start_pos: int, n_heads: int, *, last: bool = False,
+                     pos_dev: bool = False, wo=None, out=None, scaled: bool = False):
+        """One dense attention launch through the library's dispatcher (l3_op_attention_host).
+
+        ``q`` [B, L, H * HD]: the plain queries, multiplied here in fp32 by log2(e) / sqrt(HD)
+        (``attn_scale_q``), or with ``scaled`` what the kernel takes as it is.  ``cache_k`` /
+        ``cache_v`` [B, KVH, Smax, HD].  ``last``: the last-rows launch of a pruned last block;
+        ``pos_dev``: the position is read from a device word; ``wo`` [D, H * HD]: the decode launch
+        with the O-proj fused.  ``out`` [B * L, H * HD] (with ``wo``: [B, H * D]): the initial
+        contents of the output (default: ``gemm_sentinel(shape, 6)``); a float32 array of the
+        returned shape is used in place, guard row and all.
+
+        Returns (out, route): ``out`` [B * L + 1, width] WITH its guard row, which was filled with
+        ``gemm_sentinel((1, width), 7)``; ``route`` a dict — kernel ("prefill", "decode",
+        "decode_oproj"), hd, qbw, g, kt (0 for the decode kernels) and grid (x, y, z).  A launch
+        the dispatcher refuses raises and leaves ``out`` as it was."""
+        ck = np.ascontiguousarray(cache_k, dtype=np.float32)
+        cv = np.ascontiguousarray(cache_v, dtype=np.float32)
+        if ck.ndim != 4 or cv.shape != ck.shape:
+            raise ValueError(f"cache_k {ck.shape} / cache_v {cv.shape} must be [B, KVH, Smax, HD]")
+        B, KVH, Smax, HD = ck.shape
+        H = int(n_heads)
+        q = np.asarray(q, dtype=np.float32)
+        if q.ndim != 3 or q.shape[0] != B or q.shape[2] != H * HD:
+            raise ValueError(f"q {q.shape} must be [B = {B}, L, H * HD = {H * HD}]")
+        L = q.shape[1]
+        q = np.ascontiguousarray(q if scaled else attn_scale_q(q, HD))
+        D = 0
+        w = None
+        if wo is not None:
+            w = np.ascontiguousarray(wo, dtype=np.float32)
+            if w.ndim != 2 or w.shape[1] != H * HD:
+                raise ValueError(f"wo {w.shape} must be [D, H * HD = {H * HD}]")
+            D = w.shape[0]
+        width = H * D if w is not None else H * HD
+        if isinstance(out, np.ndarray) and out.shape == (B * L + 1, width) and out.dtype == np.float32 \
+                and out.flags.c_contiguous:
+            buf = out  # the caller's own buffer, guard row included, used in place
+        else:
+            buf = np.empty((B * L + 1, width), np.float32)
+            buf[:B * L] = gemm_sentinel((B * L, width), 6) if out is None \
+                else np.asarray(out, np.float32).reshape(B * L, width)
+            buf[B * L:] = gemm_sentinel((1, width), 7)
+        r = np.zeros(8, np.int32)
+        check(lib().l3_op_attention_host(self._h, ptr(q), ptr(ck), ptr(cv), B, L, int(start_pos), H, KVH, HD, Smax,
+                                         int(bool(last)) | (int(bool(pos_dev)) << 1), None if w is None else ptr(w), D,
+                                         ptr(buf), B * L + 1, ptr(r)))
+        route = {"kernel": ATTN_KERNELS[int(r[0])], "hd": int(r[1]), "qbw": int(r[2]), "g": int(r[3]), "kt": int(r[4]),
+                 "grid": (int(r[5]), int(r[6]), int(r[7]))}
+        return buf, route
 
     def op_ffn_block(self, x: np.ndarray, wg: np.ndarray, wu: np.ndarray, wd: np.ndarray, norm: bool,
                      fused: bool) -> np.ndarray:
