@@ -100,14 +100,18 @@ def kept_set(z, T, top_k, top_p, dtype=np.float64):
     return idx, w[idx]
 
 
+def draw(idx, w, u, dtype=np.float64):
+    """Step 6 on a kept set (kept_set's pair): many uniforms may share one set."""
+    c = np.cumsum(w)  # sequential, in dtype
+    hit = np.flatnonzero(c > dtype(u) * c[-1])
+    return int(idx[hit[0]]) if hit.size else int(idx[-1])
+
+
 def sample(z, T, top_k, top_p, u, dtype=np.float64):
     s = kept_set(z, T, top_k, top_p, dtype)
     if s is None:
         return argmax_rule(z)
-    idx, w = s
-    c = np.cumsum(w)  # sequential, in dtype
-    hit = np.flatnonzero(c > dtype(u) * c[-1])
-    return int(idx[hit[0]]) if hit.size else int(idx[-1])
+    return draw(s[0], s[1], u, dtype)
 
 
 def distance(z, T, top_k, top_p, u, g, d=D):
