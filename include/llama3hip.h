@@ -671,6 +671,86 @@ typedef struct l3_gemm_op {
     int32_t route[8];
 } l3_gemm_op;
 int l3_op_gemm_host(l3_ctx* ctx, l3_gemm_op* op);
+/* The arguments a captured greedy decode step adds to its GEMV / lm_head launches, on plain host
+ * arrays (tests/test_gpu_decode_gemv.py; DESIGN.md "Captured-decode GEMV arguments at kernel
+ * level"): llama3.py:312-320 (argmax of the last logits, the next position) and :253 / :259 (the
+ * residual adds) as the kernels fuse them.  One (value, index) argmax candidate: */
+typedef struct l3_argmax_part {
+    float v;
+    int32_t i;
+} l3_argmax_part;
+/* The device-resident decode state of such a step, described by the caller and returned after the
+ * launch: the entry builds it on the device with hist / hist_val (NULL: the state has none) copied
+ * from the caller's hist_len entries, and copies pos, arrive and both histories back.  hist_len
+ * counts guard entries too: at least hist_cap * rows + 1.  struct_size = sizeof(l3_dec_state_io). */
+typedef struct l3_dec_state_io {
+    int32_t struct_size;
+    int32_t pos;        /* in / out */
+    int32_t hist_base;
+    int32_t hist_cap;
+    uint32_t arrive;    /* in / out */
+    int32_t pad;
+    int32_t* hist;      /* in / out, may be NULL */
+    float* hist_val;    /* in / out, may be NULL */
+    int64_t hist_len;
+} l3_dec_state_io;
+/* One launch_gemm call like l3_op_gemm_host's (g: that entry's operands, shapes, guard rules and
+ * route controls; g.route is the report), plus:
+ *   storage    0 fp32; 1 bf16 (as g.bf16); 2 fp8: wq_codes [N, K] e4m3fn codes and wq_scale [N]
+ *              power-of-two scales as l3_op_linear_fp8_host takes them, g.w the same model in fp32
+ *              for a launch the fp8 form does not take, g.norm_w the RMSNorm weight (required with norm)
+ *   parts      [M * nparts + 1, D] (D = N for epi 1, K for epi 2): the per-head O-proj rows
+ *              [M][nparts][D] the one-row GEMV adds in head order — epi 2: x + p0 + p1 + ... is the
+ *              input row, also stored to x_out [x_out_rows >= M + 1, K] (in / out, may be NULL);
+ *              epi 1: c = ((res + p0) + p1 + ...) + x @ w^T — then one row the launch must not read
+ *   amax_part  in / out, amax_part_n entries: epi 0, M == 1 on the GEMV also leaves each block's
+ *              argmax over its columns (np.argmax's rule: first index of the maximum, the first NaN
+ *              wins); *amax_blocks = the blocks, amax_part_n >= blocks + 1.  pos_adv != 0: block 0
+ *              also adds 1 to state->pos
+ *   amax_rows  in / out [amax_rows_rows >= M + 1, amax_nct = ceil(N / 64)]: epi 0 on the tiled kernels
+ *              leaves each row's argmax per 64-column tile instead of the logits (c is not written)
+ *   amax_in    [amax_in_n]: epi 3, M == 1: the A row is x[id] (x [g.x_rows, K]), id the argmax over
+ *              these candidates (every index in [0, g.x_rows)); the id goes to amax_ids[0] (in / out,
+ *              two entries) and, with its value, to the history slot state->pos - 1 - hist_base
+ *   kv_bak     in / out [33, 2, M / L, KVH, HD] (32 undo slots and a guard slot): epi 3 on the GEMV
+ *              keeps the previous contents of cache slot pos in kv_bak[pos % 32] before it appends
+ *   pos_dev    != 0: epi 3 reads its position from state->pos; g.start_pos then holds another one
+ * Every in / out array is uploaded before the launch and downloaded after it.  What the dispatcher
+ * refuses is an error named here (nparts outside [1, 8], parts with epi 0 / 3 or off the one-row
+ * GEMV's range, amax_part off it, amax_in with M != 1, col_base, a_rows, amax_in_n < 1 or no
+ * amax_ids): nothing is written and no other kernel stands in.
+ * struct_size = sizeof(l3_decode_gemm_op), g.struct_size = sizeof(l3_gemm_op). */
+typedef struct l3_decode_gemm_op {
+    int32_t struct_size;
+    int32_t storage;
+    l3_gemm_op g;
+    const uint8_t* wq_codes;
+    const float* wq_scale;
+    const float* parts;
+    int64_t parts_rows;
+    float* x_out;
+    int64_t x_out_rows;
+    l3_argmax_part* amax_part;
+    l3_argmax_part* amax_rows;
+    int64_t amax_rows_rows;
+    const l3_argmax_part* amax_in;
+    int32_t* amax_ids;
+    l3_dec_state_io* state;
+    float* kv_bak;
+    int32_t nparts, amax_part_n, amax_blocks, amax_nct, amax_in_n, pos_adv, pos_dev, pad;
+} l3_decode_gemm_op;
+int l3_op_decode_gemm_host(l3_ctx* ctx, l3_decode_gemm_op* op);
+/* argmax_parts_kernel on plain arrays: ids[r] (in / out, rows + 1 entries) = the argmax over
+ * parts[r][0 .. n) by np.argmax's rule, for rows >= 1 rows of n >= 1 candidates.  With state (may be
+ * NULL) the captured step's bookkeeping: id and value to history slot
+ * (state->pos - hist_off - hist_base) * rows + r when that slot is in [0, hist_cap), and with
+ * hist_off == 0 the position moves on by one (the last row to arrive; arrive returns to 0). */
+int l3_op_argmax_parts_host(l3_ctx* ctx, const l3_argmax_part* parts, int32_t rows, int32_t n, int32_t hist_off,
+                            l3_dec_state_io* state, int32_t* ids);
+/* The unguarded undo of one cache's append (kv_restore_kernel): cache [cache_B >= B + 1, KVH, Smax,
+ * HD] (in / out) gets bak [B, KVH, HD] back at slot pos in [0, Smax) of sequences 0 .. B - 1. */
+int l3_op_kv_restore_host(l3_ctx* ctx, float* cache, int64_t cache_B, const float* bak, int32_t B, int32_t KVH,
+                          int32_t Smax, int32_t HD, int32_t pos);
 /* One dense attention launch on plain host arrays (tests/test_gpu_attn_dense.py): llama3.py:186-210
  * for B sequences of L new tokens at positions start_pos + t, through exactly one call of the
  * library's attention dispatcher, and a report of the kernel it chose.  Works on an op-only

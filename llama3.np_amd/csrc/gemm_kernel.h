@@ -277,6 +277,9 @@ __device__ __forceinline__ void direct_epilogue(const GemmArgs& p, const f32x4 (
             // greedy argmax partials instead of the logits (llama3.py:320 over this wave's 16 * TN
             // columns of each row): the lane's own columns in rising order ("strictly greater, or
             // the first NaN" keeps the first index on ties), then the four lanes of the row
+            // a wave wholly past the last column (N % 128 in (0, 64]) owns no record: its slot would be
+            // amax_nct, the next row's record 0 — or, from the last row, one past the buffer
+            if (ncol0 >= p.N) return;
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
                 const int row = mrow0 + i * 16 + frow;

@@ -124,6 +124,9 @@ _SIGNATURES = {
     "l3_op_linear_fp8_rows_host": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _P, _P, _P, _F, _P, _P]),
     "l3_op_linear_bf16_host": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _P, _P, _F, _P]),
     "l3_op_gemm_host": (ctypes.c_int, [_P, _P]),
+    "l3_op_decode_gemm_host": (ctypes.c_int, [_P, _P]),
+    "l3_op_argmax_parts_host": (ctypes.c_int, [_P, _P, _I32, _I32, _I32, _P, _P]),
+    "l3_op_kv_restore_host": (ctypes.c_int, [_P, _P, _I64, _P, _I32, _I32, _I32, _I32, _I32]),
     "l3_op_attention_host": (ctypes.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I32,
                                             _P, _I64, _P]),
     "l3_set_last_layer_rows": (ctypes.c_int, [_P, _I32]),
@@ -171,6 +174,80 @@ class GemmOp(ctypes.Structure):
         ("force_skinny", _I32), ("force_tiled", _I32), ("x6", _I32), ("bf16", _I32), ("wb_rows", _I32),
         ("route", _I32 * 8),
     ]
+
+
+class DecStateIO(ctypes.Structure):
+    """l3_dec_state_io (include/llama3hip.h)."""
+    _fields_ = [
+        ("struct_size", _I32), ("pos", _I32), ("hist_base", _I32), ("hist_cap", _I32), ("arrive", ctypes.c_uint32),
+        ("pad", _I32), ("hist", _P), ("hist_val", _P), ("hist_len", _I64),
+    ]
+
+
+class DecodeGemmOp(ctypes.Structure):
+    """l3_decode_gemm_op (include/llama3hip.h)."""
+    _fields_ = [
+        ("struct_size", _I32), ("storage", _I32), ("g", GemmOp),
+        ("wq_codes", _P), ("wq_scale", _P), ("parts", _P), ("parts_rows", _I64), ("x_out", _P), ("x_out_rows", _I64),
+        ("amax_part", _P), ("amax_rows", _P), ("amax_rows_rows", _I64), ("amax_in", _P), ("amax_ids", _P),
+        ("state", ctypes.POINTER(DecStateIO)), ("kv_bak", _P),
+        ("nparts", _I32), ("amax_part_n", _I32), ("amax_blocks", _I32), ("amax_nct", _I32), ("amax_in_n", _I32),
+        ("pos_adv", _I32), ("pos_dev", _I32), ("pad", _I32),
+    ]
+
+
+# l3_argmax_part: one (value, index) argmax candidate
+ARGMAX_PART = np.dtype([("v", "<f4"), ("i", "<i4")])
+ARGMAX_EMPTY = (-np.inf, 0x7FFFFFFF)  # what a lane without a valid column holds
+KV_BAK_SLOTS = 32
+STORAGES = {"fp32": 0, "bf16": 1, "fp8": 2}
+
+
+def argmax_parts_sentinel(shape, salt: int = 0) -> np.ndarray:
+    """ARGMAX_PART records no kernel writes: finite values and indices, every record different."""
+    a = np.empty(shape, ARGMAX_PART)
+    a["v"] = gemm_sentinel(shape, 20 + salt)
+    a["i"] = (-1000 - np.arange(a.size, dtype=np.int64) - 7919 * salt).astype(np.int32).reshape(shape)
+    return a
+
+
+def int_sentinel(shape, salt: int = 0) -> np.ndarray:
+    """Negative int32 ids no kernel writes, every entry different."""
+    n = int(np.prod(shape))
+    return (-5000 - np.arange(n, dtype=np.int64) - 104729 * salt).astype(np.int32).reshape(shape)
+
+
+class DecState:
+    """A decode state for op_decode_gemm / op_argmax_parts: the description going in, and after the call
+    ``pos``, ``arrive`` and the histories ``hist`` (int32) / ``hist_val`` (float32) [hist_cap * rows + 1]
+    WITH their guard entry; both start as sentinels (``int_sentinel(n, 3)``, ``gemm_sentinel(n, 11)``)."""
+
+    def __init__(self, pos: int, hist_base: int = 0, hist_cap: int = 0, hist: bool = True, hist_val: bool = True,
+                 rows: int = 1, arrive: int = 0):
+        self.pos, self.hist_base, self.hist_cap, self.rows, self.arrive = pos, hist_base, hist_cap, rows, arrive
+        n = hist_cap * rows + 1
+        self.hist = int_sentinel(n, 3) if hist else None
+        self.hist_val = gemm_sentinel(n, 11).copy() if hist_val else None
+
+    def _io(self) -> DecStateIO:
+        io = DecStateIO()
+        io.struct_size = ctypes.sizeof(DecStateIO)
+        io.pos, io.hist_base, io.hist_cap, io.arrive = self.pos, self.hist_base, self.hist_cap, self.arrive
+        io.hist = ptr(self.hist) if self.hist is not None else None
+        io.hist_val = ptr(self.hist_val) if self.hist_val is not None else None
+        io.hist_len = self.hist_cap * self.rows + 1
+        return io
+
+    def _take(self, io: DecStateIO) -> None:
+        self.pos, self.arrive = int(io.pos), int(io.arrive)
+
+
+def _gemm_route(op) -> dict:
+    fam = GEMM_FAMILIES[op.route[0]]
+    route = {"family": fam, "launches": int(op.route[6])}
+    for i, name in enumerate(_ROUTE_FIELDS[fam]):
+        route[name] = int(op.route[1 + i])
+    return route
 
 
 EPI_STORE, EPI_RESID, EPI_SWIGLU, EPI_QKV = range(4)
@@ -1129,6 +1206,23 @@ class Context:
         ``cache_v`` [B + 1, KVH, Smax, HD]; the guard was filled with ``gemm_sentinel(shape, 7)``
         (c, q_out) and ``gemm_sentinel(shape, 8 / 9)`` (cache_k / cache_v).  A launch the
         dispatcher refuses raises."""
+        op = GemmOp()
+        out, keep = self._fill_gemm_op(op, epi, x, w, gate_up=gate_up, c=c, norm=norm, eps=eps, norm_w=norm_w,
+                                       a_rows=a_rows, res_src=res_src, res_rows=res_rows, qkv=qkv, ws_floats=ws_floats,
+                                       force_skinny=force_skinny, force_tiled=force_tiled, x6=x6, bf16=bf16,
+                                       wb_rows=wb_rows, wb_min_bytes=wb_min_bytes)
+        check(lib().l3_op_gemm_host(self._h, ctypes.byref(op)))
+        del keep
+        out["route"] = _gemm_route(op)
+        return out
+
+    @staticmethod
+    def _fill_gemm_op(op, epi, x, w, *, gate_up=None, c=None, norm=False, eps=0.0, norm_w=None, a_rows=None,
+                      res_src=None, res_rows=None, qkv=None, ws_floats=0, force_skinny=False, force_tiled=0, x6=False,
+                      bf16=False, wb_rows=0, wb_min_bytes=0, table=False):
+        """The operands of op_gemm into ``op`` (a GemmOp): (out, keep) — the in / out buffers with their
+        guard space, and the arrays the struct points into.  ``table``: x is a table [rows, K] and M = 1
+        (op_decode_gemm's amax_in selects the row)."""
         x = np.ascontiguousarray(x, dtype=np.float32)
         if epi == EPI_SWIGLU and gate_up is not None:
             w = interleave_gate_up(np.asarray(gate_up[0], np.float32), np.asarray(gate_up[1], np.float32))
@@ -1136,11 +1230,10 @@ class Context:
         if x.ndim != 2 or w.ndim != 2 or w.shape[1] != x.shape[1]:
             raise ValueError(f"x {x.shape} and w {w.shape} must be [rows, K] and [N, K]")
         keep = [x, w]
-        op = GemmOp()
         op.struct_size = ctypes.sizeof(GemmOp)
         op.epi = epi
         N, K = w.shape
-        M = x.shape[0]
+        M = 1 if table else x.shape[0]
         if a_rows is not None:
             ar = np.ascontiguousarray(a_rows, dtype=np.int32)
             keep.append(ar)
@@ -1203,14 +1296,127 @@ class Context:
         op.ws_floats, op.wb_min_bytes = int(ws_floats), int(wb_min_bytes)
         op.force_skinny, op.force_tiled, op.x6 = int(bool(force_skinny)), int(force_tiled), int(bool(x6))
         op.bf16, op.wb_rows = int(bool(bf16)), int(wb_rows)
-        check(lib().l3_op_gemm_host(self._h, ctypes.byref(op)))
-        del keep
-        fam = GEMM_FAMILIES[op.route[0]]
-        route = {"family": fam, "launches": int(op.route[6])}
-        for i, name in enumerate(_ROUTE_FIELDS[fam]):
-            route[name] = int(op.route[1 + i])
-        out["route"] = route
+        return out, keep
+
+    def op_decode_gemm(self, epi: int, x: np.ndarray, w=None, *, storage: str = "fp32", parts=None, nparts=None,
+                       x_out: bool = False, amax_part: bool = False, amax_rows: bool = False, amax_nct=None,
+                       amax_in=None, amax_in_n=None, amax_ids: bool = True, state: Optional[DecState] = None,
+                       pos_adv: bool = False, kv_bak: bool = False, pos_dev: bool = False, **kw) -> dict:
+        """One GEMM launch as ``op_gemm`` (its arguments in ``kw``), with the arguments of a captured
+        greedy decode step (l3_op_decode_gemm_host).
+
+        ``storage``: "fp32", "bf16" (the entry rounds ``w``) or "fp8" (``utils.quant_fp8_rows(w)`` goes
+        in, and ``w`` itself becomes ``scale * e4m3fn(codes)``); with a norm both take ``norm_w``.
+        ``parts`` [M, P, D]: the O-proj partial rows (``nparts``: the count passed, default P); a
+        guard row ``gemm_sentinel((1, D), 12)`` follows them.  ``x_out`` / ``amax_part`` /
+        ``amax_rows`` / ``kv_bak``: ask for that output.  ``amax_in``: ARGMAX_PART [n] candidates,
+        ``x`` then is the table the winner indexes and M = 1 (``amax_in_n``: the count passed;
+        ``amax_ids=False``: no id buffer).  ``state``: a DecState, updated in place; ``pos_adv`` /
+        ``pos_dev`` use it.
+
+        Returns op_gemm's dict plus, WITH their guard space and starting as sentinels: ``x_out``
+        [M + 1, K] (``gemm_sentinel(.., 13)``), ``amax_part`` [N / 4 + 4] and ``amax_blocks``,
+        ``amax_rows`` [M + 1, nct] (both ``argmax_parts_sentinel(.., 1 / 2)``), ``amax_ids`` [2]
+        (``int_sentinel(2, 5)``), ``kv_bak`` [33, 2, B, KVH, HD] (``gemm_sentinel(.., 14)``), and with
+        fp8 storage ``w_model``, the weights the codes stand for."""
+        import utils
+
+        if storage not in STORAGES:
+            raise ValueError(f"storage {storage!r} is none of {sorted(STORAGES)}")
+        d = DecodeGemmOp()
+        d.struct_size = ctypes.sizeof(DecodeGemmOp)
+        d.storage = STORAGES[storage]
+        extra = {}
+        hold = []
+        if epi == EPI_SWIGLU and kw.get("gate_up") is not None:
+            gu = kw.pop("gate_up")
+            w = interleave_gate_up(np.asarray(gu[0], np.float32), np.asarray(gu[1], np.float32))
+        if storage == "fp8":
+            codes, scale = utils.quant_fp8_rows(w)
+            w = (utils.fp8_e4m3_table()[codes] * scale[:, None]).astype(np.float32)
+            hold += [codes, scale]
+            d.wq_codes, d.wq_scale = ptr(codes), ptr(scale)
+            extra["w_model"] = w
+        out, keep = self._fill_gemm_op(d.g, epi, x, w, table=amax_in is not None, **kw)
+        M, N, K = d.g.M, d.g.N, d.g.K
+        if parts is not None:
+            p = np.asarray(parts, np.float32)
+            D = N if epi == EPI_RESID else K
+            if p.ndim != 3 or p.shape[0] != M or p.shape[2] != D:
+                raise ValueError(f"parts {p.shape} must be [M = {M}, P, D = {D}]")
+            pbuf = np.concatenate([p.reshape(-1, D), gemm_sentinel((1, D), 12)])
+            hold.append(pbuf)
+            d.parts, d.parts_rows = ptr(pbuf), pbuf.shape[0]
+            d.nparts = p.shape[1] if nparts is None else int(nparts)
+        if x_out:
+            xo = gemm_sentinel((M + 1, K), 13).copy()
+            extra["x_out"] = xo
+            d.x_out, d.x_out_rows = ptr(xo), M + 1
+        if amax_part:
+            ap = argmax_parts_sentinel(N // 4 + 4, 1)
+            extra["amax_part"] = ap
+            d.amax_part, d.amax_part_n = ptr(ap), ap.shape[0]
+        if amax_rows:
+            nct = (N + 63) // 64 if amax_nct is None else int(amax_nct)
+            ar = argmax_parts_sentinel((M + 1, max(nct, 1)), 2)
+            extra["amax_rows"] = ar
+            d.amax_rows, d.amax_rows_rows, d.amax_nct = ptr(ar), M + 1, nct
+        if amax_in is not None:
+            ai = np.ascontiguousarray(amax_in, dtype=ARGMAX_PART)
+            hold.append(ai)
+            d.amax_in = ptr(ai)
+            d.amax_in_n = ai.shape[0] if amax_in_n is None else int(amax_in_n)
+            if amax_ids:
+                ids = int_sentinel(2, 5)
+                extra["amax_ids"] = ids
+                d.amax_ids = ptr(ids)
+        io = None
+        if state is not None:
+            io = state._io()
+            d.state = ctypes.pointer(io)
+        d.pos_adv, d.pos_dev = int(bool(pos_adv)), int(bool(pos_dev))
+        if kv_bak:
+            B = M // d.g.L
+            kb = gemm_sentinel((KV_BAK_SLOTS + 1, 2, B, d.g.KVH, d.g.HD), 14).copy()
+            extra["kv_bak"] = kb
+            d.kv_bak = ptr(kb)
+        check(lib().l3_op_decode_gemm_host(self._h, ctypes.byref(d)))
+        del keep, hold
+        if state is not None:
+            state._take(io)
+        out.update(extra)
+        out["route"] = _gemm_route(d.g)
+        if amax_part:
+            out["amax_blocks"] = int(d.amax_blocks)
         return out
+
+    def op_argmax_parts(self, parts: np.ndarray, hist_off: int = 0, state: Optional[DecState] = None) -> np.ndarray:
+        """The decode loop's argmax over per-block candidates (l3_op_argmax_parts_host): ``parts``
+        ARGMAX_PART [rows, n] -> ids int32 [rows + 1] WITH a guard entry (``int_sentinel(rows + 1, 6)``
+        before the launch).  ``state`` (a DecState of that many rows) is updated in place."""
+        p = np.ascontiguousarray(parts, dtype=ARGMAX_PART)
+        if p.ndim != 2:
+            raise ValueError(f"parts {p.shape} must be [rows, n]")
+        if state is not None and state.rows != p.shape[0]:
+            raise ValueError(f"a state of {state.rows} rows for {p.shape[0]} rows of candidates")
+        ids = int_sentinel(p.shape[0] + 1, 6)
+        io = state._io() if state is not None else None
+        check(lib().l3_op_argmax_parts_host(self._h, ptr(p), p.shape[0], p.shape[1], int(hist_off),
+                                            ctypes.byref(io) if io is not None else None, ptr(ids)))
+        if state is not None:
+            state._take(io)
+        return ids
+
+    def op_kv_restore(self, cache: np.ndarray, bak: np.ndarray, pos: int) -> np.ndarray:
+        """The unguarded undo of one cache's append (l3_op_kv_restore_host): ``cache`` [B + 1, KVH,
+        Smax, HD] WITH its guard sequence, ``bak`` [B, KVH, HD]; returns the cache after the launch."""
+        ck = np.array(cache, dtype=np.float32, order="C")
+        b = np.ascontiguousarray(bak, dtype=np.float32)
+        if ck.ndim != 4 or b.shape != (ck.shape[0] - 1, ck.shape[1], ck.shape[3]):
+            raise ValueError(f"cache {ck.shape} must be [B + 1, KVH, Smax, HD] and bak {b.shape} [B, KVH, HD]")
+        check(lib().l3_op_kv_restore_host(self._h, ptr(ck), ck.shape[0], ptr(b), b.shape[0], ck.shape[1], ck.shape[2],
+                                          ck.shape[3], int(pos)))
+        return ck
 
     def op_attention(self, q, cache_k, cache_v, start_pos: int, n_heads: int, *, last: bool = False,
                      pos_dev: bool = False, wo=None, out=None, scaled: bool = False):

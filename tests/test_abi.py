@@ -56,6 +56,17 @@ def test_dims_struct_layout():
     assert ctypes.sizeof(l3hip.Dims) == 9 * 4
 
 
+def test_decode_gemm_struct_layouts():
+    """l3_dec_state_io and l3_decode_gemm_op as the binding lays them out: no hidden padding, the
+    embedded l3_gemm_op at offset 8 (the library checks both struct_size fields against its own)."""
+    assert ctypes.sizeof(l3hip.DecStateIO) == 6 * 4 + 2 * 8 + 8
+    assert l3hip.DecodeGemmOp.g.offset == 8 and ctypes.sizeof(l3hip.GemmOp) % 8 == 0
+    assert ctypes.sizeof(l3hip.DecodeGemmOp) == 8 + ctypes.sizeof(l3hip.GemmOp) + 13 * 8 + 8 * 4
+    assert l3hip.DecodeGemmOp.nparts.offset == ctypes.sizeof(l3hip.DecodeGemmOp) - 8 * 4
+    for name in ("l3_op_decode_gemm_host", "l3_op_argmax_parts_host", "l3_op_kv_restore_host"):
+        assert name in l3hip.header_symbols() and name in l3hip._SIGNATURES
+
+
 def test_library_path_is_in_tree():
     assert os.path.dirname(l3hip.LIB_PATH).endswith(os.path.join("llama3.np_amd", "csrc"))
 
