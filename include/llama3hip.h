@@ -751,6 +751,43 @@ int l3_op_argmax_parts_host(l3_ctx* ctx, const l3_argmax_part* parts, int32_t ro
  * HD] (in / out) gets bak [B, KVH, HD] back at slot pos in [0, Smax) of sequences 0 .. B - 1. */
 int l3_op_kv_restore_host(l3_ctx* ctx, float* cache, int64_t cache_B, const float* bak, int32_t B, int32_t KVH,
                           int32_t Smax, int32_t HD, int32_t pos);
+/* One persistent batch-1 greedy decode step (decode_persist.hip), launched directly on the
+ * context's stream — not captured — and every stage's output handed back
+ * (tests/test_gpu_decode_persist.py; DESIGN.md "Persistent step coverage").  Works on a finalised
+ * model context with max_batch_size 1 and an fp32 KV cache, whose cache rows before state->pos the
+ * caller has filled on the ordinary path.  Any run-ahead is settled first; afterwards the device
+ * decode state is invalid, so the next ordinary call neither replays a graph nor trusts it.
+ *   token      the step's token id, in [0, vocab_size)
+ *   steps      1: one launch (from_parts 0, write_id 1); 2: two chained launches (0 / 0, then 1 / 1),
+ *              the second fed the first's argmax from its lm partials
+ *   use_kv_bak != 0: the launches keep each overwritten cache slot in kv_bak
+ *   state      pos in [1, max_seq_len - steps] in, pos + steps out; history as l3_dec_state_io
+ *   gran       out [gran_n = n_layers * slab] granules of the LAST launch, tag << 32 | value bits, per
+ *              layer in the order [qkv | o | h1 | hid | h2] (slab = (H + 2 KVH) HD + H HD + D + FD + D)
+ *   lm_parts   out [512]: the lm partial granules, (value, index) per lm workgroup
+ *   kv_bak     in / out [kv_bak_n = n_layers * 8 * 32 * 2 * KVH * HD]: per layer the room of the batched
+ *              layout (8 sequences), of which one sequence uses the first [32][2: k, v][KVH][HD];
+ *              uploaded whole and downloaded whole
+ *   epoch      out: the three epoch words after the last launch; tag: that launch's tag; err: the
+ *              host-mapped error word; id_out: ids[0]
+ *   route      out: the instance chosen (NCD, NCF, KPF, LMPF), the grid, GL, 0, 0
+ * A shape the persistent step does not take anywhere else is an error that names the reason, and
+ * nothing is launched.  The fault knobs stay off.  struct_size = sizeof(l3_decode_persist_op). */
+typedef struct l3_decode_persist_op {
+    int32_t struct_size;
+    int32_t token, steps, use_kv_bak;
+    l3_dec_state_io* state;
+    uint64_t* gran;
+    int64_t gran_n;
+    uint64_t* lm_parts;
+    float* kv_bak;
+    int64_t kv_bak_n;
+    uint32_t epoch[3];
+    uint32_t tag, err;
+    int32_t id_out;
+    int32_t route[8];
+} l3_decode_persist_op;
+int l3_op_decode_persist_host(l3_ctx* ctx, l3_decode_persist_op* op);
 /* One dense attention launch on plain host arrays (tests/test_gpu_attn_dense.py): llama3.py:186-210
  * for B sequences of L new tokens at positions start_pos + t, through exactly one call of the
  * library's attention dispatcher, and a report of the kernel it chose.  Works on an op-only

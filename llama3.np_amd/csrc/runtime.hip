@@ -4323,6 +4323,143 @@ extern "C" int l3_op_kv_restore_host(l3_ctx* c, float* cache, int64_t cache_B, c
     return 0;
 }
 
+// The persistent step's instance for a shape, (NCD, NCF, KPF, LMPF): a restatement of
+// decode_persist.hip's L3_PERSIST_INSTANCES / persist_instance (that file keeps its table to
+// itself), for l3_op_decode_persist_host's route report and refusal messages only — the launch
+// picks its kernel there.  Keep the two in step; tests/test_decode_persist_cpu.py restates the
+// rule a third time and tests/test_gpu_decode_persist.py asserts this report against it.
+static bool persist_route(const DecodePersistArgs& a, int32_t* out) {
+    static const int tab[][4] = {{1, 3, 16, 8}, {5, 12, 12, 11}, {5, 12, 16, 8}, {5, 16, 16, 4},
+                                 {8, 16, 16, 2}, {1, 12, 16, 8}, {5, 3, 16, 8},  {8, 12, 16, 2}};
+    const int nd = (a.D + 63) / 64, nf = (a.FD + 63) / 64;
+    const int ncd = nd <= 1 ? 1 : nd <= 5 ? 5 : nd <= 8 ? 8 : 0, ncf = nf <= 3 ? 3 : nf <= 12 ? 12 : nf <= 16 ? 16 : 0;
+    for (const auto& t : tab)
+        if (t[0] == ncd && t[1] == ncf && a.HD / 4 <= t[2]) {
+            for (int i = 0; i < 4; ++i) out[i] = t[i];
+            return true;
+        }
+    return false;
+}
+
+// One persistent decode step (two chained ones), launched directly, every stage's granules handed
+// back (include/llama3hip.h l3_decode_persist_op).  The launch, its grid and its refusals are
+// decode_persist.hip's own (launch_decode_persist, decode_persist_grid); only the refusal's message
+// is chosen here.
+extern "C" int l3_op_decode_persist_host(l3_ctx* c, l3_decode_persist_op* op) {
+    CHECK_CTX(c);
+    const char* who = "l3_op_decode_persist";
+    if (!op) return fail("%s: null argument", who);
+    if (op->struct_size != (int32_t)sizeof(l3_decode_persist_op))
+        return fail("%s: struct_size %d, this library's l3_decode_persist_op has %d bytes", who, op->struct_size,
+                    (int)sizeof(l3_decode_persist_op));
+    for (int i = 0; i < 8; ++i) op->route[i] = 0;
+    if (kv_f32_only(c, who)) return 1;
+    if (!c->finalized) return fail("%s: the context is not finalised", who);
+    if (need_model(c)) return 1;
+    if (c->d.max_batch_size != 1) return fail("%s: max_batch_size %d, the persistent step takes 1", who, c->d.max_batch_size);
+    if (c->layers.empty()) return fail("%s: a context without layers", who);
+    if (!op->state || !op->gran || !op->lm_parts) return fail("%s: null argument", who);
+    if (state_io_check(who, op->state, 1)) return 1;
+    if (op->steps != 1 && op->steps != 2) return fail("%s: steps %d is neither 1 nor 2", who, op->steps);
+    const int pos = op->state->pos, Smax = c->d.max_seq_len;
+    if (pos < 1 || pos + op->steps > Smax)
+        return fail("%s: pos %d with %d step(s) outside [1, max_seq_len %d)", who, pos, op->steps, Smax);
+    if (op->token < 0 || op->token >= c->d.vocab_size) return fail("%s: token %d outside [0, %d)", who, op->token, c->d.vocab_size);
+    const DecodePersistArgs shape = persist_shape(c);
+    const int nl = shape.n_layers;
+    const int64_t slab = decode_persist_slab(shape.H, shape.KVH, shape.HD, shape.D, shape.FD);
+    const int64_t bak_layer = (int64_t)KV_BAK_SLOTS * 2 * 8 * shape.KVH * shape.HD;
+    if (op->gran_n != slab * nl) return fail("%s: gran_n %lld, the layers hold %lld granules", who, (long long)op->gran_n, (long long)(slab * nl));
+    if (op->use_kv_bak && (!op->kv_bak || op->kv_bak_n != bak_layer * nl))
+        return fail("%s: kv_bak must hold n_layers * 32 * 2 * 8 * KVH * HD = %lld floats", who, (long long)(bak_layer * nl));
+    if (c->persist_off) return fail("%s: this context gave up on the persistent step (graph-only)", who);
+    if (set_dev(c) || spec_resolve(c) || persist_settle(c)) return 1;
+    if (c->persist_off) return fail("%s: this context gave up on the persistent step (graph-only)", who);
+    // the shape's refusals by name, in decode_persist_ok's order; the refusal itself is the grid's
+    const int grid = decode_persist_grid(shape);
+    int32_t inst[4] = {0, 0, 0, 0};
+    const bool have_inst = persist_route(shape, inst);
+    if (grid < 1) {
+        const int qkvn = c->qkvn;
+        if (shape.HD > 64) return fail("%s: head_dim %d exceeds the persistent step's 64", who, shape.HD);
+        if (shape.H > shape.GL) return fail("%s: %d heads exceed the %d layer workgroups", who, shape.H, shape.GL);
+        if ((shape.D + 63) / 64 > 8) return fail("%s: dim %d has no persistent instance (dim <= 512)", who, shape.D);
+        if ((shape.FD + 63) / 64 > 16) return fail("%s: hidden_dim %d has no persistent instance (hidden_dim <= 1024)", who, shape.FD);
+        if (!have_inst)
+            return fail("%s: no persistent instance for dim %d with hidden_dim %d (chunks %d x %d)", who, shape.D, shape.FD,
+                        (shape.D + 63) / 64, (shape.FD + 63) / 64);
+        if ((qkvn / 2 + shape.GL - 1) / shape.GL > 16 || (shape.FD + shape.GL - 1) / shape.GL > 16 ||
+            (shape.D + shape.GL - 1) / shape.GL > 16)
+            return fail("%s: a stage has more than 16 units per layer workgroup", who);
+        if (Smax > 8192) return fail("%s: max_seq_len %d exceeds the persistent step's 8192", who, Smax);
+        return fail("%s: the persistent step does not run on this device at this shape (CUs, LDS or occupancy)", who);
+    }
+    if (!have_inst) return fail("%s: the launch takes a shape this entry's instance table does not know", who);
+    if (persist_setup(c)) return 1;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (persist_failed(c)) return fail("%s: an earlier persistent step's failure is not recovered", who);
+
+    Scratch S{c};
+    StateDev sd;
+    if (state_io_upload(c, S, op->state, &sd)) return 1;
+    SCRATCH(dids, 2);
+    const int32_t ids0[2] = {op->token, -7};
+    HIP_TRY(hipMemcpy(dids, ids0, sizeof ids0, hipMemcpyHostToDevice));
+    float* dbak = nullptr;
+    if (op->use_kv_bak) {
+        SCRATCH(sbak, op->kv_bak_n);
+        H2D(sbak, op->kv_bak, op->kv_bak_n);
+        dbak = sbak;
+    }
+    unsigned tag = 0;
+    {
+        // another context's queued decode graphs first: the step needs every CU (launch_decode_graph)
+        DevOrder& d = g_order[c->device & 63];
+        std::lock_guard<std::mutex> lk(d.m);
+        if (d.ev && d.owner != c) HIP_TRY(hipStreamWaitEvent(c->stream, d.ev, 0));
+        for (int i = 0; i < op->steps; ++i) {
+            DecodePersistArgs a = c->persist;
+            a.ids = reinterpret_cast<int32_t*>(dids);
+            a.st = sd.st;
+            a.kv_bak = dbak;
+            a.from_parts = i > 0;
+            a.write_id = i == op->steps - 1;
+            a.fault_pos = -1;
+            a.stamps = nullptr;
+            if (const hipError_t e = launch_decode_persist(a, grid, c->stream); e != hipSuccess) {
+                (void)hipStreamSynchronize(c->stream);
+                c->dec_pos_mirror = -1;
+                return fail("%s: launch %d refused: %s", who, i, hipGetErrorString(e));
+            }
+        }
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    c->dec_pos_mirror = -1;
+    unsigned ep[3] = {0, 0, 0};
+    HIP_TRY(hipMemcpy(ep, c->persist.epoch, sizeof ep, hipMemcpyDeviceToHost));
+    tag = ep[0] - 1u;
+    HIP_TRY(hipMemcpy(op->gran, c->persist.gran, (size_t)op->gran_n * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(op->lm_parts, c->persist.gran + slab * nl, (size_t)512 * 8, hipMemcpyDeviceToHost));
+    int32_t ids1[2] = {0, 0};
+    HIP_TRY(hipMemcpy(ids1, dids, sizeof ids1, hipMemcpyDeviceToHost));
+    if (dbak) D2H(op->kv_bak, dbak, op->kv_bak_n);
+    if (state_io_download(c, sd, op->state)) return 1;
+    for (int i = 0; i < 3; ++i) op->epoch[i] = ep[i];
+    op->tag = tag;
+    op->err = *reinterpret_cast<volatile unsigned*>(c->persist_err);
+    op->id_out = ids1[0];
+    for (int i = 0; i < 4; ++i) op->route[i] = inst[i];
+    op->route[4] = grid;
+    op->route[5] = shape.GL;
+    if (persist_failed(c)) {
+        // not provoked here (the fault knobs are off): recovered as every entry point recovers it,
+        // and reported — the outputs above are what the failed launch left
+        if (persist_recover(c, nullptr)) return 1;
+        return fail("%s: a workgroup gave up on a hand-off at position %d", who, (int)op->err - 1);
+    }
+    return 0;
+}
+
 // One launch_attention / launch_attention_last call on plain host arrays (include/llama3hip.h).
 // Only what would take an index outside a buffer is checked ahead of the dispatcher (null arrays,
 // sizes, the key range); every shape rule is the dispatcher's own, and what it refuses is named

@@ -125,6 +125,7 @@ _SIGNATURES = {
     "l3_op_linear_bf16_host": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _P, _P, _F, _P]),
     "l3_op_gemm_host": (ctypes.c_int, [_P, _P]),
     "l3_op_decode_gemm_host": (ctypes.c_int, [_P, _P]),
+    "l3_op_decode_persist_host": (ctypes.c_int, [_P, _P]),
     "l3_op_argmax_parts_host": (ctypes.c_int, [_P, _P, _I32, _I32, _I32, _P, _P]),
     "l3_op_kv_restore_host": (ctypes.c_int, [_P, _P, _I64, _P, _I32, _I32, _I32, _I32, _I32]),
     "l3_op_attention_host": (ctypes.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I32,
@@ -193,6 +194,17 @@ class DecodeGemmOp(ctypes.Structure):
         ("state", ctypes.POINTER(DecStateIO)), ("kv_bak", _P),
         ("nparts", _I32), ("amax_part_n", _I32), ("amax_blocks", _I32), ("amax_nct", _I32), ("amax_in_n", _I32),
         ("pos_adv", _I32), ("pos_dev", _I32), ("pad", _I32),
+    ]
+
+
+class DecodePersistOp(ctypes.Structure):
+    """l3_decode_persist_op (include/llama3hip.h)."""
+    _fields_ = [
+        ("struct_size", _I32), ("token", _I32), ("steps", _I32), ("use_kv_bak", _I32),
+        ("state", ctypes.POINTER(DecStateIO)), ("gran", _P), ("gran_n", _I64), ("lm_parts", _P), ("kv_bak", _P),
+        ("kv_bak_n", _I64),
+        ("epoch", ctypes.c_uint32 * 3), ("tag", ctypes.c_uint32), ("err", ctypes.c_uint32), ("id_out", _I32),
+        ("route", _I32 * 8),
     ]
 
 
@@ -1417,6 +1429,55 @@ class Context:
         check(lib().l3_op_kv_restore_host(self._h, ptr(ck), ck.shape[0], ptr(b), b.shape[0], ck.shape[1], ck.shape[2],
                                           ck.shape[3], int(pos)))
         return ck
+
+    def op_decode_persist(self, token: int, state: DecState, *, steps: int = 1, kv_bak: bool = False) -> dict:
+        """One persistent decode step (``steps`` 2: two chained launches) launched directly, with every
+        stage's output (l3_op_decode_persist_host).  ``state``: a one-row DecState at the step's
+        position, updated in place.  Returns ``tags`` / ``vals`` per layer as dicts of the stages
+        ``qkv, o, h1, hid, h2`` (uint32 / float32 arrays, the LAST launch's granules), ``lm_tag`` [256, 2],
+        ``lm_val`` float32 [256] and ``lm_idx`` int32 [256] (the lm partial granules), ``epoch`` [3],
+        ``tag``, ``err``, ``id``, ``kv_bak`` [n_layers, 8, 32, 2, KVH, HD] (``gemm_sentinel(.., 14)``
+        before the launch; a layer's block [0] holds the one-sequence slots [32][k, v][KVH][HD], the
+        other seven are the room of the batched layout and stay untouched) or None, and ``route``: ``instance`` (NCD, NCF, KPF, LMPF), ``grid``, ``GL``."""
+        d = self.dims
+        H, KVH, D, FD, nl = d.n_heads, d.n_kv_heads, d.dim, d.hidden_dim, d.n_layers
+        HD = D // H
+        sizes = [("qkv", (H + 2 * KVH) * HD), ("o", H * HD), ("h1", D), ("hid", FD), ("h2", D)]
+        slab = sum(n for _, n in sizes)
+        if state.rows != 1:
+            raise ValueError("a one-row state")
+        op = DecodePersistOp()
+        op.struct_size = ctypes.sizeof(DecodePersistOp)
+        op.token, op.steps, op.use_kv_bak = int(token), int(steps), int(bool(kv_bak))
+        gran = np.zeros(nl * slab, np.uint64)
+        lm = np.zeros(512, np.uint64)
+        op.gran, op.gran_n, op.lm_parts = ptr(gran), gran.size, ptr(lm)
+        kb = None
+        if kv_bak:
+            kb = gemm_sentinel((nl, 8, KV_BAK_SLOTS, 2, KVH, HD), 14).copy()
+            op.kv_bak, op.kv_bak_n = ptr(kb), kb.size
+        io = state._io()
+        op.state = ctypes.pointer(io)
+        check(lib().l3_op_decode_persist_host(self._h, ctypes.byref(op)))
+        state._take(io)
+        g = gran.reshape(nl, slab)
+        tags, vals = [], []
+        for l in range(nl):
+            o, t, v = 0, {}, {}
+            for name, n in sizes:
+                t[name] = (g[l, o:o + n] >> np.uint64(32)).astype(np.uint32)
+                v[name] = (g[l, o:o + n] & np.uint64(0xFFFFFFFF)).astype(np.uint32).view(np.float32)
+                o += n
+            tags.append(t)
+            vals.append(v)
+        lo = (lm & np.uint64(0xFFFFFFFF)).astype(np.uint32).reshape(256, 2)
+        return {
+            "tags": tags, "vals": vals, "lm_tag": (lm >> np.uint64(32)).astype(np.uint32).reshape(256, 2),
+            "lm_val": lo[:, 0].copy().view(np.float32), "lm_idx": lo[:, 1].copy().view(np.int32),
+            "epoch": [int(x) for x in op.epoch], "tag": int(op.tag), "err": int(op.err), "id": int(op.id_out),
+            "kv_bak": kb,
+            "route": {"instance": tuple(int(x) for x in op.route[:4]), "grid": int(op.route[4]), "GL": int(op.route[5])},
+        }
 
     def op_attention(self, q, cache_k, cache_v, start_pos: int, n_heads: int, *, last: bool = False,
                      pos_dev: bool = False, wo=None, out=None, scaled: bool = False):

@@ -67,6 +67,18 @@ def test_decode_gemm_struct_layouts():
         assert name in l3hip.header_symbols() and name in l3hip._SIGNATURES
 
 
+def test_decode_persist_struct_layout():
+    """l3_decode_persist_op as the binding lays it out: four int32, six 8-byte fields, the epoch words,
+    tag, err and id, then the route report; no hidden padding (the library checks struct_size)."""
+    assert ctypes.sizeof(l3hip.DecodePersistOp) == 4 * 4 + 6 * 8 + 6 * 4 + 8 * 4
+    assert l3hip.DecodePersistOp.state.offset == 16 and l3hip.DecodePersistOp.epoch.offset == 64
+    assert l3hip.DecodePersistOp.route.offset == ctypes.sizeof(l3hip.DecodePersistOp) - 8 * 4
+    assert "l3_op_decode_persist_host" in l3hip.header_symbols() and "l3_op_decode_persist_host" in l3hip._SIGNATURES
+    op = l3hip.DecodePersistOp()
+    assert l3hip.lib().l3_op_decode_persist_host(None, ctypes.byref(op)) != 0
+    assert b"null context" in l3hip.lib().l3_last_error()
+
+
 def test_library_path_is_in_tree():
     assert os.path.dirname(l3hip.LIB_PATH).endswith(os.path.join("llama3.np_amd", "csrc"))
 
