@@ -3,11 +3,11 @@
 //
 // Device layout (one context per GPU, everything resident in HBM for the context's life):
 //   emb        [VS, D]                       model.embed_tokens.weight
-//   per layer  wqkv [H*HD + 2*KVH*HD, D]     q|k|v rows stacked (one GEMM)
-//              wo   [D, H*HD]
-//              wgu  [2*FD, D]                gate/up interleaved in 16-row groups (one GEMM
+//   per layer  qkv  [H*HD + 2*KVH*HD, D]     q|k|v rows stacked (one GEMM)
+//              o    [D, H*HD]
+//              gu   [2*FD, D]                gate/up interleaved in 16-row groups (one GEMM
 //                                            whose epilogue pairs gate_j with up_j)
-//              wd   [D, FD]
+//              dn   [D, FD]                  (each a Weight record: the fp32 tensor and its opt-in copies)
 //              n_attn / n_ffn [D]            RMSNorm weights, applied inside the GEMMs
 //              cache_k / cache_v [maxB, KVH, M, HD]  zero-initialised, persistent
 //                                            (fp32, or bf16 at two bytes per element in a context
@@ -68,11 +68,33 @@ static int fail(const char* fmt, ...) {
 #define CHECK_CTX(ctx) \
     if (!(ctx)) return fail("null context")
 
+// One projection as the context holds it: the fp32 tensor, which every kernel can read, and the
+// opt-in copies made from it.  bind_weight puts a record into a launch's GemmArgs; each_weight
+// walks every record of a context (teardown, the x6 pieces, the conversion at l3_finalize).
+struct Weight {
+    float* w = nullptr;  // [rows, K] fp32 (the layout comment at the top of the file)
+    int64_t rows = 0;
+    int K = 0;
+    // the opt-in x6 GEMM path (gemm_x6.h, l3_set_gemm_x6): three bf16 pieces [rows][3][K], made
+    // from the folded fp32 weight (null when the path is off; the lm_head has none)
+    unsigned short* x6 = nullptr;
+    // opt-in bf16 weight storage (l3_set_weight_bf16): bf16 in the fp32 tensor's row layout and
+    // without the norm fold, made by l3_finalize (null when the mode is off); read by the
+    // bf16-weight GEMV and rows kernel, with `norm` applied to the activations (GemmArgs::norm_w)
+    unsigned short* b = nullptr;
+    // opt-in fp8 weight storage (l3_set_weight_fp8): e4m3fn codes in the same layout, unfolded,
+    // with one power-of-two scale per row (null when the mode is off; never beside the bf16
+    // copy); read by the fp8 forms of the same two kernels (GemmArgs::Wq, wq_scale)
+    unsigned char* q = nullptr;
+    float* s = nullptr;
+    // the RMSNorm weight [K] the consuming GEMM applies to its activations when it reads a
+    // compact copy (the fp32 tensor carries it folded): n_attn for qkv, n_ffn for gate|up,
+    // final_norm for the lm_head, null for o and down.  Not owned
+    const float* norm = nullptr;
+};
+
 struct Layer {
-    float* wqkv = nullptr;
-    float* wo = nullptr;
-    float* wgu = nullptr;
-    float* wd = nullptr;
+    Weight qkv, o, gu, dn;
     float* n_attn = nullptr;
     float* n_ffn = nullptr;
     // [maxB, KVH, Smax, HD] of the context's kv_dtype.  In a bf16 context (l3_create_kv) the
@@ -83,18 +105,6 @@ struct Layer {
     unsigned have = 0;  // bitmask of uploaded kinds
     // RMSNorm weight folded into the consuming GEMM's W columns at l3_finalize
     bool folded_qkv = false, folded_gu = false;
-    // the opt-in x6 GEMM path (gemm_x6.h, l3_set_gemm_x6): each weight as three bf16 pieces
-    // [N][3][K], made from the folded fp32 weight (null when the path is off)
-    unsigned short *wqkv3 = nullptr, *wo3 = nullptr, *wgu3 = nullptr, *wd3 = nullptr;
-    // opt-in bf16 weight storage (l3_set_weight_bf16): each weight as bf16, in the fp32 tensor's row
-    // layout and without the norm fold, made by l3_finalize (null when the mode is off); read by
-    // the bf16-weight GEMV, with n_attn / n_ffn applied to the activations (GemmArgs::norm_w)
-    unsigned short *wqkvb = nullptr, *wob = nullptr, *wgub = nullptr, *wdb = nullptr;
-    // opt-in fp8 weight storage (l3_set_weight_fp8): each weight as e4m3fn codes in the same layout,
-    // unfolded, with one power-of-two scale per row (null when the mode is off; never beside the
-    // bf16 copies); read by the fp8 forms of the same two kernels (GemmArgs::Wq, wq_scale)
-    unsigned char *wqkvq = nullptr, *woq = nullptr, *wguq = nullptr, *wdq = nullptr;
-    float *wqkvs = nullptr, *wos = nullptr, *wgus = nullptr, *wds = nullptr;
 };
 
 struct Timer {
@@ -116,9 +126,8 @@ struct l3_ctx {
     int split = 2;                   // parts (1 = off); l3_set_batch_split, L3_BATCH_SPLIT
     bool gemm_x6 = false;            // prefill GEMMs on the x6 path (l3_set_gemm_x6, L3_GEMM_X6)
     // bf16 weight storage (l3_set_weight_bf16, L3_WEIGHT_BF16): 0 off, 1 exact, 2 round; taken at
-    // l3_finalize, which makes the bf16 copies (Layer::wqkvb ..., lm_headb) the decode GEMVs stream
+    // l3_finalize, which makes the bf16 copies (Weight::b of every projection) the decode GEMVs stream
     int weight_bf16 = 0;
-    unsigned short* lm_headb = nullptr;
     int64_t wb_bytes = 0;            // bytes of the bf16 copies
     int64_t wb_launches = 0;         // GEMV launches issued on them (a captured step: at capture)
     // 2 .. wb_rows rows on the bf16 copies (l3_set_weight_bf16_rows, L3_WEIGHT_BF16_ROWS /
@@ -130,11 +139,9 @@ struct l3_ctx {
     int64_t wb_rows_min_bytes = WB_ROWS_MIN_BYTES_DEFAULT;
     int64_t wb_rows_launches = 0;
     // fp8 weight storage (l3_set_weight_fp8, L3_WEIGHT_FP8): 0 off, 1 exact, 2 round; taken at
-    // l3_finalize, which makes the code / scale copies (Layer::wqkvq / wqkvs ..., lm_headq / lm_heads);
+    // l3_finalize, which makes the code / scale copies (Weight::q / s of every projection);
     // exclusive with weight_bf16.  The rows setting above governs whichever copy the context has
     int weight_fp8 = 0;
-    unsigned char* lm_headq = nullptr;
-    float* lm_heads = nullptr;
     int64_t wq_bytes = 0;            // bytes of the codes and the scales
     int64_t wq_launches = 0;         // GEMV launches issued on them (a captured step: at capture)
     int64_t wq_rows_launches = 0;    // launches of the rows kernel's fp8 form
@@ -156,7 +163,7 @@ struct l3_ctx {
     int kv_dtype = L3_KV_F32;        // KV-cache element (l3_create_kv), fixed for the context's life
     int HD = 0, qdim = 0, kvdim = 0, qkvn = 0;
     float* emb = nullptr;
-    float* lm_head = nullptr;
+    Weight lm_head;
     float* final_norm = nullptr;
     float* rope_cos = nullptr;
     float* rope_sin = nullptr;
@@ -403,6 +410,31 @@ static void dfree(void* p) {
     if (p) (void)hipFree(p);
 }
 
+// Every projection of the context, in upload order: f(record, layer, which) for each layer's
+// qkv, o, gate|up and down, then the lm_head (layer -1; its record is empty in a layer-only context)
+enum { P_QKV, P_O, P_GU, P_DN, P_LM };
+template <class F>
+static void each_weight(l3_ctx* c, F&& f) {
+    for (int li = 0; li < (int)c->layers.size(); ++li) {
+        Layer& L = c->layers[(size_t)li];
+        f(L.qkv, li, P_QKV); f(L.o, li, P_O); f(L.gu, li, P_GU); f(L.dn, li, P_DN);
+    }
+    f(c->lm_head, -1, P_LM);
+}
+
+// W, W3, Wb, Wq, wq_scale and norm_w of a launch from a projection's record, from weight row
+// row0 on (the caller sets N and K).  The x6 pieces only where the site says X6: which launches may
+// leave the fp32 kernels for the x6 path is each site's own rule.  Allocates nothing
+enum Pieces { NO_X6, X6 };
+static void bind_weight(GemmArgs& g, const Weight& W, Pieces x6, int64_t row0 = 0) {
+    g.W = W.w + row0 * W.K;
+    g.W3 = x6 == X6 && W.x6 ? W.x6 + row0 * 3 * W.K : nullptr;
+    g.Wb = W.b ? W.b + row0 * W.K : nullptr;
+    g.Wq = W.q ? W.q + row0 * W.K : nullptr;
+    g.wq_scale = W.s ? W.s + row0 : nullptr;
+    g.norm_w = W.b || W.q ? W.norm : nullptr;
+}
+
 static void drop_decode_graph(l3_ctx* c) {
     if (c->dec_exec) (void)hipGraphExecDestroy(c->dec_exec);
     if (c->dec_graph) (void)hipGraphDestroy(c->dec_graph);
@@ -598,19 +630,24 @@ extern "C" int l3_create_kv(int32_t device, const l3_dims* dims, int32_t kv_dtyp
     if (d.n_layers > 0) {
         const int64_t D = d.dim, FD = d.hidden_dim;
         const int64_t cache = kv_cache_bytes(c);  // at the element size: no fp32 allocation first
+        auto alloc = [](Weight& W, int64_t rows, int64_t K) {
+            W.rows = rows; W.K = (int)K;
+            return hipMalloc(&W.w, rows * K * 4);
+        };
         for (auto& L : c->layers) {
-            if (hipMalloc(&L.wqkv, c->qkvn * D * 4) || hipMalloc(&L.wo, D * c->qdim * 4) ||
-                hipMalloc(&L.wgu, 2 * FD * D * 4) || hipMalloc(&L.wd, D * FD * 4) ||
+            if (alloc(L.qkv, c->qkvn, D) || alloc(L.o, D, c->qdim) || alloc(L.gu, 2 * FD, D) || alloc(L.dn, D, FD) ||
                 hipMalloc(&L.n_attn, D * 4) || hipMalloc(&L.n_ffn, D * 4) ||
                 hipMalloc(&L.cache_k, cache) || hipMalloc(&L.cache_v, cache))
                 return bail(fail("l3_create: out of device memory (layers)"));
+            L.qkv.norm = L.n_attn; L.gu.norm = L.n_ffn;
             if (hipMemset(L.cache_k, 0, cache) || hipMemset(L.cache_v, 0, cache))
                 return bail(fail("l3_create: memset failed"));
         }
         const int64_t VD = (int64_t)d.vocab_size * D;
-        if (VD > 0 && (hipMalloc(&c->emb, VD * 4) || hipMalloc(&c->lm_head, VD * 4) ||
+        if (VD > 0 && (hipMalloc(&c->emb, VD * 4) || alloc(c->lm_head, d.vocab_size, D) ||
                        hipMalloc(&c->final_norm, D * 4)))
             return bail(fail("l3_create: out of device memory (embedding / lm_head)"));
+        c->lm_head.norm = c->final_norm;
         // RoPE tables: llama3.py:31-38 in double, then fp32
         const int half = HD / 2;
         std::vector<float> cs((size_t)d.max_seq_len * half), sn(cs.size());
@@ -639,16 +676,11 @@ extern "C" int l3_destroy(l3_ctx* c) {
     if (c->comm_stream) (void)hipStreamDestroy(c->comm_stream);
     if (c->comm_fwd_ev) (void)hipEventDestroy(c->comm_fwd_ev);
     if (c->comm_done_ev) (void)hipEventDestroy(c->comm_done_ev);
+    each_weight(c, [](Weight& W, int, int) { dfree(W.w); dfree(W.x6); dfree(W.b); dfree(W.q); dfree(W.s); });
     for (auto& L : c->layers) {
-        dfree(L.wqkv); dfree(L.wo); dfree(L.wgu); dfree(L.wd); dfree(L.n_attn); dfree(L.n_ffn);
-        dfree(L.cache_k); dfree(L.cache_v);
-        dfree(L.wqkv3); dfree(L.wo3); dfree(L.wgu3); dfree(L.wd3);
-        dfree(L.wqkvb); dfree(L.wob); dfree(L.wgub); dfree(L.wdb);
-        dfree(L.wqkvq); dfree(L.woq); dfree(L.wguq); dfree(L.wdq);
-        dfree(L.wqkvs); dfree(L.wos); dfree(L.wgus); dfree(L.wds);
+        dfree(L.n_attn); dfree(L.n_ffn); dfree(L.cache_k); dfree(L.cache_v);
     }
-    dfree(c->lm_headb); dfree(c->lm_headq); dfree(c->lm_heads);
-    dfree(c->emb); dfree(c->lm_head); dfree(c->final_norm); dfree(c->rope_cos); dfree(c->rope_sin);
+    dfree(c->emb); dfree(c->final_norm); dfree(c->rope_cos); dfree(c->rope_sin);
     dfree(c->h); dfree(c->q); dfree(c->attn); dfree(c->hid); dfree(c->logits); dfree(c->ids);
     dfree(c->oparts); dfree(c->amax_part); dfree(c->hsum); dfree(c->skws); dfree(c->amax_rows);
     dfree(c->amax); dfree(c->gather_ids); dfree(c->embed_tab);
@@ -717,7 +749,7 @@ extern "C" int l3_upload_weight(l3_ctx* c, int32_t layer, int32_t kind, const fl
             c->have_emb = true;
             return 0;
         case L3_W_LM_HEAD:
-            if (expect_shape(kind, rows, cols, VS, D) || h2d(c->lm_head, VS * D)) return 1;
+            if (expect_shape(kind, rows, cols, VS, D) || h2d(c->lm_head.w, VS * D)) return 1;
             c->have_lm = true;
             return 0;
         case L3_W_FINAL_NORM:
@@ -725,31 +757,31 @@ extern "C" int l3_upload_weight(l3_ctx* c, int32_t layer, int32_t kind, const fl
             c->have_fnorm = true;
             return 0;
         case L3_W_Q:
-            if (expect_shape(kind, rows, cols, c->qdim, D) || h2d(L->wqkv, c->qdim * D)) return 1;
+            if (expect_shape(kind, rows, cols, c->qdim, D) || h2d(L->qkv.w, c->qdim * D)) return 1;
             break;
         case L3_W_K:
-            if (expect_shape(kind, rows, cols, c->kvdim, D) || h2d(L->wqkv + c->qdim * D, c->kvdim * D))
+            if (expect_shape(kind, rows, cols, c->kvdim, D) || h2d(L->qkv.w + c->qdim * D, c->kvdim * D))
                 return 1;
             break;
         case L3_W_V:
             if (expect_shape(kind, rows, cols, c->kvdim, D) ||
-                h2d(L->wqkv + (c->qdim + c->kvdim) * D, c->kvdim * D))
+                h2d(L->qkv.w + (c->qdim + c->kvdim) * D, c->kvdim * D))
                 return 1;
             break;
         case L3_W_O:
-            if (expect_shape(kind, rows, cols, D, c->qdim) || h2d(L->wo, D * c->qdim)) return 1;
+            if (expect_shape(kind, rows, cols, D, c->qdim) || h2d(L->o.w, D * c->qdim)) return 1;
             break;
         case L3_W_GATE:
         case L3_W_UP: {
             if (expect_shape(kind, rows, cols, FD, D)) return 1;
             // 16-row groups: fused row 32g + c <- gate row 16g + c, fused row 32g + 16 + c <- up
-            float* dst = L->wgu + (kind == L3_W_UP ? 16 * D : 0);
+            float* dst = L->gu.w + (kind == L3_W_UP ? 16 * D : 0);
             HIP_TRY(hipMemcpy2D(dst, 32 * D * 4, host, 16 * D * 4, 16 * D * 4, FD / 16,
                                 hipMemcpyHostToDevice));
             break;
         }
         case L3_W_DOWN:
-            if (expect_shape(kind, rows, cols, D, FD) || h2d(L->wd, D * FD)) return 1;
+            if (expect_shape(kind, rows, cols, D, FD) || h2d(L->dn.w, D * FD)) return 1;
             break;
         case L3_W_ATTN_NORM:
             if (expect_shape(kind, rows, cols, 1, D) || h2d(L->n_attn, D)) return 1;
@@ -772,26 +804,20 @@ static const unsigned NEED_LAYER = NEED_ATTN | (1u << L3_W_GATE) | (1u << L3_W_U
 // the x6 pieces of every layer weight (gemm_x6.h), from the weights as the GEMMs use them
 // (after the RMSNorm fold); free_x6 drops them
 static void free_x6(l3_ctx* c) {
-    for (auto& L : c->layers) {
-        dfree(L.wqkv3); dfree(L.wo3); dfree(L.wgu3); dfree(L.wd3);
-        L.wqkv3 = L.wo3 = L.wgu3 = L.wd3 = nullptr;
-    }
+    each_weight(c, [](Weight& W, int, int) { dfree(W.x6); W.x6 = nullptr; });
 }
 
 static int make_x6(l3_ctx* c) {
-    const int64_t D = c->d.dim, FD = c->d.hidden_dim;
     hipError_t e = hipSuccess;
-    for (auto& L : c->layers) {
-        if (L.wqkv3) continue;
-        if (hipMalloc(&L.wqkv3, c->qkvn * D * 6) || hipMalloc(&L.wo3, D * c->qdim * 6) ||
-            hipMalloc(&L.wgu3, 2 * FD * D * 6) || hipMalloc(&L.wd3, D * FD * 6)) {
-            free_x6(c);
-            return fail("l3_set_gemm_x6: out of device memory (1.5x the layer weights)");
-        }
-        if (e == hipSuccess) e = launch_split_planes(L.wqkv, L.wqkv3, c->qkvn, (int)D, c->stream);
-        if (e == hipSuccess) e = launch_split_planes(L.wo, L.wo3, D, c->qdim, c->stream);
-        if (e == hipSuccess) e = launch_split_planes(L.wgu, L.wgu3, 2 * FD, (int)D, c->stream);
-        if (e == hipSuccess) e = launch_split_planes(L.wd, L.wd3, D, (int)FD, c->stream);
+    bool oom = false;
+    each_weight(c, [&](Weight& W, int, int which) {  // the layers' weights: the lm_head has no x6 launch
+        if (which == P_LM || W.x6 || oom || e != hipSuccess) return;
+        if (hipMalloc(&W.x6, (size_t)W.rows * W.K * 6) != hipSuccess) oom = true;
+        else e = launch_split_planes(W.w, W.x6, W.rows, W.K, c->stream);
+    });
+    if (oom) {
+        free_x6(c);
+        return fail("l3_set_gemm_x6: out of device memory (1.5x the layer weights)");
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) {  // no half-made pieces: the GEMMs run on them as soon as they exist
@@ -824,7 +850,7 @@ extern "C" int l3_set_gemm_x6(l3_ctx* c, int32_t on) {
 }
 
 // q is stored pre-scaled by log2(e) / sqrt(HD) (the attention's exp2 softmax)
-static float qkv_q_scale(const l3_ctx* c) { return (float)(1.4426950408889634 / std::sqrt((double)c->HD)); }
+static float qkv_q_scale(int HD) { return (float)(1.4426950408889634 / std::sqrt((double)HD)); }
 
 // The layer-0 QKV table (embed_qkv.h): true when it exists.  may_build: make it now, on c->stream
 // (the caller's launches are ordered after c->stream: run_layer on it, forward_dev before its
@@ -844,9 +870,9 @@ static bool embed_table(l3_ctx* c, bool may_build) {
         return false;
     }
     GemmArgs t{};
-    t.A = c->emb; t.lda = c->d.dim; t.W = c->layers[0].wqkv; t.C = tab; t.ldc = c->qkvn;
+    t.A = c->emb; t.lda = c->d.dim; t.W = c->layers[0].qkv.w; t.C = tab; t.ldc = c->qkvn;
     t.M = (int)VS; t.N = c->qkvn; t.K = c->d.dim; t.norm = true; t.eps = c->d.norm_eps;
-    t.H = c->d.n_heads; t.KVH = c->d.n_kv_heads; t.HD = c->HD; t.q_scale = qkv_q_scale(c);
+    t.H = c->d.n_heads; t.KVH = c->d.n_kv_heads; t.HD = c->HD; t.q_scale = qkv_q_scale(c->HD);
     if (launch_qkv_table(t, c->stream) != hipSuccess) {
         (void)hipGetLastError();
         (void)hipFree(tab);
@@ -882,14 +908,13 @@ extern "C" int l3_set_embed_qkv(l3_ctx* c, int32_t on, int64_t max_bytes) {
 // ---- bf16 weight storage (DESIGN.md "bf16 weight storage") ------------------------------------
 static int group_members(const l3_group* g);  // (below)
 
-static void free_bf16(l3_ctx* c) {
-    for (auto& L : c->layers) {
-        dfree(L.wqkvb); dfree(L.wob); dfree(L.wgub); dfree(L.wdb);
-        L.wqkvb = L.wob = L.wgub = L.wdb = nullptr;
-    }
-    dfree(c->lm_headb);
-    c->lm_headb = nullptr;
-    c->wb_bytes = 0;
+// the compact copies of either format (a context has at most one)
+static void free_compact(l3_ctx* c) {
+    each_weight(c, [](Weight& W, int, int) {
+        dfree(W.b); dfree(W.q); dfree(W.s);
+        W.b = nullptr; W.q = nullptr; W.s = nullptr;
+    });
+    c->wb_bytes = c->wq_bytes = 0;
 }
 
 extern "C" int l3_set_weight_bf16(l3_ctx* c, int32_t mode) {
@@ -960,19 +985,6 @@ static int ffn_pair(l3_ctx* c, const GemmArgs& gu, const GemmArgs& dn, hipStream
 }
 
 // ---- fp8 weight storage (DESIGN.md "fp8 weight storage") --------------------------------------
-static void free_fp8(l3_ctx* c) {
-    for (auto& L : c->layers) {
-        dfree(L.wqkvq); dfree(L.woq); dfree(L.wguq); dfree(L.wdq);
-        dfree(L.wqkvs); dfree(L.wos); dfree(L.wgus); dfree(L.wds);
-        L.wqkvq = L.woq = L.wguq = L.wdq = nullptr;
-        L.wqkvs = L.wos = L.wgus = L.wds = nullptr;
-    }
-    dfree(c->lm_headq); dfree(c->lm_heads);
-    c->lm_headq = nullptr;
-    c->lm_heads = nullptr;
-    c->wq_bytes = 0;
-}
-
 extern "C" int l3_set_weight_fp8(l3_ctx* c, int32_t mode) {
     CHECK_CTX(c);
     if (mode < 0 || mode > 2) return fail("l3_set_weight_fp8: mode %d (0 off, 1 exact, 2 round)", mode);
@@ -998,156 +1010,94 @@ extern "C" int l3_weight_fp8_info(l3_ctx* c, int32_t* mode, int64_t* bytes, int6
     return 0;
 }
 
-// The code / scale copies of every projection whose kinds were all uploaded, and of the lm_head,
-// from the weights as uploaded (before the norm fold).  A non-finite element fails the call in
-// both modes.  Exact mode: any element that is not scale * float(code) of its own row fails the
-// call — the first (layer, kind) in upload order is named — and leaves the context as it was.
-// Round mode: the fp32 tensors become that value too, so the kernels that read them compute the
-// same model.
-static int finalize_fp8(l3_ctx* c) {
+// The compact copies (bf16, or fp8 codes and row scales) of every projection whose kinds were all
+// uploaded, and of the lm_head, from the weights as uploaded (before the norm fold).  fp8: a
+// non-finite element fails the call in both modes.  Exact mode: any element that is not the
+// format's value of itself (a bf16 value; scale * float(code) of its own row) fails the call —
+// the first (layer, kind) in upload order is named — and leaves the context as it was.  Round
+// mode: the fp32 tensors become that value too, so the kernels that read them (prefill, skinny,
+// split-K, x6, the layer-0 table, the persistent step) compute the same model.
+static int finalize_compact(l3_ctx* c, bool fp8) {
     static const char* const kind_name[] = {"self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj",
                                             "self_attn.o_proj", "mlp.gate_proj", "mlp.up_proj", "mlp.down_proj"};
-    const int D = c->d.dim, FD = c->d.hidden_dim, VS = c->d.vocab_size;
+    const char* const fmt = fp8 ? "fp8" : "bf16";
+    const int mode = fp8 ? c->weight_fp8 : c->weight_bf16;
     const int nl = (int)c->layers.size();
-    const bool wr = c->weight_fp8 == 2;
-    // [nl + 1][7][4]: per layer and kind slot (kind - L3_W_Q; the lm_head: slot 0 of the last group)
-    // the four counters of launch_to_fp8_rows {inexact, inexact of the up rows, non-finite,
-    // non-finite of the up rows}; gate | up are one launch, on slot 4's group
+    const bool wr = mode == 2;
+    // A conversion launch adds into n counters from its own: launch_to_bf16 a pair {inexact,
+    // inexact of the up rows}, launch_to_fp8_rows four {inexact, inexact of the up rows,
+    // non-finite, non-finite of the up rows}.  A layer's kind slots (kind - L3_W_Q) lie cs counters
+    // apart; gate | up are one launch on slot 4, so with cs = 1 the up rows count in slot 5.  The
+    // lm_head's counters follow the layers'
+    const size_t cs = fp8 ? 4 : 1, n = fp8 ? 4 : 2, per = 6 * cs + n, ncnt = (size_t)nl * per + n;
     unsigned long long* cnt = nullptr;
-    const size_t per = 7 * 4, ncnt = (size_t)(nl + 1) * per;
     HIP_TRY(hipMalloc(&cnt, ncnt * 8));
     auto bail = [&](int rc) {
         (void)hipStreamSynchronize(c->stream);
         dfree(cnt);
-        free_fp8(c);
+        free_compact(c);
         return rc;
     };
     if (hipMemsetAsync(cnt, 0, ncnt * 8, c->stream) != hipSuccess) return bail(fail("l3_finalize: memset failed"));
-    const unsigned QKV = (1u << L3_W_Q) | (1u << L3_W_K) | (1u << L3_W_V);
-    const unsigned GU = (1u << L3_W_GATE) | (1u << L3_W_UP);
+    // per record (P_QKV .. P_DN): the kinds that must all be uploaded, and its first kind slot
+    const unsigned need[4] = {(1u << L3_W_Q) | (1u << L3_W_K) | (1u << L3_W_V), 1u << L3_W_O,
+                              (1u << L3_W_GATE) | (1u << L3_W_UP), 1u << L3_W_DOWN};
+    const int slot[5] = {0, 3, 4, 6, 0};
     hipError_t e = hipSuccess;
     int64_t bytes = 0;
-    auto conv = [&](float* w, unsigned char** codes, float** sc, int64_t rows, int K, int sel_rows,
-                    unsigned long long* k) {
-        if (e != hipSuccess) return;
-        e = hipMalloc(codes, (size_t)rows * K);
-        if (e == hipSuccess) e = hipMalloc(sc, (size_t)rows * 4);
-        if (e == hipSuccess) e = launch_to_fp8_rows(w, *codes, *sc, rows, K, sel_rows, wr, k, c->stream);
-        bytes += rows * K + rows * 4;
+    // rows [r0, r0 + rows) of W into its copy; sel_rows: the gate / up group height (0: one kind)
+    auto convert = [&](Weight& W, int64_t r0, int64_t rows, int sel_rows, unsigned long long* k) {
+        float* w = W.w + r0 * W.K;
+        return fp8 ? launch_to_fp8_rows(w, W.q + r0 * W.K, W.s + r0, rows, W.K, sel_rows, wr, k, c->stream)
+                   : launch_to_bf16(w, W.b + r0 * W.K, rows * W.K, (int64_t)sel_rows * W.K, wr, k, c->stream);
     };
-    for (int li = 0; li < nl; ++li) {
-        Layer& L = c->layers[li];
-        unsigned long long* k = cnt + (size_t)li * per;
-        if ((L.have & QKV) == QKV) {  // q | k | v stacked: one copy, a launch and a counter group per section
-            if (e == hipSuccess) e = hipMalloc(&L.wqkvq, (size_t)c->qkvn * D);
-            if (e == hipSuccess) e = hipMalloc(&L.wqkvs, (size_t)c->qkvn * 4);
-            const int64_t off[4] = {0, c->qdim, c->qdim + c->kvdim, c->qkvn};  // rows
-            for (int t = 0; t < 3 && e == hipSuccess; ++t)
-                e = launch_to_fp8_rows(L.wqkv + off[t] * D, L.wqkvq + off[t] * D, L.wqkvs + off[t], off[t + 1] - off[t],
-                                       D, 0, wr, k + 4 * t, c->stream);
-            bytes += (int64_t)c->qkvn * D + (int64_t)c->qkvn * 4;
+    each_weight(c, [&](Weight& W, int li, int which) {
+        const bool all = li >= 0 ? (c->layers[(size_t)li].have & need[which]) == need[which] : c->have_lm;
+        if (!all || e != hipSuccess) return;
+        const int64_t elems = W.rows * W.K;
+        if (fp8) {
+            e = hipMalloc(&W.q, (size_t)elems);
+            if (e == hipSuccess) e = hipMalloc(&W.s, (size_t)W.rows * 4);
+            bytes += elems + W.rows * 4;
+        } else {
+            e = hipMalloc(&W.b, (size_t)elems * 2);
+            bytes += elems * 2;
         }
-        if (L.have & (1u << L3_W_O)) conv(L.wo, &L.woq, &L.wos, D, c->qdim, 0, k + 4 * 3);
-        if ((L.have & GU) == GU) conv(L.wgu, &L.wguq, &L.wgus, 2 * (int64_t)FD, D, 16, k + 4 * 4);  // 16-row groups: gate, up
-        if (L.have & (1u << L3_W_DOWN)) conv(L.wd, &L.wdq, &L.wds, D, FD, 0, k + 4 * 6);
-    }
-    if (c->have_lm) conv(c->lm_head, &c->lm_headq, &c->lm_heads, VS, D, 0, cnt + (size_t)nl * per);
+        unsigned long long* k = cnt + (size_t)(li >= 0 ? li : nl) * per + cs * slot[which];
+        if (which == P_QKV) {  // q | k | v stacked: one copy, a launch and a slot per section
+            const int64_t off[4] = {0, c->qdim, c->qdim + c->kvdim, c->qkvn};  // rows
+            for (int t = 0; t < 3 && e == hipSuccess; ++t) e = convert(W, off[t], off[t + 1] - off[t], 0, k + cs * t);
+        } else if (e == hipSuccess) {
+            e = convert(W, 0, W.rows, which == P_GU ? 16 : 0, k);  // 16-row groups: gate, up
+        }
+    });
     std::vector<unsigned long long> h(ncnt, 0);
     if (e == hipSuccess) e = hipMemcpyAsync(h.data(), cnt, ncnt * 8, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        return bail(fail("l3_finalize: making the fp8 weight copies failed: %s", hipGetErrorString(e)));
+        return bail(fail("l3_finalize: making the %s weight copies failed: %s", fmt, hipGetErrorString(e)));
     }
-    // slot t of a layer: its inexact / non-finite counts (gate | up share a launch: the up rows'
-    // counts are the second of each pair of slot 4)
+    // kind slot t of a layer: its inexact (what 0) / non-finite (what 1) count; the up rows' counts
+    // are the second of each pair of slot 4
     auto count = [&](int li, int t, int what) {
         const unsigned long long* k = h.data() + (size_t)li * per;
-        return t == 5 ? k[4 * 4 + 2 * what + 1] : k[4 * t + 2 * what];
+        return t == 5 ? k[cs * 4 + 2 * what + 1] : k[cs * t + 2 * what];
     };
-    for (int what = 1; what >= (c->weight_fp8 == 1 ? 0 : 1); --what) {  // non-finite first, then exact mode's check
+    const char* const bad[2] = {fp8 ? "not fp8-e4m3 values at the row's scale" : "not bf16-representable", "not finite"};
+    for (int what = fp8 ? 1 : 0; what >= (mode == 1 ? 0 : 1); --what) {  // non-finite first, then exact mode's check
         for (int li = 0; li < nl; ++li)
             for (int t = 0; t < 7; ++t)
-                if (const unsigned long long n = count(li, t, what))
-                    return bail(fail("l3_finalize: weight_fp8%s: model.layers.%d.%s.weight (layer %d, kind %d) has %llu "
-                                     "elements that are %s", what ? "" : " exact mode", li, kind_name[t], li,
-                                     t + (int)L3_W_Q, n, what ? "not finite" : "not fp8-e4m3 values at the row's scale"));
-        if (const unsigned long long n = h[(size_t)nl * per + 2 * what])
-            return bail(fail("l3_finalize: weight_fp8%s: lm_head.weight (kind %d) has %llu elements that are %s",
-                             what ? "" : " exact mode", (int)L3_W_LM_HEAD, n,
-                             what ? "not finite" : "not fp8-e4m3 values at the row's scale"));
+                if (const unsigned long long m = count(li, t, what))
+                    return bail(fail("l3_finalize: weight_%s%s: model.layers.%d.%s.weight (layer %d, kind %d) has %llu "
+                                     "elements that are %s", fmt, what ? "" : " exact mode", li, kind_name[t], li,
+                                     t + (int)L3_W_Q, m, bad[what]));
+        if (const unsigned long long m = h[(size_t)nl * per + 2 * what])
+            return bail(fail("l3_finalize: weight_%s%s: lm_head.weight (kind %d) has %llu elements that are %s", fmt,
+                             what ? "" : " exact mode", (int)L3_W_LM_HEAD, m, bad[what]));
     }
     dfree(cnt);
-    c->wq_bytes = bytes;
-    return 0;
-}
-
-// The bf16 copies of every projection whose kinds were all uploaded, and of the lm_head, from the
-// weights as uploaded (before the norm fold).  Exact mode: any element that is not a bf16 value
-// fails the call — the first (layer, kind) in upload order is named — and leaves the context as it
-// was.  Round mode: the fp32 tensors become float(bf16(W)) too, so the kernels that read them
-// (prefill, skinny, split-K, x6, the layer-0 table, the persistent step) compute the same model.
-static int finalize_bf16(l3_ctx* c) {
-    static const char* const kind_name[] = {"self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj",
-                                            "self_attn.o_proj", "mlp.gate_proj", "mlp.up_proj", "mlp.down_proj"};
-    const int64_t D = c->d.dim, FD = c->d.hidden_dim, VS = c->d.vocab_size;
-    const int nl = (int)c->layers.size();
-    const bool wr = c->weight_bf16 == 2;
-    unsigned long long* cnt = nullptr;  // [nl][8] per-kind counts (slot = kind - L3_W_Q), then the lm_head's pair
-    const size_t ncnt = (size_t)nl * 8 + 2;
-    HIP_TRY(hipMalloc(&cnt, ncnt * 8));
-    auto bail = [&](int rc) {
-        (void)hipStreamSynchronize(c->stream);
-        dfree(cnt);
-        free_bf16(c);
-        return rc;
-    };
-    if (hipMemsetAsync(cnt, 0, ncnt * 8, c->stream) != hipSuccess) return bail(fail("l3_finalize: memset failed"));
-    const unsigned QKV = (1u << L3_W_Q) | (1u << L3_W_K) | (1u << L3_W_V);
-    const unsigned GU = (1u << L3_W_GATE) | (1u << L3_W_UP);
-    hipError_t e = hipSuccess;
-    int64_t bytes = 0;
-    auto conv = [&](float* w, unsigned short** out, int64_t n, int64_t sel, unsigned long long* k) {
-        if (e != hipSuccess) return;
-        e = hipMalloc(out, (size_t)n * 2);
-        if (e == hipSuccess) e = launch_to_bf16(w, *out, n, sel, wr, k, c->stream);
-        bytes += n * 2;
-    };
-    for (int li = 0; li < nl; ++li) {
-        Layer& L = c->layers[li];
-        unsigned long long* k = cnt + (size_t)li * 8;
-        if ((L.have & QKV) == QKV) {  // q | k | v stacked: one copy, a count per section
-            if (e == hipSuccess) e = hipMalloc(&L.wqkvb, (size_t)c->qkvn * D * 2);
-            const int64_t off[4] = {0, c->qdim * D, (c->qdim + c->kvdim) * D, c->qkvn * D};
-            for (int t = 0; t < 3 && e == hipSuccess; ++t)
-                e = launch_to_bf16(L.wqkv + off[t], L.wqkvb + off[t], off[t + 1] - off[t], 0, wr, k + t, c->stream);
-            bytes += c->qkvn * D * 2;
-        }
-        if (L.have & (1u << L3_W_O)) conv(L.wo, &L.wob, D * c->qdim, 0, k + 3);
-        if ((L.have & GU) == GU) conv(L.wgu, &L.wgub, 2 * FD * D, 16 * D, k + 4);  // 16-row groups: gate, up
-        if (L.have & (1u << L3_W_DOWN)) conv(L.wd, &L.wdb, D * FD, 0, k + 6);
-    }
-    if (c->have_lm) conv(c->lm_head, &c->lm_headb, VS * D, 0, cnt + (size_t)nl * 8);
-    std::vector<unsigned long long> h(ncnt, 0);
-    if (e == hipSuccess) e = hipMemcpyAsync(h.data(), cnt, ncnt * 8, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return bail(fail("l3_finalize: making the bf16 weight copies failed: %s", hipGetErrorString(e)));
-    }
-    if (c->weight_bf16 == 1) {
-        for (int li = 0; li < nl; ++li)
-            for (int t = 0; t < 7; ++t)
-                if (h[(size_t)li * 8 + t])
-                    return bail(fail("l3_finalize: weight_bf16 exact mode: model.layers.%d.%s.weight (layer %d, kind %d) "
-                                     "has %llu elements that are not bf16-representable", li, kind_name[t], li,
-                                     t + (int)L3_W_Q, h[(size_t)li * 8 + t]));
-        if (h[(size_t)nl * 8])
-            return bail(fail("l3_finalize: weight_bf16 exact mode: lm_head.weight (kind %d) has %llu elements that are "
-                             "not bf16-representable", (int)L3_W_LM_HEAD, h[(size_t)nl * 8]));
-    }
-    dfree(cnt);
-    c->wb_bytes = bytes;
+    (fp8 ? c->wq_bytes : c->wb_bytes) = bytes;
     return 0;
 }
 
@@ -1155,8 +1105,7 @@ extern "C" int l3_finalize(l3_ctx* c) {
     CHECK_CTX(c);
     if (c->finalized) return 0;
     if (set_dev(c)) return 1;
-    if (c->weight_bf16 && finalize_bf16(c)) return 1;
-    if (c->weight_fp8 && finalize_fp8(c)) return 1;
+    if ((c->weight_bf16 || c->weight_fp8) && finalize_compact(c, c->weight_fp8 != 0)) return 1;
     // Fold each RMSNorm weight into the columns of the GEMM that consumes the normalised rows
     // (attention norm -> wqkv, FFN norm -> wgu, final norm -> lm_head): the GEMMs then apply
     // only the per-row 1/rms factor.  Only where both were uploaded: a layer-only (attention)
@@ -1166,16 +1115,16 @@ extern "C" int l3_finalize(l3_ctx* c) {
     const unsigned GU = (1u << L3_W_GATE) | (1u << L3_W_UP);
     for (auto& L : c->layers) {
         if ((L.have & QKV) == QKV && (L.have & (1u << L3_W_ATTN_NORM))) {
-            HIP_TRY(launch_fold_cols(L.wqkv, c->qkvn, D, L.n_attn, c->stream));
+            HIP_TRY(launch_fold_cols(L.qkv.w, c->qkvn, D, L.n_attn, c->stream));
             L.folded_qkv = true;
         }
         if ((L.have & GU) == GU && (L.have & (1u << L3_W_FFN_NORM))) {
-            HIP_TRY(launch_fold_cols(L.wgu, 2 * (int64_t)c->d.hidden_dim, D, L.n_ffn, c->stream));
+            HIP_TRY(launch_fold_cols(L.gu.w, 2 * (int64_t)c->d.hidden_dim, D, L.n_ffn, c->stream));
             L.folded_gu = true;
         }
     }
     if (c->have_lm && c->have_fnorm) {
-        HIP_TRY(launch_fold_cols(c->lm_head, c->d.vocab_size, D, c->final_norm, c->stream));
+        HIP_TRY(launch_fold_cols(c->lm_head.w, c->d.vocab_size, D, c->final_norm, c->stream));
         c->folded_lm = true;
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1235,6 +1184,55 @@ static int check_call(l3_ctx* c, int B, int L, int start_pos) {
     return 0;
 }
 
+// The GEMM arguments of one block (llama3.py:239-261) for every path that drives a layer: M rows
+// in the caller's buffers at the caller's leading dimensions; x6: whether the launch may take the
+// x6 pieces; ws: the split-K workspace (null: none); skinny: the skinny MFMA kernel whatever M;
+// emb_rows (layer 0 of a model forward): the block's input rows are c->emb[emb_rows], which the
+// QKV GEMM gathers and the O-proj adds as its residual.  What belongs to one caller (the fused
+// QKV epilogue, fuse_o, the decode fold, kv_bak, split_rows) it sets on the result.
+//
+// rmsnorm -> QKV of x [M, D]; out: the raw rows [M, qkvn] (EPI_STORE), null for EPI_QKV
+static GemmArgs qkv_args(const l3_ctx* c, const Layer& Ly, int M, const float* x, int64_t ldx, float* out, Pieces x6,
+                         float* ws, bool skinny, const int32_t* emb_rows) {
+    GemmArgs g{};
+    g.A = x; g.lda = ldx; g.C = out; g.ldc = out ? c->qkvn : 0;
+    g.M = M; g.N = c->qkvn; g.K = c->d.dim; g.norm = true; g.eps = c->d.norm_eps;  // n_attn folded into the weight
+    bind_weight(g, Ly.qkv, x6);
+    g.ws = ws; g.ws_cap = c->skws_cap; g.force_skinny = skinny;
+    if (emb_rows) { g.A = c->emb; g.a_rows = emb_rows; }
+    return g;
+}
+
+// O-proj of attn [M, qdim] into h [M, D]: EPI_RESID adds in place (emb_rows: h = emb[emb_rows] + attn . Wo^T)
+static GemmArgs oproj_args(const l3_ctx* c, const Layer& Ly, int M, const float* attn, int64_t lda, float* h,
+                           int64_t ldh, Pieces x6, float* ws, bool skinny, const int32_t* emb_rows) {
+    GemmArgs o{};
+    o.A = attn; o.lda = lda; o.C = h; o.ldc = ldh;
+    o.M = M; o.N = c->d.dim; o.K = c->qdim; o.norm = false;
+    bind_weight(o, Ly.o, x6);
+    o.ws = ws; o.ws_cap = c->skws_cap; o.force_skinny = skinny;
+    if (emb_rows) { o.res_src = c->emb; o.res_rows = emb_rows; }
+    return o;
+}
+
+// rmsnorm -> gate|up -> SwiGLU of h [M, D] into hid [M, FD], and down + residual back onto h (ffn_pair)
+struct FfnPair { GemmArgs gu, dn; };
+static FfnPair ffn_args(const l3_ctx* c, const Layer& Ly, int M, float* h, int64_t ldh, float* hid, Pieces x6,
+                        float* ws, bool skinny) {
+    const int D = c->d.dim, FD = c->d.hidden_dim;
+    FfnPair f{};
+    GemmArgs &gu = f.gu, &dn = f.dn;
+    gu.A = h; gu.lda = ldh; gu.C = hid; gu.ldc = FD;
+    gu.M = M; gu.N = 2 * FD; gu.K = D; gu.norm = true; gu.eps = c->d.norm_eps;  // n_ffn folded into the weight
+    bind_weight(gu, Ly.gu, x6);
+    dn.A = hid; dn.lda = FD; dn.C = h; dn.ldc = ldh;
+    dn.M = M; dn.N = D; dn.K = FD; dn.norm = false;
+    bind_weight(dn, Ly.dn, x6);
+    gu.ws = dn.ws = ws; gu.ws_cap = dn.ws_cap = c->skws_cap;
+    gu.force_skinny = dn.force_skinny = skinny;
+    return f;
+}
+
 // one transformer block on the residual stream c->h [B*L, D] (llama3.py:239-261)
 // emb_ids: layer 0 of a model forward reads its input rows straight from the embedding table
 // (llama3.py:287 fused into the QKV GEMM's A gather and the O-proj's residual), so no embed
@@ -1263,40 +1261,30 @@ static int run_layer(l3_ctx* c, int li, int B, int L, int start_pos, const int* 
     float* attn = c->attn + r0 * c->qdim;
     float* hid = c->hid + r0 * FD;
     if (emb_ids) emb_ids += r0;
-    GemmArgs g{};
-    g.eps = c->d.norm_eps;
-    // rmsnorm -> QKV -> RoPE -> q + KV-cache append
-    g.A = h; g.lda = D; g.W = Ly.wqkv; g.C = nullptr; g.ldc = 0;
-    g.M = (int)T; g.N = c->qkvn; g.K = D; g.norm = true;  // n_attn folded into wqkv
+    // split-K workspace: one, for the GEMMs on c->stream (a batch split's parts keep > 256 rows,
+    // past launch_split's range, so no two streams ever share it)
+    float* skws = s == c->stream ? c->skws : nullptr;
+    // rmsnorm -> QKV -> RoPE -> q + KV-cache append (the x6 pieces take it past 32 rows)
+    GemmArgs g = qkv_args(c, Ly, (int)T, h, D, nullptr, X6, skws, false, emb_ids);
     g.q_out = q; g.cache_k = Ly.cache_k + cache0; g.cache_v = Ly.cache_v + cache0;
     g.rope_cos = c->rope_cos; g.rope_sin = c->rope_sin;
     g.L = L; g.start_pos = start_pos; g.H = c->d.n_heads; g.KVH = c->d.n_kv_heads; g.HD = c->HD;
     g.Smax = c->d.max_seq_len;
     g.pos_dev = pos_dev;
-    g.q_scale = qkv_q_scale(c);
-    if (emb_ids) { g.A = c->emb; g.a_rows = emb_ids; }
+    g.q_scale = qkv_q_scale(c->HD);
     if (emb_ids && c->fold_in) {  // the id comes from the previous step's lm_head partials
         g.a_rows = nullptr;
         g.amax_in = c->amax_part; g.amax_in_n = c->fold_n;
         g.amax_ids = c->dec_ids; g.amax_st = c->dec_state;  // read by gate|up / O-proj below
     }
     if (c->bak_capture) g.kv_bak = c->kv_bak + (int64_t)li * KV_BAK_SLOTS * 2 * 8 * c->d.n_kv_heads * c->HD;
-    // split-K workspace: one, for the GEMMs on c->stream (a batch split's parts keep > 256 rows,
-    // past launch_split's range, so no two streams ever share it)
-    float* skws = s == c->stream ? c->skws : nullptr;
-    g.ws = skws; g.ws_cap = c->skws_cap;
     const bool prune = last_rows && L > 1 && !emb_ids && !pos_dev;
     // a pruned block with more than 256 rows (the tiled QKV kernel): K / V for every row, q for
     // the last row of each sequence only (its RoPE at position start_pos + L - 1)
     const bool kv_only = prune && T > 256;
-    g.W3 = Ly.wqkv3;  // null unless the x6 path is on (then launch_gemm takes it past 32 rows)
-    g.Wb = Ly.wqkvb; g.Wq = Ly.wqkvq; g.wq_scale = Ly.wqkvs;  // null unless bf16 / fp8 weight storage is on
-    g.norm_w = Ly.wqkvb || Ly.wqkvq ? Ly.n_attn : nullptr;
-    if (kv_only) {
-        g.W = Ly.wqkv + (int64_t)c->qdim * D; g.N = 2 * c->kvdim; g.col_base = c->qdim;
-        if (g.W3) g.W3 += (int64_t)c->qdim * 3 * D;
-        if (g.Wb) g.Wb += (int64_t)c->qdim * D;
-        if (g.Wq) { g.Wq += (int64_t)c->qdim * D; g.wq_scale += c->qdim; }
+    if (kv_only) {  // the k | v rows of the stacked weight
+        bind_weight(g, Ly.qkv, X6, c->qdim);
+        g.N = 2 * c->kvdim; g.col_base = c->qdim;
     }
     // Layer 0 on embedding rows, exactly where launch_gemm would reach the tiled fp32 kernel with
     // a_rows set (more than 256 rows: past the GEMV, the skinny kernel and split-K, which round
@@ -1317,43 +1305,29 @@ static int run_layer(l3_ctx* c, int li, int B, int L, int start_pos, const int* 
         AttnArgs a{};
         a.cache_k = Ly.cache_k + cache0; a.cache_v = Ly.cache_v + cache0; a.out = attn;
         a.H = c->d.n_heads; a.KVH = c->d.n_kv_heads; a.HD = c->HD; a.Smax = c->d.max_seq_len;
-        GemmArgs o{};  // O-proj + residual on the last rows, in place on h
+        // the last rows' GEMMs: the skinny kernel on fp32 / compact weights (no x6), in place on h
+        const float* ol = kv_only ? attn : attn + (int64_t)(L - 1) * c->qdim;
+        GemmArgs o = oproj_args(c, Ly, B, ol, kv_only ? c->qdim : (int64_t)L * c->qdim, hl, (int64_t)L * D4, NO_X6,
+                                nullptr, true, nullptr);
+        FfnPair f = ffn_args(c, Ly, B, hl, (int64_t)L * D4, hid, NO_X6, nullptr, true);
+        o.split_rows = f.gu.split_rows = f.dn.split_rows = true;
         if (kv_only) {
             GemmArgs gq = g;  // q of the last rows: [B, qdim], compact
-            gq.A = hl; gq.lda = (int64_t)L * D4; gq.W = Ly.wqkv; gq.W3 = nullptr; gq.Wb = Ly.wqkvb; gq.Wq = Ly.wqkvq; gq.wq_scale = Ly.wqkvs; gq.N = c->qdim; gq.col_base = 0;
+            gq.A = hl; gq.lda = (int64_t)L * D4; bind_weight(gq, Ly.qkv, NO_X6); gq.N = c->qdim; gq.col_base = 0;
             gq.M = B; gq.L = 1; gq.start_pos = start_pos + L - 1; gq.force_skinny = gq.split_rows = true;
             gq.ws = nullptr;
             if (timed_on(c, L3_K_QKV, s, [&] { return gemm(c, EPI_QKV, gq, s); })) return 1;
             a.q = q; a.B = B; a.L = 1; a.start_pos = start_pos + L - 1;  // one query per sequence
             if (timed_on(c, L3_K_ATTN, s, [&] { return launch_attention(a, s); })) return 1;
-            o.A = attn; o.lda = c->qdim;
         } else {  // the last q-blocks of the full launch (same per-query arithmetic)
             a.q = q; a.B = B; a.L = L; a.start_pos = start_pos;
             if (timed_on(c, L3_K_ATTN, s, [&] { return launch_attention_last(a, s); })) return 1;
-            o.A = attn + (int64_t)(L - 1) * c->qdim; o.lda = (int64_t)L * c->qdim;
         }
-        o.W = Ly.wo; o.Wb = Ly.wob; o.Wq = Ly.woq; o.wq_scale = Ly.wos; o.C = hl; o.ldc = (int64_t)L * D4;
-        o.M = B; o.N = D4; o.K = c->qdim; o.norm = false; o.force_skinny = o.split_rows = true;
         if (timed_on(c, L3_K_OPROJ, s, [&] { return gemm(c, EPI_RESID, o, s); })) return 1;
-        GemmArgs gl{};  // rmsnorm -> gate|up -> SwiGLU on the last rows
-        gl.A = hl; gl.lda = (int64_t)L * D4; gl.W = Ly.wgu; gl.C = hid; gl.ldc = FD;
-        gl.Wb = Ly.wgub; gl.Wq = Ly.wguq; gl.wq_scale = Ly.wgus; gl.norm_w = Ly.wgub || Ly.wguq ? Ly.n_ffn : nullptr;
-        gl.M = B; gl.N = 2 * FD; gl.K = D4; gl.norm = true; gl.eps = c->d.norm_eps; gl.force_skinny = gl.split_rows = true;
-        if (timed_on(c, L3_K_GATEUP, s, [&] { return gemm(c, EPI_SWIGLU, gl, s); })) return 1;
-        GemmArgs dl{};  // down + residual on the last rows
-        dl.A = hid; dl.lda = FD; dl.W = Ly.wd; dl.Wb = Ly.wdb; dl.Wq = Ly.wdq; dl.wq_scale = Ly.wds; dl.C = hl; dl.ldc = (int64_t)L * D4;
-        dl.M = B; dl.N = D4; dl.K = FD; dl.norm = false; dl.force_skinny = dl.split_rows = true;
-        return timed_on(c, L3_K_DOWN, s, [&] { return gemm(c, EPI_RESID, dl, s); });
+        return ffn_pair(c, f.gu, f.dn, s);  // (skinny: never the fused kernel)
     }
-    GemmArgs gu{};  // rmsnorm -> gate|up -> SwiGLU
-    gu.A = h; gu.lda = D; gu.W = Ly.wgu; gu.W3 = Ly.wgu3; gu.C = hid; gu.ldc = FD;
-    gu.M = (int)T; gu.N = 2 * FD; gu.K = D; gu.norm = true;  // n_ffn folded into wgu
-    gu.Wb = Ly.wgub; gu.Wq = Ly.wguq; gu.wq_scale = Ly.wgus; gu.norm_w = Ly.wgub || Ly.wguq ? Ly.n_ffn : nullptr;
-    gu.eps = c->d.norm_eps;
-    GemmArgs dn{};  // down + residual
-    dn.A = hid; dn.lda = FD; dn.W = Ly.wd; dn.W3 = Ly.wd3; dn.C = h; dn.ldc = D;
-    dn.M = (int)T; dn.N = D; dn.K = FD; dn.norm = false; dn.Wb = Ly.wdb; dn.Wq = Ly.wdq; dn.wq_scale = Ly.wds;
-    gu.ws = dn.ws = skws; gu.ws_cap = dn.ws_cap = c->skws_cap;
+    FfnPair f = ffn_args(c, Ly, (int)T, h, D, hid, X6, skws, false);
+    GemmArgs &gu = f.gu, &dn = f.dn;
     // Batch-1 decode: the O-proj rides in the attention launch as per-head partial rows, which
     // gate|up adds to its input and down to its residual (h + attn . Wo^T, llama3.py:211,253),
     // so a step runs one launch per layer fewer (device loop 0.104 -> 0.101 ms/step; at B = 8
@@ -1367,7 +1341,7 @@ static int run_layer(l3_ctx* c, int li, int B, int L, int start_pos, const int* 
     a.q = q; a.cache_k = Ly.cache_k + cache0; a.cache_v = Ly.cache_v + cache0; a.out = attn;
     a.B = B; a.L = L; a.start_pos = start_pos; a.H = c->d.n_heads; a.KVH = c->d.n_kv_heads;
     a.HD = c->HD; a.Smax = c->d.max_seq_len; a.pos_dev = pos_dev;
-    if (fuse_o) { a.wo = Ly.wo; a.parts = c->oparts; a.D = D; }
+    if (fuse_o) { a.wo = Ly.o.w; a.parts = c->oparts; a.D = D; }
     if (timed_on(c, L3_K_ATTN, s, [&] { return launch_attention(a, s); })) return 1;
     if (fuse_o) {
         gu.parts = c->oparts;
@@ -1377,11 +1351,7 @@ static int run_layer(l3_ctx* c, int li, int B, int L, int start_pos, const int* 
         if (emb_ids) { gu.A = c->emb; gu.a_rows = emb_ids; }  // layer 0: h is the embedding row
     } else {
         // O-proj + residual (in place on h)
-        GemmArgs o{};
-        o.A = attn; o.lda = c->qdim; o.W = Ly.wo; o.W3 = Ly.wo3; o.Wb = Ly.wob; o.Wq = Ly.woq; o.wq_scale = Ly.wos; o.C = h; o.ldc = D;
-        o.M = (int)T; o.N = D; o.K = c->qdim; o.norm = false;
-        o.ws = skws; o.ws_cap = c->skws_cap;
-        if (emb_ids) { o.res_src = c->emb; o.res_rows = emb_ids; }  // h = emb[ids] + attn . Wo^T
+        const GemmArgs o = oproj_args(c, Ly, (int)T, attn, c->qdim, h, D, X6, skws, false, emb_ids);
         if (timed_on(c, L3_K_OPROJ, s, [&] { return gemm(c, EPI_RESID, o, s); })) return 1;
     }
     return ffn_pair(c, gu, dn, s);
@@ -1391,11 +1361,10 @@ static int run_layer(l3_ctx* c, int li, int B, int L, int start_pos, const int* 
 static GemmArgs lm_head_args(l3_ctx* c, int B, int L, float* logits_dev, int b0) {
     const int64_t D = c->d.dim, VS = c->d.vocab_size;
     GemmArgs lm{};
-    lm.A = c->h + ((int64_t)b0 * L + L - 1) * D; lm.lda = (int64_t)L * D; lm.W = c->lm_head;
+    lm.A = c->h + ((int64_t)b0 * L + L - 1) * D; lm.lda = (int64_t)L * D;
     lm.C = logits_dev + (int64_t)b0 * VS; lm.ldc = VS;
     lm.M = B; lm.N = (int)VS; lm.K = (int)D; lm.norm = true;  // final norm folded
-    lm.Wb = c->lm_headb; lm.Wq = c->lm_headq; lm.wq_scale = c->lm_heads;
-    lm.norm_w = c->lm_headb || c->lm_headq ? c->final_norm : nullptr;
+    bind_weight(lm, c->lm_head, NO_X6);
     lm.eps = c->d.norm_eps;
     return lm;
 }
@@ -1488,7 +1457,7 @@ static int forward_dev(l3_ctx* c, const int32_t* ids_dev, int B, int L, int star
     // the call that makes it forks after it even behind a gather (that one call gives up the overlap)
     bool tab_new = false;
     if (ids_dev && c->embed_qkv && !pos_dev && (int64_t)(B / parts) * L > 256 && !c->layers.empty() &&
-        !c->layers[0].wqkv3 && !c->embed_tab)
+        !c->layers[0].qkv.x6 && !c->embed_tab)
         tab_new = embed_table(c, true);
     const bool fork_early = after_gather && !tab_new;
     if (parts > 1) {  // the aux streams join the work queued so far on stream
@@ -1685,8 +1654,8 @@ static int persist_setup(l3_ctx* c) {
     a = persist_shape(c);
     const int nl = (int)c->layers.size();
     a.eps = c->d.norm_eps;
-    a.q_scale = (float)(1.4426950408889634 / std::sqrt((double)c->HD));
-    a.emb = c->emb; a.lm_head = c->lm_head; a.rope_cos = c->rope_cos; a.rope_sin = c->rope_sin;
+    a.q_scale = qkv_q_scale(c->HD);
+    a.emb = c->emb; a.lm_head = c->lm_head.w; a.rope_cos = c->rope_cos; a.rope_sin = c->rope_sin;
     a.bak_layer = (int64_t)KV_BAK_SLOTS * 2 * 8 * c->d.n_kv_heads * c->HD;
     const int64_t slab = decode_persist_slab(a.H, a.KVH, a.HD, a.D, a.FD);
     const size_t ptr_bytes = (size_t)6 * nl * sizeof(void*);
@@ -1699,8 +1668,8 @@ static int persist_setup(l3_ctx* c) {
     std::vector<const void*> ptrs((size_t)6 * nl);
     for (int i = 0; i < nl; ++i) {
         const Layer& L = c->layers[(size_t)i];
-        ptrs[(size_t)i] = L.wqkv; ptrs[(size_t)nl + i] = L.wo; ptrs[(size_t)2 * nl + i] = L.wgu;
-        ptrs[(size_t)3 * nl + i] = L.wd; ptrs[(size_t)4 * nl + i] = L.cache_k; ptrs[(size_t)5 * nl + i] = L.cache_v;
+        ptrs[(size_t)i] = L.qkv.w; ptrs[(size_t)nl + i] = L.o.w; ptrs[(size_t)2 * nl + i] = L.gu.w;
+        ptrs[(size_t)3 * nl + i] = L.dn.w; ptrs[(size_t)4 * nl + i] = L.cache_k; ptrs[(size_t)5 * nl + i] = L.cache_v;
     }
     HIP_TRY(hipMemcpy(c->persist_mem, ptrs.data(), ptr_bytes, hipMemcpyHostToDevice));
     char* base = static_cast<char*>(c->persist_mem);
@@ -2549,18 +2518,13 @@ extern "C" int l3_ragged_forward_host(l3_ctx* c, const int64_t* ids_host, const 
 // chose once for the whole call, ragged_split_pick, and the workspace is there); its two launches
 // are one timed L3_K_ATTN entry, so ms per entry compares with the single-pass kernel's.
 static int ragged_step(l3_ctx* c, int B, int s_cap, int chunk) {
-    const int D = c->d.dim, FD = c->d.hidden_dim;
-    const int32_t* cur = rag_word(c, RAG_CUR);
+    const int D = c->d.dim;
     hipStream_t s = c->stream;
     for (size_t li = 0; li < c->layers.size(); ++li) {
         Layer& Ly = c->layers[li];
-        GemmArgs g{};  // rmsnorm -> QKV, raw
-        g.eps = c->d.norm_eps;
-        g.A = c->h; g.lda = D; g.W = Ly.wqkv; g.C = c->rag_qkv; g.ldc = c->qkvn;
-        g.M = B; g.N = c->qkvn; g.K = D; g.norm = true;
-        g.Wb = Ly.wqkvb; g.Wq = Ly.wqkvq; g.wq_scale = Ly.wqkvs; g.norm_w = Ly.wqkvb || Ly.wqkvq ? Ly.n_attn : nullptr;
-        g.ws = c->skws; g.ws_cap = c->skws_cap;
-        if (li == 0) { g.A = c->emb; g.a_rows = cur; }
+        const int32_t* cur = li == 0 ? rag_word(c, RAG_CUR) : nullptr;  // layer 0: the rows are emb[cur_id]
+        // rmsnorm -> QKV, raw
+        const GemmArgs g = qkv_args(c, Ly, B, c->h, D, c->rag_qkv, NO_X6, c->skws, false, cur);
         if (timed(c, L3_K_QKV, [&] { return gemm(c, EPI_STORE, g, s); })) return 1;
         RaggedAttnArgs a{};
         a.qkv = c->rag_qkv; a.cache_k = Ly.cache_k; a.cache_v = Ly.cache_v; a.kv_dtype = c->kv_dtype; a.out = c->attn;
@@ -2568,28 +2532,18 @@ static int ragged_step(l3_ctx* c, int B, int s_cap, int chunk) {
         a.pos = rag_word(c, RAG_POS); a.finished = rag_word(c, RAG_FIN);
         a.B = B; a.H = c->d.n_heads; a.KVH = c->d.n_kv_heads; a.HD = c->HD; a.Smax = c->d.max_seq_len;
         a.s_cap = s_cap;
-        a.q_scale = (float)(1.4426950408889634 / std::sqrt((double)c->HD));
+        a.q_scale = qkv_q_scale(c->HD);
         a.chunk = chunk; a.ws = c->rag_split_ws;
         if (chunk) c->rag_split_launches += 1;
         if (timed(c, L3_K_ATTN, [&] {
                 return chunk ? launch_attn_decode_ragged_split(a, s) : launch_attn_decode_ragged(a, s);
             }))
             return 1;
-        GemmArgs o{};  // O-proj + residual (layer 0: h = emb[cur_id] + attn . Wo^T)
-        o.A = c->attn; o.lda = c->qdim; o.W = Ly.wo; o.Wb = Ly.wob; o.Wq = Ly.woq; o.wq_scale = Ly.wos; o.C = c->h; o.ldc = D;
-        o.M = B; o.N = D; o.K = c->qdim; o.norm = false;
-        o.ws = c->skws; o.ws_cap = c->skws_cap;
-        if (li == 0) { o.res_src = c->emb; o.res_rows = cur; }
+        // O-proj + residual (layer 0: h = emb[cur_id] + attn . Wo^T), then the FFN
+        const GemmArgs o = oproj_args(c, Ly, B, c->attn, c->qdim, c->h, D, NO_X6, c->skws, false, cur);
         if (timed(c, L3_K_OPROJ, [&] { return gemm(c, EPI_RESID, o, s); })) return 1;
-        GemmArgs gu{};  // rmsnorm -> gate|up -> SwiGLU
-        gu.A = c->h; gu.lda = D; gu.W = Ly.wgu; gu.C = c->hid; gu.ldc = FD;
-        gu.M = B; gu.N = 2 * FD; gu.K = D; gu.norm = true; gu.eps = c->d.norm_eps;
-        gu.Wb = Ly.wgub; gu.Wq = Ly.wguq; gu.wq_scale = Ly.wgus; gu.norm_w = Ly.wgub || Ly.wguq ? Ly.n_ffn : nullptr;
-        GemmArgs dn{};  // down + residual
-        dn.A = c->hid; dn.lda = FD; dn.W = Ly.wd; dn.Wb = Ly.wdb; dn.Wq = Ly.wdq; dn.wq_scale = Ly.wds; dn.C = c->h; dn.ldc = D;
-        dn.M = B; dn.N = D; dn.K = FD; dn.norm = false;
-        gu.ws = dn.ws = c->skws; gu.ws_cap = dn.ws_cap = c->skws_cap;
-        if (ffn_pair(c, gu, dn, s)) return 1;
+        const FfnPair f = ffn_args(c, Ly, B, c->h, D, c->hid, NO_X6, c->skws, false);
+        if (ffn_pair(c, f.gu, f.dn, s)) return 1;
     }
     const GemmArgs lm = lm_head_args(c, B, 1, c->logits, 0);
     return timed(c, L3_K_LMHEAD, [&] { return gemm(c, EPI_STORE, lm, s); });
@@ -2696,43 +2650,26 @@ static int ragged_extend_run(l3_ctx* c, const int64_t* ids_host, const int32_t* 
 // of every chunk row in c->h [B * Lmax, D].  skinny (the speculative iterations' short chunks): the
 // four projections on the skinny MFMA kernel whatever their M
 static int ragged_extend_layers(l3_ctx* c, int B, int Lmax, bool skinny) {
-    const int D = c->d.dim, FD = c->d.hidden_dim, T = B * Lmax;
+    const int D = c->d.dim, T = B * Lmax;
     hipStream_t s = c->stream;
     for (size_t li = 0; li < c->layers.size(); ++li) {
         Layer& Ly = c->layers[li];
-        GemmArgs g{};  // rmsnorm -> QKV, raw
-        g.eps = c->d.norm_eps;
-        g.A = c->h; g.lda = D; g.W = Ly.wqkv; g.C = c->rag_ext_qkv; g.ldc = c->qkvn;
-        g.M = T; g.N = c->qkvn; g.K = D; g.norm = true;
-        g.Wb = Ly.wqkvb; g.Wq = Ly.wqkvq; g.wq_scale = Ly.wqkvs; g.norm_w = Ly.wqkvb || Ly.wqkvq ? Ly.n_attn : nullptr;
-        g.ws = c->skws; g.ws_cap = c->skws_cap;
-        if (li == 0) { g.A = c->emb; g.a_rows = c->ids; }
-        g.force_skinny = skinny;
+        const int32_t* ids = li == 0 ? c->ids : nullptr;  // layer 0: the rows are emb[ids]
+        // rmsnorm -> QKV, raw: on the fp32 kernels (no x6), as the decode step's
+        const GemmArgs g = qkv_args(c, Ly, T, c->h, D, c->rag_ext_qkv, NO_X6, c->skws, skinny, ids);
         if (timed(c, L3_K_QKV, [&] { return gemm(c, EPI_STORE, g, s); })) return 1;
         ExtendAttnArgs a{};
         a.qkv = c->rag_ext_qkv; a.cache_k = Ly.cache_k; a.cache_v = Ly.cache_v; a.kv_dtype = c->kv_dtype; a.out = c->attn;
         a.rope_cos = c->rope_cos; a.rope_sin = c->rope_sin;
         a.starts = rag_word(c, RAG_EXT_START); a.lens = rag_word(c, RAG_EXT_LEN);
         a.B = B; a.Lq = Lmax; a.H = c->d.n_heads; a.KVH = c->d.n_kv_heads; a.HD = c->HD; a.Smax = c->d.max_seq_len;
-        a.q_scale = (float)(1.4426950408889634 / std::sqrt((double)c->HD));
+        a.q_scale = qkv_q_scale(c->HD);
         if (timed(c, L3_K_ATTN, [&] { return launch_attn_extend_ragged(a, s); })) return 1;
-        GemmArgs o{};  // O-proj + residual (layer 0: h = emb[ids] + attn . Wo^T)
-        o.A = c->attn; o.lda = c->qdim; o.W = Ly.wo; o.W3 = Ly.wo3; o.Wb = Ly.wob; o.Wq = Ly.woq; o.wq_scale = Ly.wos; o.C = c->h; o.ldc = D;
-        o.M = T; o.N = D; o.K = c->qdim; o.norm = false;
-        o.ws = c->skws; o.ws_cap = c->skws_cap;
-        if (li == 0) { o.res_src = c->emb; o.res_rows = c->ids; }
-        o.force_skinny = skinny;
+        // O-proj + residual (layer 0: h = emb[ids] + attn . Wo^T), then the FFN: these may take x6
+        const GemmArgs o = oproj_args(c, Ly, T, c->attn, c->qdim, c->h, D, X6, c->skws, skinny, ids);
         if (timed(c, L3_K_OPROJ, [&] { return gemm(c, EPI_RESID, o, s); })) return 1;
-        GemmArgs gu{};  // rmsnorm -> gate|up -> SwiGLU
-        gu.A = c->h; gu.lda = D; gu.W = Ly.wgu; gu.W3 = Ly.wgu3; gu.C = c->hid; gu.ldc = FD;
-        gu.M = T; gu.N = 2 * FD; gu.K = D; gu.norm = true; gu.eps = c->d.norm_eps;
-        gu.Wb = Ly.wgub; gu.Wq = Ly.wguq; gu.wq_scale = Ly.wgus; gu.norm_w = Ly.wgub || Ly.wguq ? Ly.n_ffn : nullptr;
-        GemmArgs dn{};  // down + residual
-        dn.A = c->hid; dn.lda = FD; dn.W = Ly.wd; dn.W3 = Ly.wd3; dn.Wb = Ly.wdb; dn.Wq = Ly.wdq; dn.wq_scale = Ly.wds; dn.C = c->h; dn.ldc = D;
-        dn.M = T; dn.N = D; dn.K = FD; dn.norm = false;
-        gu.ws = dn.ws = c->skws; gu.ws_cap = dn.ws_cap = c->skws_cap;
-        gu.force_skinny = dn.force_skinny = skinny;
-        if (ffn_pair(c, gu, dn, s)) return 1;
+        const FfnPair f = ffn_args(c, Ly, T, c->h, D, c->hid, X6, c->skws, skinny);
+        if (ffn_pair(c, f.gu, f.dn, s)) return 1;
     }
     return 0;
 }
@@ -3153,24 +3090,21 @@ extern "C" int l3_attention_forward_host(l3_ctx* c, int32_t layer, const float* 
     const int64_t T = (int64_t)B * L;
     const int D = c->d.dim;
     HIP_TRY(hipMemcpyAsync(c->h, x_host, T * D * 4, hipMemcpyHostToDevice, c->stream));
-    GemmArgs g{};
-    g.A = c->h; g.lda = D; g.W = Ly.wqkv; g.M = (int)T; g.N = c->qkvn; g.K = D; g.norm = false;
-    g.Wb = Ly.wqkvb; g.Wq = Ly.wqkvq; g.wq_scale = Ly.wqkvs;  // (no attention norm in this context: norm_w stays null)
+    GemmArgs g = qkv_args(c, Ly, (int)T, c->h, D, nullptr, NO_X6, nullptr, false, nullptr);
+    g.norm = false; g.norm_w = nullptr;  // x is already normalised: no attention norm in this context
     g.q_out = c->q; g.cache_k = Ly.cache_k; g.cache_v = Ly.cache_v;
     g.rope_cos = c->rope_cos; g.rope_sin = c->rope_sin;
     g.L = L; g.start_pos = start_pos; g.H = c->d.n_heads; g.KVH = c->d.n_kv_heads; g.HD = c->HD;
     g.Smax = c->d.max_seq_len;
-    g.q_scale = (float)(1.4426950408889634 / std::sqrt((double)c->HD));
+    g.q_scale = qkv_q_scale(c->HD);
     if (timed(c, L3_K_QKV, [&] { return gemm(c, EPI_QKV, g, c->stream); })) return 1;
     AttnArgs a{};
     a.q = c->q; a.cache_k = Ly.cache_k; a.cache_v = Ly.cache_v; a.out = c->attn;
     a.B = B; a.L = L; a.start_pos = start_pos; a.H = c->d.n_heads; a.KVH = c->d.n_kv_heads;
     a.HD = c->HD; a.Smax = c->d.max_seq_len;
     if (timed(c, L3_K_ATTN, [&] { return launch_attention(a, c->stream); })) return 1;
-    GemmArgs o{};
-    o.A = c->attn; o.lda = c->qdim; o.W = Ly.wo; o.Wb = Ly.wob; o.Wq = Ly.woq; o.wq_scale = Ly.wos; o.C = c->h; o.ldc = D;
-    o.M = (int)T; o.N = D; o.K = c->qdim; o.norm = false;
-    if (timed(c, L3_K_OPROJ, [&] { return gemm(c, EPI_STORE, o, c->stream); })) return 1;
+    const GemmArgs o = oproj_args(c, Ly, (int)T, c->attn, c->qdim, c->h, D, NO_X6, nullptr, false, nullptr);
+    if (timed(c, L3_K_OPROJ, [&] { return gemm(c, EPI_STORE, o, c->stream); })) return 1;  // no residual
     HIP_TRY(hipMemcpyAsync(out_host, c->h, T * D * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
@@ -3396,7 +3330,7 @@ extern "C" int l3_op_attn_decode_ragged_kv_host(l3_ctx* c, const float* qkv, voi
     a.qkv = dq; a.cache_k = dk; a.cache_v = dv; a.kv_dtype = kv_dtype; a.out = dout; a.rope_cos = dc; a.rope_sin = ds;
     a.pos = reinterpret_cast<const int32_t*>(dp); a.finished = reinterpret_cast<const int32_t*>(df);
     a.B = B; a.H = H; a.KVH = KVH; a.HD = HD; a.Smax = Smax; a.s_cap = s_cap;
-    a.q_scale = (float)(1.4426950408889634 / std::sqrt((double)HD));
+    a.q_scale = qkv_q_scale(HD);
     a.chunk = split; a.ws = dws;
     if (split) c->rag_split_launches += 1;
     if (timed(c, L3_K_ATTN, [&] {
@@ -3459,7 +3393,7 @@ extern "C" int l3_op_attn_extend_ragged_kv_host(l3_ctx* c, const float* qkv, voi
     a.qkv = dq; a.cache_k = dk; a.cache_v = dv; a.kv_dtype = kv_dtype; a.out = dout; a.rope_cos = dc; a.rope_sin = ds;
     a.starts = reinterpret_cast<const int32_t*>(dst); a.lens = reinterpret_cast<const int32_t*>(dl);
     a.B = B; a.Lq = Lq; a.H = H; a.KVH = KVH; a.HD = HD; a.Smax = Smax;
-    a.q_scale = (float)(1.4426950408889634 / std::sqrt((double)HD));
+    a.q_scale = qkv_q_scale(HD);
     if (timed(c, L3_K_ATTN, [&] { return launch_attn_extend_ragged(a, c->stream); })) return 1;
     D2H(out, dout, no);
     HIP_TRY(hipMemcpyAsync(cache_k, dk, cb, hipMemcpyDeviceToHost, c->stream));
@@ -3608,77 +3542,6 @@ extern "C" int l3_op_to_bf16_host(l3_ctx* c, const float* x, int64_t n, uint16_t
     return 0;
 }
 
-extern "C" int l3_op_linear_bf16_host(l3_ctx* c, const float* x, int64_t rows, int32_t K, int32_t N,
-                                      const uint16_t* w_u16, const float* norm_w, float eps, float* y) {
-    CHECK_CTX(c);
-    if (!x || !w_u16 || !y) return fail("l3_op_linear_bf16: null argument");
-    if (rows < 1 || rows > 8) return fail("l3_op_linear_bf16: rows = %lld outside [1, 8] (the GEMV's range)", (long long)rows);
-    if (K <= 0 || K % 32) return fail("l3_op_linear_bf16: K=%d must be a positive multiple of 32", K);
-    if (N <= 0 || N % 4) return fail("l3_op_linear_bf16: N=%d must be a positive multiple of 4", N);
-    // rows per launch: the GEMV stages its rows in 64 KB of LDS (gemm_is_gemv), so a long K takes
-    // the rows in smaller blocks — always on the GEMV, never another kernel
-    int per = 8;
-    while (per > 1 && (int64_t)per * K > 16384) per /= 2;
-    if (set_dev(c)) return 1;
-    Scratch S{c};
-    SCRATCH(dx, rows * K);
-    SCRATCH(dw, ((int64_t)N * K + 1) / 2);
-    SCRATCH(dg, K);
-    SCRATCH(dy, rows * N);
-    H2D(dx, x, rows * K);
-    HIP_TRY(hipMemcpyAsync(dw, w_u16, (size_t)N * K * 2, hipMemcpyHostToDevice, c->stream));
-    if (norm_w) H2D(dg, norm_w, K);
-    for (int64_t r0 = 0; r0 < rows; r0 += per) {
-        GemmArgs g{};
-        g.A = dx + r0 * K; g.lda = K; g.W = nullptr; g.Wb = reinterpret_cast<const unsigned short*>(dw);
-        g.norm_w = norm_w ? dg : nullptr; g.norm = norm_w != nullptr; g.eps = eps;
-        g.C = dy + r0 * N; g.ldc = N;
-        g.M = (int)(rows - r0 < per ? rows - r0 : per); g.N = N; g.K = K;
-        if (!gemm_takes_bf16(EPI_STORE, g))
-            return fail("l3_op_linear_bf16: %d x %d x %d is not a shape of the weight-streaming GEMV", g.M, K, N);
-        c->wb_launches += 1;  // always the GEMV, whatever l3_set_weight_bf16_rows says
-        HIP_TRY(launch_gemm(EPI_STORE, g, c->stream));
-    }
-    D2H(y, dy, rows * N);
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-// gemm_rows_bf16_kernel with EPI_STORE on plain arrays: y [rows, N] = x [rows, K] . float(w)^T, with
-// norm_w the RMSNorm of x first.  No other kernel stands in, and the context's own rows setting
-// plays no part: the launch carries max_rows 64 and min_bytes 0
-extern "C" int l3_op_linear_bf16_rows_host(l3_ctx* c, const float* x, int64_t rows, int32_t K, int32_t N,
-                                           const uint16_t* w_u16, const float* norm_w, float eps, float* y) {
-    CHECK_CTX(c);
-    if (!x || !w_u16 || !y) return fail("l3_op_linear_bf16_rows: null argument");
-    if (rows < 2 || rows > WB_ROWS_MAX)
-        return fail("l3_op_linear_bf16_rows: rows = %lld outside [2, %d] (the kernel's range)", (long long)rows, WB_ROWS_MAX);
-    if (K <= 0 || K % 32) return fail("l3_op_linear_bf16_rows: K=%d must be a positive multiple of 32", K);
-    if (N <= 0 || N % 4) return fail("l3_op_linear_bf16_rows: N=%d must be a positive multiple of 4", N);
-    if (set_dev(c)) return 1;
-    Scratch S{c};
-    SCRATCH(dx, rows * K);
-    SCRATCH(dw, ((int64_t)N * K + 1) / 2);
-    SCRATCH(dg, K);
-    SCRATCH(dy, rows * N);
-    H2D(dx, x, rows * K);
-    HIP_TRY(hipMemcpyAsync(dw, w_u16, (size_t)N * K * 2, hipMemcpyHostToDevice, c->stream));
-    if (norm_w) H2D(dg, norm_w, K);
-    GemmArgs g{};
-    g.A = dx; g.lda = K; g.W = nullptr; g.Wb = reinterpret_cast<const unsigned short*>(dw);
-    g.norm_w = norm_w ? dg : nullptr; g.norm = norm_w != nullptr; g.eps = eps;
-    g.C = dy; g.ldc = N;
-    g.M = (int)rows; g.N = N; g.K = K;
-    g.wb_rows = WB_ROWS_MAX; g.wb_min_bytes = 0;
-    if (!gemm_takes_bf16_rows(EPI_STORE, g))
-        return fail("l3_op_linear_bf16_rows: %d x %d x %d is not a shape of the bf16 rows kernel", g.M, K, N);
-    c->wb_rows_launches += 1;
-    HIP_TRY(launch_gemm(EPI_STORE, g, c->stream));
-    D2H(y, dy, rows * N);
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
 // fp8 weight storage on plain arrays: the conversion kernel of l3_finalize, and the fp8 forms of
 // the GEMV and of the rows kernel with EPI_STORE
 extern "C" int l3_op_to_fp8_rows_host(l3_ctx* c, const float* x, int64_t rows, int32_t K, uint8_t* codes_out,
@@ -3732,84 +3595,89 @@ static void route_out(int32_t* route) {
     for (int i = 0; i < 5; ++i) route[1 + i] = r.v[i];
 }
 
-extern "C" int l3_op_linear_fp8_host(l3_ctx* c, const float* x, int64_t rows, int32_t K, int32_t N, const uint8_t* codes,
-                                     const float* scale, const float* norm_w, float eps, float* y, int32_t* route) {
+// The compact-weight linear with EPI_STORE on plain arrays, behind the four entries below:
+// y [rows, N] = x [rows, K] . W^T, W the bf16 array w, or (fp8) the codes w with one scale per row;
+// norm_w: the RMSNorm of x first.  rows_kernel false: the weight-streaming GEMV (gemv_kernel's WB
+// form), which stages its rows in 64 KB of LDS (gemm_is_gemv), so a long K takes the rows in
+// smaller blocks — always on the GEMV.  rows_kernel true: gemm_rows_bf16_kernel, one launch; the
+// context's own rows setting plays no part: the launch carries max_rows 64 and min_bytes 0.  A
+// shape the kernel does not take is an error, never another kernel.  fp8: the route is returned
+static int op_linear_compact(l3_ctx* c, const char* who, bool fp8, bool rows_kernel, const float* x, int64_t rows,
+                             int32_t K, int32_t N, const void* w, const float* scale, const float* norm_w, float eps,
+                             float* y, int32_t* route) {
     CHECK_CTX(c);
-    if (!x || !codes || !scale || !y) return fail("l3_op_linear_fp8: null argument");
-    if (rows < 1 || rows > 8) return fail("l3_op_linear_fp8: rows = %lld outside [1, 8] (the GEMV's range)", (long long)rows);
-    if (K <= 0 || K % 32) return fail("l3_op_linear_fp8: K=%d must be a positive multiple of 32", K);
-    if (N <= 0 || N % 4) return fail("l3_op_linear_fp8: N=%d must be a positive multiple of 4", N);
-    if (check_fp8_operands("l3_op_linear_fp8", codes, scale, N, K)) return 1;
-    // rows per launch as in l3_op_linear_bf16_host: always on the GEMV, never another kernel
-    int per = 8;
-    while (per > 1 && (int64_t)per * K > 16384) per /= 2;
+    if (!x || !w || (fp8 && !scale) || !y) return fail("%s: null argument", who);
+    if (rows_kernel && (rows < 2 || rows > WB_ROWS_MAX))
+        return fail("%s: rows = %lld outside [2, %d] (the kernel's range)", who, (long long)rows, WB_ROWS_MAX);
+    if (!rows_kernel && (rows < 1 || rows > 8))
+        return fail("%s: rows = %lld outside [1, 8] (the GEMV's range)", who, (long long)rows);
+    if (K <= 0 || K % 32) return fail("%s: K=%d must be a positive multiple of 32", who, K);
+    if (N <= 0 || N % 4) return fail("%s: N=%d must be a positive multiple of 4", who, N);
+    if (fp8 && check_fp8_operands(who, static_cast<const uint8_t*>(w), scale, N, K)) return 1;
+    int64_t per = rows_kernel ? rows : 8;  // rows per launch
+    while (!rows_kernel && per > 1 && per * K > 16384) per /= 2;
     if (set_dev(c)) return 1;
     Scratch S{c};
     SCRATCH(dx, rows * K);
-    SCRATCH(dw, (int64_t)N * K / 4);
-    SCRATCH(ds, N);
+    SCRATCH(dw, fp8 ? (int64_t)N * K / 4 : ((int64_t)N * K + 1) / 2);
+    float* ds = fp8 ? S.get(N) : nullptr;
+    if (fp8 && !ds) return fail("op scratch allocation failed");
     SCRATCH(dg, K);
     SCRATCH(dy, rows * N);
     H2D(dx, x, rows * K);
-    HIP_TRY(hipMemcpyAsync(dw, codes, (size_t)N * K, hipMemcpyHostToDevice, c->stream));
-    H2D(ds, scale, N);
+    HIP_TRY(hipMemcpyAsync(dw, w, (size_t)N * K * (fp8 ? 1 : 2), hipMemcpyHostToDevice, c->stream));
+    if (fp8) H2D(ds, scale, N);
     if (norm_w) H2D(dg, norm_w, K);
-    gemm_route_reset();
+    if (fp8) gemm_route_reset();
+    // the kernel the entry stands for: the test that a launch reaches it, and its counter
+    bool (*const takes)(int, const GemmArgs&) = fp8 ? (rows_kernel ? gemm_takes_fp8_rows : gemm_takes_fp8)
+                                                    : (rows_kernel ? gemm_takes_bf16_rows : gemm_takes_bf16);
+    int64_t& launches = fp8 ? (rows_kernel ? c->wq_rows_launches : c->wq_launches)
+                            : (rows_kernel ? c->wb_rows_launches : c->wb_launches);
+    Weight W{};  // the uploaded operand as a projection's record: a compact copy and no fp32 tensor
+    W.rows = N; W.K = K; W.norm = norm_w ? dg : nullptr;
+    if (fp8) { W.q = reinterpret_cast<unsigned char*>(dw); W.s = ds; }
+    else W.b = reinterpret_cast<unsigned short*>(dw);
     for (int64_t r0 = 0; r0 < rows; r0 += per) {
         GemmArgs g{};
-        g.A = dx + r0 * K; g.lda = K; g.W = nullptr; g.Wq = reinterpret_cast<const unsigned char*>(dw); g.wq_scale = ds;
-        g.norm_w = norm_w ? dg : nullptr; g.norm = norm_w != nullptr; g.eps = eps;
+        g.A = dx + r0 * K; g.lda = K; g.norm = norm_w != nullptr; g.eps = eps;
+        bind_weight(g, W, NO_X6);
         g.C = dy + r0 * N; g.ldc = N;
         g.M = (int)(rows - r0 < per ? rows - r0 : per); g.N = N; g.K = K;
-        if (!gemm_takes_fp8(EPI_STORE, g))
-            return fail("l3_op_linear_fp8: %d x %d x %d is not a shape of the weight-streaming GEMV", g.M, K, N);
-        c->wq_launches += 1;  // always the GEMV, whatever l3_set_weight_bf16_rows says
+        if (rows_kernel) { g.wb_rows = WB_ROWS_MAX; g.wb_min_bytes = 0; }
+        if (!takes(EPI_STORE, g) && rows_kernel)
+            return fail("%s: %d x %d x %d is not a shape of the %s rows kernel", who, g.M, K, N, fp8 ? "fp8" : "bf16");
+        if (!takes(EPI_STORE, g))
+            return fail("%s: %d x %d x %d is not a shape of the weight-streaming GEMV", who, g.M, K, N);
+        launches += 1;  // (the GEMV forms: always the GEMV, whatever l3_set_weight_bf16_rows says)
         HIP_TRY(launch_gemm(EPI_STORE, g, c->stream));
     }
-    route_out(route);
+    if (fp8) route_out(route);
     D2H(y, dy, rows * N);
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }
 
-// the rows kernel's fp8 form with EPI_STORE, one launch; the context's own rows setting plays no
-// part: the launch carries max_rows 64 and min_bytes 0
+extern "C" int l3_op_linear_bf16_host(l3_ctx* c, const float* x, int64_t rows, int32_t K, int32_t N,
+                                      const uint16_t* w_u16, const float* norm_w, float eps, float* y) {
+    return op_linear_compact(c, "l3_op_linear_bf16", false, false, x, rows, K, N, w_u16, nullptr, norm_w, eps, y, nullptr);
+}
+
+extern "C" int l3_op_linear_bf16_rows_host(l3_ctx* c, const float* x, int64_t rows, int32_t K, int32_t N,
+                                           const uint16_t* w_u16, const float* norm_w, float eps, float* y) {
+    return op_linear_compact(c, "l3_op_linear_bf16_rows", false, true, x, rows, K, N, w_u16, nullptr, norm_w, eps, y,
+                             nullptr);
+}
+
+extern "C" int l3_op_linear_fp8_host(l3_ctx* c, const float* x, int64_t rows, int32_t K, int32_t N, const uint8_t* codes,
+                                     const float* scale, const float* norm_w, float eps, float* y, int32_t* route) {
+    return op_linear_compact(c, "l3_op_linear_fp8", true, false, x, rows, K, N, codes, scale, norm_w, eps, y, route);
+}
+
 extern "C" int l3_op_linear_fp8_rows_host(l3_ctx* c, const float* x, int64_t rows, int32_t K, int32_t N,
                                           const uint8_t* codes, const float* scale, const float* norm_w, float eps,
                                           float* y, int32_t* route) {
-    CHECK_CTX(c);
-    if (!x || !codes || !scale || !y) return fail("l3_op_linear_fp8_rows: null argument");
-    if (rows < 2 || rows > WB_ROWS_MAX)
-        return fail("l3_op_linear_fp8_rows: rows = %lld outside [2, %d] (the kernel's range)", (long long)rows, WB_ROWS_MAX);
-    if (K <= 0 || K % 32) return fail("l3_op_linear_fp8_rows: K=%d must be a positive multiple of 32", K);
-    if (N <= 0 || N % 4) return fail("l3_op_linear_fp8_rows: N=%d must be a positive multiple of 4", N);
-    if (check_fp8_operands("l3_op_linear_fp8_rows", codes, scale, N, K)) return 1;
-    if (set_dev(c)) return 1;
-    Scratch S{c};
-    SCRATCH(dx, rows * K);
-    SCRATCH(dw, (int64_t)N * K / 4);
-    SCRATCH(ds, N);
-    SCRATCH(dg, K);
-    SCRATCH(dy, rows * N);
-    H2D(dx, x, rows * K);
-    HIP_TRY(hipMemcpyAsync(dw, codes, (size_t)N * K, hipMemcpyHostToDevice, c->stream));
-    H2D(ds, scale, N);
-    if (norm_w) H2D(dg, norm_w, K);
-    GemmArgs g{};
-    g.A = dx; g.lda = K; g.W = nullptr; g.Wq = reinterpret_cast<const unsigned char*>(dw); g.wq_scale = ds;
-    g.norm_w = norm_w ? dg : nullptr; g.norm = norm_w != nullptr; g.eps = eps;
-    g.C = dy; g.ldc = N;
-    g.M = (int)rows; g.N = N; g.K = K;
-    g.wb_rows = WB_ROWS_MAX; g.wb_min_bytes = 0;
-    if (!gemm_takes_fp8_rows(EPI_STORE, g))
-        return fail("l3_op_linear_fp8_rows: %d x %d x %d is not a shape of the fp8 rows kernel", g.M, K, N);
-    c->wq_rows_launches += 1;
-    gemm_route_reset();
-    HIP_TRY(launch_gemm(EPI_STORE, g, c->stream));
-    route_out(route);
-    D2H(y, dy, rows * N);
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
+    return op_linear_compact(c, "l3_op_linear_fp8_rows", true, true, x, rows, K, N, codes, scale, norm_w, eps, y, route);
 }
 
 extern "C" int l3_op_ffn_host(l3_ctx* c, const float* x, int64_t rows, int32_t dim, int32_t hidden,
@@ -4094,7 +3962,7 @@ static int op_gemm_impl(l3_ctx* c, const char* who, l3_gemm_op* op, l3_decode_ge
     g.force_skinny = op->force_skinny != 0;
     g.force_tiled = op->force_tiled;
     if (bf16) {
-        // finalize_bf16's round mode: Wb = bf16(w), W = float(Wb); the norm weight stays beside Wb
+        // finalize_compact's bf16 round mode: Wb = bf16(w), W = float(Wb); the norm weight stays beside Wb
         // and is folded into the fp32 copy, which then holds the same model for the fp32 routes
         SCRATCH(dwb, ((int64_t)N * K + 1) / 2);
         SCRATCH(dcnt, 4);
@@ -4643,7 +4511,7 @@ extern "C" int l3_score_host(l3_ctx* c, const int64_t* ids_host, const int64_t* 
     const int nl = (int)c->layers.size();
     for (int li = 0; li < nl; ++li)
         if (run_layer(c, li, B, L, start_pos, nullptr, li == 0 ? c->ids : nullptr)) return 1;
-    if (score_lm(c, c->h, c->d.dim, T, c->d.dim, c->d.vocab_size, c->lm_head, true, tgt, tl, lp, nullptr, am))
+    if (score_lm(c, c->h, c->d.dim, T, c->d.dim, c->d.vocab_size, c->lm_head.w, true, tgt, tl, lp, nullptr, am))
         return 1;
     HIP_TRY(hipMemcpyAsync(logprobs_host, lp, (size_t)T * 4, hipMemcpyDeviceToHost, c->stream));
     if (am) HIP_TRY(hipMemcpyAsync(argmax_host, am, (size_t)T * 4, hipMemcpyDeviceToHost, c->stream));
