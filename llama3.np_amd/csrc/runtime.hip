@@ -1,5 +1,6 @@
 // libllama3hip runtime: device context, weight residency, forward orchestration, RCCL.
-// Implements include/llama3hip.h.  Reference anchors are given per entry point.
+// Implements include/llama3hip.h but for the op-level entry points, which are in ops.hip (what the
+// two units share: runtime.h).  Reference anchors are given per entry point.
 //
 // Device layout (one context per GPU, everything resident in HBM for the context's life):
 //   emb        [VS, D]                       model.embed_tokens.weight
@@ -16,32 +17,13 @@
 //   rope cos/sin [M, HD/2] fp32 (computed in double exactly as llama3.py:31-38, then rounded)
 //   workspace  h [T, D] residual stream, q [T, H*HD], attn [T, H*HD], hidden [T, FD],
 //              logits [B, VS], ids [T], argmax [B]   (grown on demand, T = B*L)
-#include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
-#include <rocprofiler-sdk-roctx/roctx.h>
-
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstddef>
-#include <cstdlib>
-#include <cstring>
-#include <mutex>
-#include <string>
-#include <chrono>
-#include <deque>
-#include <vector>
-
-#include "../../include/llama3hip.h"
-#include "kernels.h"
-
-using namespace l3;
+#include "runtime.h"
 
 static_assert(offsetof(DecState, pos) == 0, "captured kernels read &DecState::pos as pos_dev");
 
 static thread_local std::string g_err;
 
-static int fail(const char* fmt, ...) {
+int l3rt::fail(const char* fmt, ...) {
     char buf[512];
     va_list ap;
     va_start(ap, fmt);
@@ -51,302 +33,16 @@ static int fail(const char* fmt, ...) {
     return 1;
 }
 
-#define HIP_TRY(expr)                                                                    \
-    do {                                                                                 \
-        hipError_t e_ = (expr);                                                          \
-        if (e_ != hipSuccess)                                                            \
-            return fail("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, \
-                        __LINE__);                                                       \
-    } while (0)
-
 #define NCCL_TRY(expr)                                                                         \
     do {                                                                                       \
         ncclResult_t r_ = (expr);                                                              \
         if (r_ != ncclSuccess) return fail("%s failed: %s", #expr, ncclGetErrorString(r_));    \
     } while (0)
 
-#define CHECK_CTX(ctx) \
-    if (!(ctx)) return fail("null context")
-
-// One projection as the context holds it: the fp32 tensor, which every kernel can read, and the
-// opt-in copies made from it.  bind_weight puts a record into a launch's GemmArgs; each_weight
-// walks every record of a context (teardown, the x6 pieces, the conversion at l3_finalize).
-struct Weight {
-    float* w = nullptr;  // [rows, K] fp32 (the layout comment at the top of the file)
-    int64_t rows = 0;
-    int K = 0;
-    // the opt-in x6 GEMM path (gemm_x6.h, l3_set_gemm_x6): three bf16 pieces [rows][3][K], made
-    // from the folded fp32 weight (null when the path is off; the lm_head has none)
-    unsigned short* x6 = nullptr;
-    // opt-in bf16 weight storage (l3_set_weight_bf16): bf16 in the fp32 tensor's row layout and
-    // without the norm fold, made by l3_finalize (null when the mode is off); read by the
-    // bf16-weight GEMV and rows kernel, with `norm` applied to the activations (GemmArgs::norm_w)
-    unsigned short* b = nullptr;
-    // opt-in fp8 weight storage (l3_set_weight_fp8): e4m3fn codes in the same layout, unfolded,
-    // with one power-of-two scale per row (null when the mode is off; never beside the bf16
-    // copy); read by the fp8 forms of the same two kernels (GemmArgs::Wq, wq_scale)
-    unsigned char* q = nullptr;
-    float* s = nullptr;
-    // the RMSNorm weight [K] the consuming GEMM applies to its activations when it reads a
-    // compact copy (the fp32 tensor carries it folded): n_attn for qkv, n_ffn for gate|up,
-    // final_norm for the lm_head, null for o and down.  Not owned
-    const float* norm = nullptr;
-};
-
-struct Layer {
-    Weight qkv, o, gu, dn;
-    float* n_attn = nullptr;
-    float* n_ffn = nullptr;
-    // [maxB, KVH, Smax, HD] of the context's kv_dtype.  In a bf16 context (l3_create_kv) the
-    // allocations hold unsigned short and are half the size: only the ragged paths, which pass
-    // kv_dtype to their kernels, may touch them; every fp32-cache entry point refuses first (kv_f32_only)
-    float* cache_k = nullptr;
-    float* cache_v = nullptr;
-    unsigned have = 0;  // bitmask of uploaded kinds
-    // RMSNorm weight folded into the consuming GEMM's W columns at l3_finalize
-    bool folded_qkv = false, folded_gu = false;
-};
-
-struct Timer {
-    hipEvent_t a, b;
-    int kind;
-};
-
-struct l3_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    // batch split: a large prefill runs as two independent halves of the batch rows on stream
-    // and aux (llama3.py:163-211 never mixes rows), so each half's kernels fill the other's
-    // launch tails and boundaries; fork / join by events
-    static constexpr int MAX_PARTS = 4;
-    hipStream_t aux[MAX_PARTS - 1] = {};
-    hipEvent_t fork_ev = nullptr, join_ev[MAX_PARTS - 1] = {};
-    // host path: part p's last layers wait for part p - 1's same layer (forward_dev)
-    hipEvent_t lag_ev[MAX_PARTS - 1] = {};
-    int split = 2;                   // parts (1 = off); l3_set_batch_split, L3_BATCH_SPLIT
-    bool gemm_x6 = false;            // prefill GEMMs on the x6 path (l3_set_gemm_x6, L3_GEMM_X6)
-    // bf16 weight storage (l3_set_weight_bf16, L3_WEIGHT_BF16): 0 off, 1 exact, 2 round; taken at
-    // l3_finalize, which makes the bf16 copies (Weight::b of every projection) the decode GEMVs stream
-    int weight_bf16 = 0;
-    int64_t wb_bytes = 0;            // bytes of the bf16 copies
-    int64_t wb_launches = 0;         // GEMV launches issued on them (a captured step: at capture)
-    // 2 .. wb_rows rows on the bf16 copies (l3_set_weight_bf16_rows, L3_WEIGHT_BF16_ROWS /
-    // L3_WEIGHT_BF16_MIN_BYTES; gemm.hip gemm_takes_bf16_rows): the largest M (0: off) and the
-    // least bf16 bytes of a launch's weight that gemm_rows_bf16_kernel takes; its launches
-    static constexpr int WB_ROWS_DEFAULT = 32;  // measured: DESIGN.md "bf16 weight storage for 2-64 rows"
-    static constexpr int64_t WB_ROWS_MIN_BYTES_DEFAULT = (int64_t)32 << 20;
-    int wb_rows = WB_ROWS_DEFAULT;
-    int64_t wb_rows_min_bytes = WB_ROWS_MIN_BYTES_DEFAULT;
-    int64_t wb_rows_launches = 0;
-    // fp8 weight storage (l3_set_weight_fp8, L3_WEIGHT_FP8): 0 off, 1 exact, 2 round; taken at
-    // l3_finalize, which makes the code / scale copies (Weight::q / s of every projection);
-    // exclusive with weight_bf16.  The rows setting above governs whichever copy the context has
-    int weight_fp8 = 0;
-    int64_t wq_bytes = 0;            // bytes of the codes and the scales
-    int64_t wq_launches = 0;         // GEMV launches issued on them (a captured step: at capture)
-    int64_t wq_rows_launches = 0;    // launches of the rows kernel's fp8 form
-    // layer 0's QKV of a prefill as a lookup in a table of its pre-RoPE rows per token id
-    // (embed_qkv.h, l3_set_embed_qkv, L3_EMBED_QKV): built at the first call that qualifies, on
-    // stream, if its bytes fit embed_qkv_cap; a refused allocation is not retried
-    static constexpr int64_t EMBED_QKV_CAP_DEFAULT = (int64_t)256 << 20;
-    bool embed_qkv = true;
-    // gate|up + down of a block past 256 rows as one launch (ffn_fused.h, l3_set_ffn_fused,
-    // L3_FFN_FUSED): bit-identical to the two tiled launches
-    bool ffn_fused = true;
-    int64_t embed_qkv_cap = EMBED_QKV_CAP_DEFAULT;
-    float* embed_tab = nullptr;      // [vocab_size, qkvn]
-    bool embed_tab_failed = false;
-    bool prune_last = true;          // last layer: attention / O-proj / FFN on the last rows only
-                                     // (l3_set_last_layer_rows, L3_LAST_LAYER_ALL_ROWS)
-    int64_t split_min_tokens = 8192; // a part must hold at least this many tokens
-    l3_dims d{};
-    int kv_dtype = L3_KV_F32;        // KV-cache element (l3_create_kv), fixed for the context's life
-    int HD = 0, qdim = 0, kvdim = 0, qkvn = 0;
-    float* emb = nullptr;
-    Weight lm_head;
-    float* final_norm = nullptr;
-    float* rope_cos = nullptr;
-    float* rope_sin = nullptr;
-    std::vector<Layer> layers;
-    bool have_emb = false, have_lm = false, have_fnorm = false, finalized = false;
-    bool folded_lm = false;
-    // workspace
-    int64_t ws_T = 0, ws_B = 0;
-    float *h = nullptr, *q = nullptr, *attn = nullptr, *hid = nullptr, *logits = nullptr;
-    float* oparts = nullptr;         // [8, H, D] per-head O-proj rows of the fused decode attention
-    float* hsum = nullptr;           // [8, D] h + those rows (gate|up writes it for down's residual)
-    float* skws = nullptr;           // split-K workspace of the layer GEMMs on `stream` (models
-    int64_t skws_cap = 0;            //   with D or FD >= 2048; gemm.hip launch_split), floats
-    ArgmaxPart* amax_part = nullptr; // batch-1 lm_head's per-block argmax partials
-    int amax_n = 0;                  // partials the last lm_head wrote (0: none, use the logits)
-    // captured batched decode steps: the tiled lm_head writes per-row argmax partials [B][ceil(VS/64)]
-    // instead of the logits (GemmArgs::amax_rows), reduced by one B-row argmax launch
-    ArgmaxPart* amax_rows = nullptr;
-    int amax_rows_n = 0;             // partials per row the last lm_head wrote (0: none)
-    bool rows_amax = false;          // capture_steps: the lm_head may leave partials only
-    int32_t *ids = nullptr, *amax = nullptr;
-    int32_t* ids_pin = nullptr;      // pinned host staging of the int32 ids (upload_ids)
-    int64_t ids_pin_n = 0;
-    // op scratch
-    std::vector<void*> scratch;
-    // timing (bit k of timing_mask: record HIP events around launches of kernel id k)
-    bool timing = false;
-    unsigned timing_mask = 0;
-    std::vector<Timer> timers;
-    size_t timer_used = 0;
-    double tot_ms[L3_K_COUNT] = {0};
-    int64_t cnt[L3_K_COUNT] = {0};
-    // rccl
-    ncclComm_t comm = nullptr;
-    int nranks = 1, rank = 0;
-    bool comm_owned = true;          // false: the communicator belongs to an l3_group
-    l3_group* group = nullptr;       // the group this context is a member of (l3_group_create)
-    // logits gather form (l3_comm_set_overlap; env L3_COMM_MODE for A/B): 1 serialized on the
-    // context stream (default), 3 the next forward's second batch part overlapping the gather,
-    // 0 a comm stream ordered by events (measured slower)
-    int comm_mode = 1;
-    // comm stream of the A/B gather mode 0 (modes 1 and 3 gather on stream, see
-    // l3_comm_gather_logits); the next lm_head (the writer of the gathered rows) waits for the
-    // gather, every other entry point joins it first (set_dev)
-    hipStream_t comm_stream = nullptr;
-    int32_t* gather_ids = nullptr;   // [maxB] this rank's argmax ids (l3_comm_gather_argmax)
-    hipEvent_t comm_fwd_ev = nullptr, comm_done_ev = nullptr;
-    bool gather_pending = false;
-    // mode 3 (l3_comm_set_overlap): the gather was the last work queued on stream, and comm_fwd_ev marks
-    // the stream just before it — the next l3_forward_dev's second batch part starts from there,
-    // so its layers overlap the transfer (only that entry point keeps the flag: set_dev clears it)
-    bool gather_tail = false;
-    // captured greedy decode step (llama3.py:316-320 as one hipGraph replay per token)
-    int32_t* dec_ids = nullptr;      // [maxB] input ids of the next decode step (argmax output)
-    DecState* dec_state = nullptr;   // device loop state: position, generate history
-    int* dec_pos = nullptr;          // &dec_state->pos: start_pos of the next decode step
-    int32_t* dec_host = nullptr;     // pinned [maxB] for the per-token ids copy-back
-    hipGraph_t dec_graph = nullptr;
-    hipGraphExec_t dec_exec = nullptr;
-    int dec_B = 0;                   // batch the graph was captured for
-    // the device loop (generate_all) replays dec_n steps per graph launch: one captured graph of
-    // dec_n consecutive decode steps (the position and ids live on the device, so the steps
-    // chain inside the graph), which removes the gap between graph launches
-    hipGraph_t dec_graph_n = nullptr;
-    hipGraphExec_t dec_exec_n = nullptr;
-    int dec_n = 0, dec_n_B = 0;
-    int64_t dec_pos_mirror = -1;     // host copy of *dec_pos; -1 = device decode state invalid
-    std::vector<int64_t> dec_last;   // ids the device state holds (last returned)
-    int64_t graph_steps = 0;         // decode steps served by graph replay (stats)
-    // Run-ahead decode (lazy generate): when a step returns, up to SPEC_AHEAD further decode
-    // steps are already queued as replays of the captured step graphs (the ids chain on the
-    // device; each step's ids land in spec_hist by position), so the GPU keeps running while the
-    // host yields.  Every captured QKV append first keeps the slot it overwrites in kv_bak; a call
-    // that does not continue the schedule restores the slots of every step not yet handed out.
-    // The queue is bounded by steps (SPEC_AHEAD) and by time: at most SPEC_BUDGET_US of queued
-    // decode work, by the measured step time (step_us), so a caller that leaves the schedule
-    // (EOS, an abandoned generator) waits at most about that long for work nobody asked for —
-    // 16 steps at stories15M's 0.1 ms, none at the Llama-3-8B shape's 5 ms per step.
-    static constexpr int SPEC_AHEAD = 16;
-    static constexpr double SPEC_BUDGET_US = 4000.0;
-    double step_us = 0.0;            // decode step time (EMA): graph replays (host wall clock of a
-                                     // synced replay, HIP events around each queued run-ahead graph)
-    bool step_us_seed = false;       // step_us is still the eager first step's (an upper bound):
-                                     // the first replay's time replaces it
-    float* kv_bak = nullptr;         // [n_layers][KV_BAK_SLOTS][2: k, v][8][KVH][HD]
-    bool bak_capture = false;        // run_layer: QKV launches keep the overwritten slot
-    // capture_steps, batch-1 argmax fold: the lm_head moves the position on (fold_adv), and the
-    // layer-0 QKV of every step after a graph's first reduces the previous step's fold_n lm_head
-    // partials itself (fold_in) instead of a separate argmax launch
-    bool fold_in = false, fold_adv = false;
-    int fold_n = 0;
-    bool dec_bak = false;            // the captured single-step graph keeps it
-    bool dec_n_bak = false;          // ... and the multi-step graph
-    bool in_loop = false;            // generate_all drives the device state itself
-    int32_t* spec_hist = nullptr;    // device [max_seq_len][8]: each run-ahead step's ids
-    int32_t* spec_ids = nullptr;     // pinned mirror, copied chunk by chunk
-    bool spec_hist_armed = false;    // DecState.hist points at spec_hist
-    DecState* hist_host = nullptr;   // pinned staging of the DecState hist fields
-    int spec_base = 0, spec_end = 0; // queued steps cover positions [spec_base, spec_end)
-    int spec_B = 0;
-    int spec_limit = 0x7fffffff;     // l3_set_decode_horizon: no step at or past this position
-    // ev0 / ev1 bracket the chunk's graph launch (its device time keeps step_us current while
-    // steps are served from the queue; ev0 after any wait for another context's decode graphs),
-    // ev follows the ids copy (the chunk is ready)
-    struct SpecChunk { int pos0, n; hipEvent_t ev0, ev1, ev; bool done; };
-    std::deque<SpecChunk> spec_q;
-    std::vector<hipEvent_t> spec_free;  // event pool (timing events)
-    int64_t spec_hits = 0;
-    // persistent batch-1 decode step (decode_persist.hip): a captured step is one launch of
-    // decode_persist_kernel instead of 25 kernels (L3_DECODE_PERSIST; persist_setup)
-    void* persist_mem = nullptr;     // per-layer pointer arrays, epoch word, granule slabs
-    unsigned* persist_err = nullptr; // host-mapped error word (device writes it on a timeout)
-    unsigned* persist_err_dev = nullptr;
-    DecodePersistArgs persist{};
-    bool persist_ready = false;
-    bool persist_graph = false;      // the captured single-step graph runs the persistent step
-    // graph-only for the rest of the context's life: a persistent step gave up on a hand-off
-    // (persist_recover) or its launch was refused inside a capture (capture_steps)
-    bool persist_off = false;
-    // spec_resolve queued a guarded undo behind persistent steps without waiting for them: a
-    // give-up among them is noticed (and the context turned graph-only) by persist_settle, at the
-    // next decode entry point, before any further persistent step is launched
-    bool persist_unsettled = false;
-    int host_lag = 2;  // forward_dev: host-path lag of the later batch parts (layers; tools/host_path_probe.py)
-    int64_t persist_recoveries = 0;  // steps recovered on the graph path (stats)
-    hipEvent_t order_ev = nullptr;   // after this context's last decode graph (launch_decode_graph)
-    // sampling (l3_set_sampling; sample.hip): temperature 0 = greedy, every decode path as it was.
-    // While it is on, the step's argmax launch is the sample kernel, which needs whole logits rows:
-    // no persistent step, no argmax fold, no per-row argmax partials.
-    SampleParams samp{0.f, 0, 1.f, 0u, 0u};
-    SampleParams* samp_dev = nullptr;  // the kernel's copy (allocated by the first l3_set_sampling)
-    // teacher-forced scoring (l3_score_host, l3_op_linear_logprob_host): the lm_head's partials of
-    // one row chunk [chunk rows][ceil(N / 64)] live in score_ws (allocated on first use, bounded:
-    // l3_set_score_workspace), the per-row targets / target logits / results in score_rows
-    static constexpr int64_t SCORE_WS_DEFAULT = (int64_t)64 << 20;
-    int64_t score_ws_bytes = SCORE_WS_DEFAULT;  // the size asked for
-    void* score_ws = nullptr;
-    int64_t score_ws_have = 0;                  // bytes allocated (0: none yet)
-    int32_t* score_rows = nullptr;              // [5][score_rows_cap]: targets, target logit, logprob, lse, argmax
-    int64_t score_rows_cap = 0;
-    std::vector<int32_t> score_tgt_host;        // int32 staging of the int64 host targets
-    // ragged batches (l3_ragged_*; ragged.hip): per-row device state [RAG_WORDS][max_batch_size]
-    // int32 (pos, cur_id, finished, n_out, len, budget, lm_head rows, token, and a continuation's
-    // chunk starts and lengths) + the live word, the step's raw QKV rows and sampling uniforms, the
-    // output ids and the stop list (grown on demand)
-    static constexpr int RAG_WORDS = 10;
-    int32_t* rag_state = nullptr;
-    float* rag_qkv = nullptr;                   // [max_batch_size, qkvn]
-    float* rag_u = nullptr;                     // [max_batch_size]
-    int32_t* rag_out = nullptr;                 // [B, cap]
-    int64_t rag_out_n = 0;
-    int32_t* rag_stop = nullptr;
-    int64_t rag_stop_n = 0;
-    std::vector<int32_t> rag_host;              // host staging of rag_state (kept until the call's sync)
-    std::vector<int64_t> rag_ids_host;          // the padded ids with the pads replaced
-    // split-KV decode attention of the ragged step (l3_set_ragged_attn_split; DESIGN.md "Split-KV
-    // decode attention"): mode 0 auto (split only where the single-pass kernel's LDS does not
-    // fit), 1 always; the chunk asked for (the one in force: ragged_chunk); the chunk partials'
-    // workspace, allocated on first use and grown as needed
-    static constexpr int RAG_SPLIT_CHUNK_DEFAULT = 256;  // measured: DESIGN.md "Split-KV decode attention"
-    int rag_split_mode = 0;
-    int rag_split_chunk = RAG_SPLIT_CHUNK_DEFAULT;
-    float* rag_split_ws = nullptr;
-    int64_t rag_split_ws_n = 0;                 // floats
-    int64_t rag_split_launches = 0;             // split-kernel launches since l3_create (stats)
-    // ragged continuation (l3_ragged_extend_host; ragged_extend.hip): the chunk's raw QKV rows
-    // [B * Lmax, qkvn], allocated on first use and grown as needed
-    float* rag_ext_qkv = nullptr;
-    int64_t rag_ext_qkv_n = 0;                  // floats
-    // speculative decoding (l3_ragged_generate_spec_host, l3_ragged_verify_host; spec.hip): one
-    // workspace — the logits of every chunk row [rows, VS], their token choices and uniforms, and
-    // the loop's sequences S, lengths and counters — allocated on first use and grown as needed
-    char* draft_ws = nullptr;
-    int64_t draft_ws_n = 0;                     // bytes
-    std::vector<int32_t> draft_host;            // host staging of the sequences (kept until the call's sync)
-};
-
 static bool sampling_on(const l3_ctx* c) { return c->samp.temperature > 0.f; }
 
 // ---------------------------------------------------------------------------------------
-// join = the context stream waits for an in-flight logits gather: every entry point except
-// l3_forward_dev (which waits only before its lm_head) and the gather itself
-static int set_dev(l3_ctx* c, bool join = true) {
+int l3rt::set_dev(l3_ctx* c, bool join) {
     HIP_TRY(hipSetDevice(c->device));
     if (join) c->gather_tail = false;
     if (join && c->gather_pending) {
@@ -357,33 +53,6 @@ static int set_dev(l3_ctx* c, bool join = true) {
 }
 
 static int spec_resolve(l3_ctx* c);  // undo of a speculative decode step (below)
-
-template <typename F>
-static int timed_on(l3_ctx* c, int kind, hipStream_t s, F&& launch) {
-    Timer* t = nullptr;
-    // a fused FFN launch (L3_K_FFN) is timed when any of the gateup, down or ffn bits asks
-    const unsigned bits = kind == L3_K_FFN ? 1u << L3_K_FFN | 1u << L3_K_GATEUP | 1u << L3_K_DOWN : 1u << kind;
-    if (c->timing && (c->timing_mask & bits)) {
-        if (c->timer_used == c->timers.size()) {
-            Timer nt{};
-            HIP_TRY(hipEventCreate(&nt.a));
-            HIP_TRY(hipEventCreate(&nt.b));
-            c->timers.push_back(nt);
-        }
-        t = &c->timers[c->timer_used++];
-        t->kind = kind;
-        HIP_TRY(hipEventRecord(t->a, s));
-    }
-    hipError_t e = launch();
-    if (e != hipSuccess) return fail("kernel launch (kind %d) failed: %s", kind, hipGetErrorString(e));
-    if (t) HIP_TRY(hipEventRecord(t->b, s));
-    return 0;
-}
-
-template <typename F>
-static int timed(l3_ctx* c, int kind, F&& launch) {
-    return timed_on(c, kind, c->stream, launch);
-}
 
 static int harvest_timers(l3_ctx* c) {
     if (!c->timer_used) return 0;
@@ -406,10 +75,6 @@ static int harvest_timers(l3_ctx* c) {
     return 0;
 }
 
-static void dfree(void* p) {
-    if (p) (void)hipFree(p);
-}
-
 // Every projection of the context, in upload order: f(record, layer, which) for each layer's
 // qkv, o, gate|up and down, then the lm_head (layer -1; its record is empty in a layer-only context)
 enum { P_QKV, P_O, P_GU, P_DN, P_LM };
@@ -420,19 +85,6 @@ static void each_weight(l3_ctx* c, F&& f) {
         f(L.qkv, li, P_QKV); f(L.o, li, P_O); f(L.gu, li, P_GU); f(L.dn, li, P_DN);
     }
     f(c->lm_head, -1, P_LM);
-}
-
-// W, W3, Wb, Wq, wq_scale and norm_w of a launch from a projection's record, from weight row
-// row0 on (the caller sets N and K).  The x6 pieces only where the site says X6: which launches may
-// leave the fp32 kernels for the x6 path is each site's own rule.  Allocates nothing
-enum Pieces { NO_X6, X6 };
-static void bind_weight(GemmArgs& g, const Weight& W, Pieces x6, int64_t row0 = 0) {
-    g.W = W.w + row0 * W.K;
-    g.W3 = x6 == X6 && W.x6 ? W.x6 + row0 * 3 * W.K : nullptr;
-    g.Wb = W.b ? W.b + row0 * W.K : nullptr;
-    g.Wq = W.q ? W.q + row0 * W.K : nullptr;
-    g.wq_scale = W.s ? W.s + row0 : nullptr;
-    g.norm_w = W.b || W.q ? W.norm : nullptr;
 }
 
 static void drop_decode_graph(l3_ctx* c) {
@@ -685,7 +337,7 @@ extern "C" int l3_destroy(l3_ctx* c) {
     dfree(c->oparts); dfree(c->amax_part); dfree(c->hsum); dfree(c->skws); dfree(c->amax_rows);
     dfree(c->amax); dfree(c->gather_ids); dfree(c->embed_tab);
     if (c->ids_pin) (void)hipHostFree(c->ids_pin);
-    for (void* p : c->scratch) dfree(p);
+    dfree(c->barrier_buf);
     for (auto& t : c->timers) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
     drop_decode_graph(c);
     dfree(c->dec_ids); dfree(c->dec_state); dfree(c->kv_bak); dfree(c->samp_dev);
@@ -849,9 +501,6 @@ extern "C" int l3_set_gemm_x6(l3_ctx* c, int32_t on) {
     return 0;
 }
 
-// q is stored pre-scaled by log2(e) / sqrt(HD) (the attention's exp2 softmax)
-static float qkv_q_scale(int HD) { return (float)(1.4426950408889634 / std::sqrt((double)HD)); }
-
 // The layer-0 QKV table (embed_qkv.h): true when it exists.  may_build: make it now, on c->stream
 // (the caller's launches are ordered after c->stream: run_layer on it, forward_dev before its
 // fork event).  It is a function of the finalized weights alone, so it stays valid for the
@@ -943,7 +592,7 @@ extern "C" int l3_weight_bf16_info(l3_ctx* c, int32_t* mode, int64_t* bytes, int
 // launch_gemm, counting the launches served from the bf16 copies (the GEMV: l3_weight_bf16_info;
 // gemm_rows_bf16_kernel: l3_weight_bf16_rows_info); the context's rows setting travels in the
 // arguments, so two contexts of one process may differ
-static hipError_t gemm(l3_ctx* c, int epi, const GemmArgs& g_in, hipStream_t s) {
+hipError_t l3rt::gemm(l3_ctx* c, int epi, const GemmArgs& g_in, hipStream_t s) {
     if (!g_in.Wb && !g_in.Wq) return launch_gemm(epi, g_in, s);
     GemmArgs g = g_in;
     g.wb_rows = c->wb_rows;
@@ -2034,7 +1683,7 @@ static int spec_resolve(l3_ctx* c) {
 // ---------------------------------------------------------------------------------------
 // sampling (sample.hip).  The arguments are checked before anything else, so a bad value is
 // reported whatever the context.
-static int check_sampling(const char* who, float T, int32_t top_k, float top_p) {
+int l3rt::check_sampling(const char* who, float T, int32_t top_k, float top_p) {
     if (!(T >= 0.f) || std::isinf(T)) return fail("%s: temperature %g must be finite and >= 0", who, (double)T);
     if (top_k < 0) return fail("%s: top_k %d must be >= 0", who, top_k);
     if (!(top_p > 0.f && top_p <= 1.f)) return fail("%s: top_p %g must be in (0, 1]", who, (double)top_p);
@@ -2702,6 +2351,81 @@ extern "C" int l3_ragged_extend_host(l3_ctx* c, const int64_t* ids_host, const i
     return 0;
 }
 
+// The fork of a cache row (DESIGN.md "Ragged continuation"): slots [0, n_slots) of K and V in every
+// layer from row src_row to each row of dst_rows — one small copy kernel per layer on the
+// context's stream (ragged_extend.hip cache_copy_rows_kernel)
+extern "C" int l3_cache_copy_rows(l3_ctx* c, int32_t src_row, const int32_t* dst_rows, int32_t n_dst,
+                                  int32_t n_slots) {
+    CHECK_CTX(c);
+    const char* who = "l3_cache_copy_rows";
+    if (n_dst < 0 || (n_dst > 0 && !dst_rows)) return fail("%s: null argument", who);
+    if (need_model(c)) return 1;
+    if (c->group && group_members(c->group) > 1)
+        return fail("%s: this context is a member of a multi-device l3_group (not supported)", who);
+    const int mb = c->d.max_batch_size;
+    if (src_row < 0 || src_row >= mb) return fail("%s: src_row %d outside [0, %d)", who, src_row, mb);
+    if (n_dst > mb) return fail("%s: n_dst %d exceeds max_batch_size %d", who, n_dst, mb);
+    for (int i = 0; i < n_dst; ++i) {
+        if (dst_rows[i] < 0 || dst_rows[i] >= mb)
+            return fail("%s: dst_rows[%d] = %d outside [0, %d)", who, i, dst_rows[i], mb);
+        if (dst_rows[i] == src_row) return fail("%s: dst_rows[%d] is src_row %d", who, i, src_row);
+    }
+    if (n_slots < 0 || n_slots > c->d.max_seq_len)
+        return fail("%s: n_slots %d outside [0, %d]", who, n_slots, c->d.max_seq_len);
+    if (set_dev(c) || spec_resolve(c)) return 1;
+    if (n_dst == 0 || n_slots == 0) return 0;
+    if (ragged_bufs(c)) return 1;
+    int32_t* dst_dev = rag_word(c, RAG_TOK);  // free between calls: a step's token choice writes it
+    HIP_TRY(hipMemcpyAsync(dst_dev, dst_rows, (size_t)n_dst * 4, hipMemcpyHostToDevice, c->stream));
+    for (auto& Ly : c->layers)
+        HIP_TRY(launch_cache_copy_rows(Ly.cache_k, Ly.cache_v, c->kv_dtype, src_row, dst_dev, n_dst, c->d.n_kv_heads,
+                                       c->d.max_seq_len, c->HD, n_slots, mb, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // dst_rows is the caller's: read before the return
+    return 0;
+}
+
+extern "C" int l3_kv_info(l3_ctx* c, int32_t* dtype, int64_t* bytes) {
+    CHECK_CTX(c);
+    if (dtype) *dtype = c->kv_dtype;
+    if (bytes) *bytes = 2 * (int64_t)c->layers.size() * kv_cache_bytes(c);
+    return 0;
+}
+
+// Slots [slot0, slot0 + n_slots) of one cache row of one layer, every KV head, as fp32 on the host:
+// one strided copy per cache (a head's run of slots is contiguous), then a bf16 cache widened
+// exactly (bits << 16)
+extern "C" int l3_cache_read_host(l3_ctx* c, int32_t layer, int32_t row, int32_t slot0, int32_t n_slots, float* k_out,
+                                  float* v_out) {
+    CHECK_CTX(c);
+    const char* who = "l3_cache_read_host";
+    if (!k_out || !v_out) return fail("%s: null argument", who);
+    if (layer < 0 || layer >= (int)c->layers.size()) return fail("%s: layer %d outside [0, %d)", who, layer, (int)c->layers.size());
+    if (row < 0 || row >= c->d.max_batch_size) return fail("%s: row %d outside [0, %d)", who, row, c->d.max_batch_size);
+    if (slot0 < 0 || n_slots < 0 || (int64_t)slot0 + n_slots > c->d.max_seq_len)
+        return fail("%s: slots [%d, %lld) outside [0, %d]", who, slot0, (long long)slot0 + n_slots, c->d.max_seq_len);
+    if (set_dev(c) || spec_resolve(c)) return 1;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (n_slots == 0) return 0;
+    const int KVH = c->d.n_kv_heads, HD = c->HD, eb = kv_elem_bytes(c->kv_dtype);
+    const size_t run = (size_t)n_slots * HD * eb, pitch = (size_t)c->d.max_seq_len * HD * eb;
+    const size_t off = (((size_t)row * KVH) * c->d.max_seq_len + slot0) * HD * eb;
+    const Layer& Ly = c->layers[(size_t)layer];
+    const int64_t n = (int64_t)KVH * n_slots * HD;
+    float* outs[2] = {k_out, v_out};
+    const float* caches[2] = {Ly.cache_k, Ly.cache_v};
+    std::vector<uint16_t> bits(c->kv_dtype == L3_KV_BF16 ? (size_t)n : 0);
+    for (int i = 0; i < 2; ++i) {
+        const char* src = reinterpret_cast<const char*>(caches[i]) + off;
+        void* dst = bits.empty() ? (void*)outs[i] : (void*)bits.data();
+        HIP_TRY(hipMemcpy2D(dst, run, src, pitch, run, (size_t)KVH, hipMemcpyDeviceToHost));
+        for (int64_t j = 0; j < (int64_t)bits.size(); ++j) {
+            const uint32_t w = (uint32_t)bits[(size_t)j] << 16;
+            memcpy(outs[i] + j, &w, 4);
+        }
+    }
+    return 0;
+}
+
 // The generate loop of l3_ragged_generate_host (starts null: the prefill at position 0, its code
 // path as it always was) and of l3_ragged_generate_from_host (the extend, T_b = starts[b] + lens[b]
 // in the prompt length's place).  sp set: l3_ragged_generate_spec_host — the same prefill and first
@@ -2862,7 +2586,7 @@ extern "C" int l3_ragged_generate_from_host(l3_ctx* c, const int64_t* ids_host, 
 // lookup in the row's own sequence, runs the chunk [last token, draft...] as one ragged extend,
 // chooses a token from every chunk position's logits by the ordinary rule and keeps the draft's
 // longest prefix that equals those choices: the ids are l3_ragged_generate_host's.
-static int draft_range_check(const char* who, int draft_len, int ngram_max, int ngram_min) {
+int l3rt::draft_range_check(const char* who, int draft_len, int ngram_max, int ngram_min) {
     if (draft_len < 0 || draft_len > SPEC_MAX_DRAFT)
         return fail("%s: draft_len %d outside [0, %d]", who, draft_len, SPEC_MAX_DRAFT);
     if (ngram_min < 1 || ngram_min > ngram_max || ngram_max > SPEC_MAX_NGRAM)
@@ -3110,1087 +2834,6 @@ extern "C" int l3_attention_forward_host(l3_ctx* c, int32_t layer, const float* 
     return 0;
 }
 
-// ---------------------------------------------------------------------------------------
-// op-level entry points: H2D -> kernel -> D2H on per-call scratch (not a hot path)
-struct Scratch {
-    l3_ctx* c;
-    std::vector<void*> ptrs;
-    ~Scratch() {
-        for (void* p : ptrs) dfree(p);
-    }
-    float* get(int64_t n) {
-        void* p = nullptr;
-        if (hipMalloc(&p, (size_t)(n > 0 ? n : 1) * 4) != hipSuccess) return nullptr;
-        ptrs.push_back(p);
-        return (float*)p;
-    }
-};
-
-#define SCRATCH(var, n)                                   \
-    float* var = S.get(n);                                \
-    if (!var) return fail("op scratch allocation failed")
-
-#define H2D(dst, src, n) HIP_TRY(hipMemcpyAsync(dst, src, (size_t)(n) * 4, hipMemcpyHostToDevice, c->stream))
-#define D2H(dst, src, n) HIP_TRY(hipMemcpyAsync(dst, src, (size_t)(n) * 4, hipMemcpyDeviceToHost, c->stream))
-
-extern "C" int l3_op_softmax_host(l3_ctx* c, const float* x, int64_t rows, int64_t n, float* y) {
-    CHECK_CTX(c);
-    if (set_dev(c)) return 1;
-    Scratch S{c};
-    SCRATCH(dx, rows * n);
-    SCRATCH(dy, rows * n);
-    H2D(dx, x, rows * n);
-    HIP_TRY(launch_softmax(dx, dy, rows, (int)n, c->stream));
-    D2H(y, dy, rows * n);
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-extern "C" int l3_op_argmax_host(l3_ctx* c, const float* x, int64_t rows, int64_t n, int32_t* out) {
-    CHECK_CTX(c);
-    if (rows <= 0 || n <= 0 || n > INT32_MAX) return fail("argmax: bad shape %lld x %lld", (long long)rows, (long long)n);
-    if (set_dev(c)) return 1;
-    Scratch S{c};
-    SCRATCH(dx, rows * n);
-    SCRATCH(di, rows);
-    H2D(dx, x, rows * n);
-    HIP_TRY(launch_argmax(dx, rows, (int)n, reinterpret_cast<int32_t*>(di), c->stream));
-    D2H(out, di, rows);
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-// The drafting rule of the speculative loop on plain arrays (spec.hip spec_draft_kernel, op form)
-extern "C" int l3_op_spec_draft_host(l3_ctx* c, const int32_t* seq, const int32_t* seq_lens, const int32_t* k,
-                                     int32_t B, int32_t Smax, int32_t draft_len, int32_t ngram_max,
-                                     int32_t ngram_min, int32_t* out, int32_t* out_n) {
-    const char* who = "l3_op_spec_draft_host";
-    if (draft_range_check(who, draft_len, ngram_max, ngram_min)) return 1;
-    if (B <= 0 || B > 65535 || Smax <= 0) return fail("%s: bad shape B=%d Smax=%d", who, B, Smax);
-    if (!seq || !seq_lens || !k || !out_n || (draft_len > 0 && !out)) return fail("%s: null argument", who);
-    for (int b = 0; b < B; ++b) {
-        if (seq_lens[b] < 0 || seq_lens[b] > Smax)
-            return fail("%s: seq_lens[%d] = %d outside [0, %d]", who, b, seq_lens[b], Smax);
-        if (k[b] < 0 || k[b] > draft_len) return fail("%s: k[%d] = %d outside [0, %d]", who, b, k[b], draft_len);
-    }
-    CHECK_CTX(c);
-    if (draft_len == 0) {  // nothing to search for
-        for (int b = 0; b < B; ++b) out_n[b] = 0;
-        return 0;
-    }
-    if (set_dev(c)) return 1;
-    Scratch S{c};
-    SCRATCH(dseq, (int64_t)B * Smax);
-    SCRATCH(dlen, B);
-    SCRATCH(dk, B);
-    SCRATCH(dout, (int64_t)B * draft_len);
-    SCRATCH(dn, B);
-    H2D(dseq, seq, (int64_t)B * Smax);
-    H2D(dlen, seq_lens, B);
-    H2D(dk, k, B);
-    SpecDraftArgs a{};
-    a.seq = reinterpret_cast<int32_t*>(dseq); a.seq_stride = Smax; a.seq_len = reinterpret_cast<int32_t*>(dlen);
-    a.draft_len = draft_len; a.ngram_max = ngram_max; a.ngram_min = ngram_min;
-    a.k = reinterpret_cast<int32_t*>(dk);
-    a.out = reinterpret_cast<int32_t*>(dout); a.out_n = reinterpret_cast<int32_t*>(dn);
-    HIP_TRY(launch_spec_draft(a, B, c->stream));
-    D2H(out, dout, (int64_t)B * draft_len);
-    D2H(out_n, dn, B);
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-extern "C" int l3_op_sample_host(l3_ctx* c, const float* logits, int64_t rows, int64_t n, float temperature,
-                                 int32_t top_k, float top_p, const float* u, uint64_t seed, int32_t row0,
-                                 int32_t pos, int32_t* out) {
-    if (check_sampling("l3_op_sample_host", temperature, top_k, top_p)) return 1;
-    if (rows <= 0 || rows > INT32_MAX || n <= 0 || n > INT32_MAX)
-        return fail("l3_op_sample_host: bad shape %lld x %lld", (long long)rows, (long long)n);
-    if (!logits || !out) return fail("l3_op_sample_host: null argument");
-    for (int64_t r = 0; u && r < rows; ++r)
-        if (!(u[r] >= 0.f && u[r] < 1.f)) return fail("l3_op_sample_host: u[%lld] = %g outside [0, 1)", (long long)r, (double)u[r]);
-    CHECK_CTX(c);
-    if (set_dev(c)) return 1;
-    Scratch S{c};
-    SCRATCH(dx, rows * n);
-    SCRATCH(di, rows);
-    SCRATCH(du, rows);
-    SCRATCH(dp, (int64_t)(sizeof(SampleParams) + 3) / 4);
-    const SampleParams p{temperature, top_k, top_p, (uint32_t)seed, (uint32_t)(seed >> 32)};
-    H2D(dx, logits, rows * n);
-    if (u) H2D(du, u, rows);
-    HIP_TRY(hipMemcpyAsync(dp, &p, sizeof p, hipMemcpyHostToDevice, c->stream));
-    if (temperature > 0.f)
-        HIP_TRY(launch_sample(dx, rows, (int)n, reinterpret_cast<int32_t*>(di), reinterpret_cast<SampleParams*>(dp),
-                              u ? du : nullptr, row0, pos, c->stream));
-    else  // temperature 0 is greedy
-        HIP_TRY(launch_argmax(dx, rows, (int)n, reinterpret_cast<int32_t*>(di), c->stream));
-    D2H(out, di, rows);
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-extern "C" int l3_op_silu_host(l3_ctx* c, const float* x, int64_t n, float* y) {
-    CHECK_CTX(c);
-    if (set_dev(c)) return 1;
-    Scratch S{c};
-    SCRATCH(dx, n);
-    SCRATCH(dy, n);
-    H2D(dx, x, n);
-    HIP_TRY(launch_silu(dx, dy, n, c->stream));
-    D2H(y, dy, n);
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-extern "C" int l3_op_rmsnorm_host(l3_ctx* c, const float* x, const float* w, int64_t rows,
-                                  int64_t dim, float eps, float* y) {
-    CHECK_CTX(c);
-    if (set_dev(c)) return 1;
-    Scratch S{c};
-    SCRATCH(dx, rows * dim);
-    SCRATCH(dw, dim);
-    SCRATCH(dy, rows * dim);
-    H2D(dx, x, rows * dim);
-    H2D(dw, w, dim);
-    HIP_TRY(launch_rmsnorm(dx, dw, dy, rows, (int)dim, eps, c->stream));
-    D2H(y, dy, rows * dim);
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-extern "C" int l3_op_rope_host(l3_ctx* c, const float* x, int32_t B, int32_t L, int32_t nh,
-                               int32_t hd, const float* cos_t, const float* sin_t, float* y) {
-    CHECK_CTX(c);
-    if (set_dev(c)) return 1;
-    const int64_t n = (int64_t)B * L * nh * hd, nt = (int64_t)L * (hd / 2);
-    Scratch S{c};
-    SCRATCH(dx, n);
-    SCRATCH(dy, n);
-    SCRATCH(dc, nt);
-    SCRATCH(ds, nt);
-    H2D(dx, x, n);
-    H2D(dc, cos_t, nt);
-    H2D(ds, sin_t, nt);
-    HIP_TRY(launch_rope(dx, dy, dc, ds, B, L, nh, hd, c->stream));
-    D2H(y, dy, n);
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-// One ragged decode-attention launch on plain arrays (ragged.hip): split 0 the single-pass kernel,
-// else the split-KV form at that chunk length — the A/B between the two on identical inputs.
-// cache_k / cache_v [B, KVH, Smax, HD] are copied in and, with slot pos[b] appended, back out:
-// floats for L3_KV_F32, uint16 bf16 bit patterns for L3_KV_BF16.
-extern "C" int l3_op_attn_decode_ragged_kv_host(l3_ctx* c, const float* qkv, void* cache_k, void* cache_v,
-                                                int32_t kv_dtype, const float* rope_cos, const float* rope_sin,
-                                                const int32_t* pos, const int32_t* finished, int32_t B, int32_t H,
-                                                int32_t KVH, int32_t HD, int32_t Smax, int32_t s_cap, int32_t split,
-                                                float* out) {
-    CHECK_CTX(c);
-    const char* who = "l3_op_attn_decode_ragged";
-    if (!kv_dtype_ok(kv_dtype)) return fail("%s: kv_dtype %d (L3_KV_F32 = 0, L3_KV_BF16 = 1)", who, kv_dtype);
-    if (!qkv || !cache_k || !cache_v || !rope_cos || !rope_sin || !pos || !finished || !out)
-        return fail("%s: null argument", who);
-    if (B < 1 || B > 65535 || Smax < 1 || s_cap < 1 || s_cap > Smax)
-        return fail("%s: bad shape (B %d, Smax %d, s_cap %d: need 1 <= s_cap <= Smax)", who, B, Smax, s_cap);
-    if (!attn_decode_ragged_shape_ok(H, KVH, HD))
-        return fail("%s: the decode attention takes at most %d query heads per KV head and head sizes 16, 32, 48, "
-                    "64, 96, 128 (H %d, KVH %d, head size %d)", who, RAGGED_MAX_REP, H, KVH, HD);
-    if (split == 0 && !attn_decode_ragged_ok(H, KVH, HD, s_cap))
-        return fail("%s: the single-pass kernel needs s_cap %% 4 == 0 and %zu bytes of LDS at s_cap %d (budget %zu)",
-                    who, attn_decode_ragged_lds(H, KVH, HD, s_cap), s_cap, RAGGED_LDS_BYTES);
-    if (split != 0 && (split < RAGGED_CHUNK_MIN || split > RAGGED_CHUNK_MAX || split % 64 ||
-                       attn_decode_split_lds(H, KVH, HD, split) > RAGGED_LDS_BYTES))
-        return fail("%s: chunk %d (a multiple of 64 in [%d, %d] whose LDS fits %zu bytes)", who, split,
-                    RAGGED_CHUNK_MIN, RAGGED_CHUNK_MAX, RAGGED_LDS_BYTES);
-    if (set_dev(c)) return 1;
-    const int64_t nq = (int64_t)B * (H + 2 * KVH) * HD, nc = (int64_t)B * KVH * Smax * HD;
-    const int64_t nt = (int64_t)Smax * (HD / 2), no = (int64_t)B * H * HD;
-    const int n_split = split ? attn_decode_split_n(s_cap, split) : 0;
-    Scratch S{c};
-    SCRATCH(dq, nq);
-    const size_t cb = (size_t)nc * kv_elem_bytes(kv_dtype);  // bytes of a cache
-    SCRATCH(dk, (int64_t)((cb + 3) / 4));
-    SCRATCH(dv, (int64_t)((cb + 3) / 4));
-    SCRATCH(dc, nt);
-    SCRATCH(ds, nt);
-    SCRATCH(dp, B);
-    SCRATCH(df, B);
-    SCRATCH(dout, no);
-    SCRATCH(dws, attn_decode_split_ws_floats(B, H, HD, n_split));
-    H2D(dq, qkv, nq);
-    HIP_TRY(hipMemcpyAsync(dk, cache_k, cb, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(dv, cache_v, cb, hipMemcpyHostToDevice, c->stream));
-    H2D(dc, rope_cos, nt);
-    H2D(ds, rope_sin, nt);
-    H2D(dp, pos, B);
-    H2D(df, finished, B);
-    RaggedAttnArgs a{};
-    a.qkv = dq; a.cache_k = dk; a.cache_v = dv; a.kv_dtype = kv_dtype; a.out = dout; a.rope_cos = dc; a.rope_sin = ds;
-    a.pos = reinterpret_cast<const int32_t*>(dp); a.finished = reinterpret_cast<const int32_t*>(df);
-    a.B = B; a.H = H; a.KVH = KVH; a.HD = HD; a.Smax = Smax; a.s_cap = s_cap;
-    a.q_scale = qkv_q_scale(HD);
-    a.chunk = split; a.ws = dws;
-    if (split) c->rag_split_launches += 1;
-    if (timed(c, L3_K_ATTN, [&] {
-            return split ? launch_attn_decode_ragged_split(a, c->stream) : launch_attn_decode_ragged(a, c->stream);
-        }))
-        return 1;
-    D2H(out, dout, no);
-    HIP_TRY(hipMemcpyAsync(cache_k, dk, cb, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(cache_v, dv, cb, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-// The two launches of a ragged extend on plain arrays (ragged_extend.hip): the append of the new
-// keys / values, then the attention.  cache_k / cache_v [B, KVH, Smax, HD] are copied in and, with
-// slots [starts[b], starts[b] + lens[b]) written, back out; lens[b] may be 0 (an all-pad row).
-// Floats for L3_KV_F32, uint16 bf16 bit patterns for L3_KV_BF16.
-extern "C" int l3_op_attn_extend_ragged_kv_host(l3_ctx* c, const float* qkv, void* cache_k, void* cache_v,
-                                                int32_t kv_dtype, const float* rope_cos, const float* rope_sin,
-                                                const int32_t* starts, const int32_t* lens, int32_t B, int32_t Lq,
-                                                int32_t H, int32_t KVH, int32_t HD, int32_t Smax, float* out) {
-    CHECK_CTX(c);
-    const char* who = "l3_op_attn_extend_ragged";
-    if (!kv_dtype_ok(kv_dtype)) return fail("%s: kv_dtype %d (L3_KV_F32 = 0, L3_KV_BF16 = 1)", who, kv_dtype);
-    if (!qkv || !cache_k || !cache_v || !rope_cos || !rope_sin || !starts || !lens || !out)
-        return fail("%s: null argument", who);
-    if (B < 1 || B > 65535 || Lq < 1 || Smax < 1)
-        return fail("%s: bad shape (B %d, Lq %d, Smax %d)", who, B, Lq, Smax);
-    if (!attn_decode_ragged_shape_ok(H, KVH, HD))
-        return fail("%s: the ragged attention takes at most %d query heads per KV head and head sizes 16, 32, 48, "
-                    "64, 96, 128 (H %d, KVH %d, head size %d)", who, RAGGED_MAX_REP, H, KVH, HD);
-    for (int b = 0; b < B; ++b) {
-        if (lens[b] < 0 || lens[b] > Lq) return fail("%s: lens[%d] = %d outside [0, %d]", who, b, lens[b], Lq);
-        if (starts[b] < 0) return fail("%s: starts[%d] = %d is negative", who, b, starts[b]);
-        if ((int64_t)starts[b] + lens[b] > Smax || starts[b] >= Smax)
-            return fail("%s: row %d: positions [%d, %lld) exceed Smax %d", who, b, starts[b],
-                        (long long)starts[b] + lens[b], Smax);
-    }
-    if (set_dev(c)) return 1;
-    const int64_t nq = (int64_t)B * Lq * (H + 2 * KVH) * HD, nc = (int64_t)B * KVH * Smax * HD;
-    const int64_t nt = (int64_t)Smax * (HD / 2), no = (int64_t)B * Lq * H * HD;
-    Scratch S{c};
-    SCRATCH(dq, nq);
-    const size_t cb = (size_t)nc * kv_elem_bytes(kv_dtype);  // bytes of a cache
-    SCRATCH(dk, (int64_t)((cb + 3) / 4));
-    SCRATCH(dv, (int64_t)((cb + 3) / 4));
-    SCRATCH(dc, nt);
-    SCRATCH(ds, nt);
-    SCRATCH(dst, B);
-    SCRATCH(dl, B);
-    SCRATCH(dout, no);
-    H2D(dq, qkv, nq);
-    HIP_TRY(hipMemcpyAsync(dk, cache_k, cb, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(dv, cache_v, cb, hipMemcpyHostToDevice, c->stream));
-    H2D(dc, rope_cos, nt);
-    H2D(ds, rope_sin, nt);
-    H2D(dst, starts, B);
-    H2D(dl, lens, B);
-    ExtendAttnArgs a{};
-    a.qkv = dq; a.cache_k = dk; a.cache_v = dv; a.kv_dtype = kv_dtype; a.out = dout; a.rope_cos = dc; a.rope_sin = ds;
-    a.starts = reinterpret_cast<const int32_t*>(dst); a.lens = reinterpret_cast<const int32_t*>(dl);
-    a.B = B; a.Lq = Lq; a.H = H; a.KVH = KVH; a.HD = HD; a.Smax = Smax;
-    a.q_scale = qkv_q_scale(HD);
-    if (timed(c, L3_K_ATTN, [&] { return launch_attn_extend_ragged(a, c->stream); })) return 1;
-    D2H(out, dout, no);
-    HIP_TRY(hipMemcpyAsync(cache_k, dk, cb, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(cache_v, dv, cb, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-// the two ops above on fp32 caches
-extern "C" int l3_op_attn_decode_ragged_host(l3_ctx* c, const float* qkv, float* cache_k, float* cache_v,
-                                             const float* rope_cos, const float* rope_sin, const int32_t* pos,
-                                             const int32_t* finished, int32_t B, int32_t H, int32_t KVH, int32_t HD,
-                                             int32_t Smax, int32_t s_cap, int32_t split, float* out) {
-    return l3_op_attn_decode_ragged_kv_host(c, qkv, cache_k, cache_v, L3_KV_F32, rope_cos, rope_sin, pos, finished, B,
-                                            H, KVH, HD, Smax, s_cap, split, out);
-}
-
-extern "C" int l3_op_attn_extend_ragged_host(l3_ctx* c, const float* qkv, float* cache_k, float* cache_v,
-                                             const float* rope_cos, const float* rope_sin, const int32_t* starts,
-                                             const int32_t* lens, int32_t B, int32_t Lq, int32_t H, int32_t KVH,
-                                             int32_t HD, int32_t Smax, float* out) {
-    return l3_op_attn_extend_ragged_kv_host(c, qkv, cache_k, cache_v, L3_KV_F32, rope_cos, rope_sin, starts, lens, B,
-                                            Lq, H, KVH, HD, Smax, out);
-}
-
-// The fork of a cache row (DESIGN.md "Ragged continuation"): slots [0, n_slots) of K and V in every
-// layer from row src_row to each row of dst_rows — one small copy kernel per layer on the
-// context's stream (ragged_extend.hip cache_copy_rows_kernel)
-extern "C" int l3_cache_copy_rows(l3_ctx* c, int32_t src_row, const int32_t* dst_rows, int32_t n_dst,
-                                  int32_t n_slots) {
-    CHECK_CTX(c);
-    const char* who = "l3_cache_copy_rows";
-    if (n_dst < 0 || (n_dst > 0 && !dst_rows)) return fail("%s: null argument", who);
-    if (need_model(c)) return 1;
-    if (c->group && group_members(c->group) > 1)
-        return fail("%s: this context is a member of a multi-device l3_group (not supported)", who);
-    const int mb = c->d.max_batch_size;
-    if (src_row < 0 || src_row >= mb) return fail("%s: src_row %d outside [0, %d)", who, src_row, mb);
-    if (n_dst > mb) return fail("%s: n_dst %d exceeds max_batch_size %d", who, n_dst, mb);
-    for (int i = 0; i < n_dst; ++i) {
-        if (dst_rows[i] < 0 || dst_rows[i] >= mb)
-            return fail("%s: dst_rows[%d] = %d outside [0, %d)", who, i, dst_rows[i], mb);
-        if (dst_rows[i] == src_row) return fail("%s: dst_rows[%d] is src_row %d", who, i, src_row);
-    }
-    if (n_slots < 0 || n_slots > c->d.max_seq_len)
-        return fail("%s: n_slots %d outside [0, %d]", who, n_slots, c->d.max_seq_len);
-    if (set_dev(c) || spec_resolve(c)) return 1;
-    if (n_dst == 0 || n_slots == 0) return 0;
-    if (ragged_bufs(c)) return 1;
-    int32_t* dst_dev = rag_word(c, RAG_TOK);  // free between calls: a step's token choice writes it
-    HIP_TRY(hipMemcpyAsync(dst_dev, dst_rows, (size_t)n_dst * 4, hipMemcpyHostToDevice, c->stream));
-    for (auto& Ly : c->layers)
-        HIP_TRY(launch_cache_copy_rows(Ly.cache_k, Ly.cache_v, c->kv_dtype, src_row, dst_dev, n_dst, c->d.n_kv_heads,
-                                       c->d.max_seq_len, c->HD, n_slots, mb, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));  // dst_rows is the caller's: read before the return
-    return 0;
-}
-
-extern "C" int l3_kv_info(l3_ctx* c, int32_t* dtype, int64_t* bytes) {
-    CHECK_CTX(c);
-    if (dtype) *dtype = c->kv_dtype;
-    if (bytes) *bytes = 2 * (int64_t)c->layers.size() * kv_cache_bytes(c);
-    return 0;
-}
-
-// Slots [slot0, slot0 + n_slots) of one cache row of one layer, every KV head, as fp32 on the host:
-// one strided copy per cache (a head's run of slots is contiguous), then a bf16 cache widened
-// exactly (bits << 16)
-extern "C" int l3_cache_read_host(l3_ctx* c, int32_t layer, int32_t row, int32_t slot0, int32_t n_slots, float* k_out,
-                                  float* v_out) {
-    CHECK_CTX(c);
-    const char* who = "l3_cache_read_host";
-    if (!k_out || !v_out) return fail("%s: null argument", who);
-    if (layer < 0 || layer >= (int)c->layers.size()) return fail("%s: layer %d outside [0, %d)", who, layer, (int)c->layers.size());
-    if (row < 0 || row >= c->d.max_batch_size) return fail("%s: row %d outside [0, %d)", who, row, c->d.max_batch_size);
-    if (slot0 < 0 || n_slots < 0 || (int64_t)slot0 + n_slots > c->d.max_seq_len)
-        return fail("%s: slots [%d, %lld) outside [0, %d]", who, slot0, (long long)slot0 + n_slots, c->d.max_seq_len);
-    if (set_dev(c) || spec_resolve(c)) return 1;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (n_slots == 0) return 0;
-    const int KVH = c->d.n_kv_heads, HD = c->HD, eb = kv_elem_bytes(c->kv_dtype);
-    const size_t run = (size_t)n_slots * HD * eb, pitch = (size_t)c->d.max_seq_len * HD * eb;
-    const size_t off = (((size_t)row * KVH) * c->d.max_seq_len + slot0) * HD * eb;
-    const Layer& Ly = c->layers[(size_t)layer];
-    const int64_t n = (int64_t)KVH * n_slots * HD;
-    float* outs[2] = {k_out, v_out};
-    const float* caches[2] = {Ly.cache_k, Ly.cache_v};
-    std::vector<uint16_t> bits(c->kv_dtype == L3_KV_BF16 ? (size_t)n : 0);
-    for (int i = 0; i < 2; ++i) {
-        const char* src = reinterpret_cast<const char*>(caches[i]) + off;
-        void* dst = bits.empty() ? (void*)outs[i] : (void*)bits.data();
-        HIP_TRY(hipMemcpy2D(dst, run, src, pitch, run, (size_t)KVH, hipMemcpyDeviceToHost));
-        for (int64_t j = 0; j < (int64_t)bits.size(); ++j) {
-            const uint32_t w = (uint32_t)bits[(size_t)j] << 16;
-            memcpy(outs[i] + j, &w, 4);
-        }
-    }
-    return 0;
-}
-
-static int op_linear(l3_ctx* c, int epi, const float* dA, int64_t rows, int K, int N,
-                     const float* dW, float* dC, bool norm) {
-    GemmArgs g{};
-    g.A = dA; g.lda = K; g.W = dW; g.C = dC; g.ldc = (epi == EPI_SWIGLU) ? N / 2 : N;
-    g.M = (int)rows; g.N = N; g.K = K; g.norm = norm;
-    HIP_TRY(gemm(c, epi, g, c->stream));
-    return 0;
-}
-
-extern "C" int l3_op_linear_host(l3_ctx* c, const float* x, int64_t rows, int32_t K, int32_t N,
-                                 const float* w, float* y) {
-    CHECK_CTX(c);
-    if (K % 32) return fail("l3_op_linear: K=%d must be a multiple of 32", K);
-    if (set_dev(c)) return 1;
-    Scratch S{c};
-    SCRATCH(dx, rows * K);
-    SCRATCH(dw, (int64_t)N * K);
-    SCRATCH(dy, rows * N);
-    H2D(dx, x, rows * K);
-    H2D(dw, w, (int64_t)N * K);
-    if (op_linear(c, EPI_STORE, dx, rows, K, N, dw, dy, false)) return 1;
-    D2H(y, dy, rows * N);
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-// bf16 weight storage on plain arrays: the conversion kernel of l3_finalize, and the bf16-weight
-// GEMV (gemv_kernel's WB form) with EPI_STORE
-extern "C" int l3_op_to_bf16_host(l3_ctx* c, const float* x, int64_t n, uint16_t* out_u16, int64_t* n_inexact) {
-    CHECK_CTX(c);
-    if (n < 0 || (n > 0 && (!x || !out_u16))) return fail("l3_op_to_bf16: bad argument (n = %lld)", (long long)n);
-    if (set_dev(c)) return 1;
-    Scratch S{c};
-    SCRATCH(dx, n);
-    SCRATCH(db, (n + 1) / 2);
-    SCRATCH(dn, 4);
-    H2D(dx, x, n);
-    HIP_TRY(hipMemsetAsync(dn, 0, 16, c->stream));
-    HIP_TRY(launch_to_bf16(dx, reinterpret_cast<unsigned short*>(db), n, 0, false,
-                           reinterpret_cast<unsigned long long*>(dn), c->stream));
-    unsigned long long bad[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(bad, dn, 16, hipMemcpyDeviceToHost, c->stream));
-    if (n > 0) HIP_TRY(hipMemcpyAsync(out_u16, db, (size_t)n * 2, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (n_inexact) *n_inexact = (int64_t)bad[0];
-    return 0;
-}
-
-// fp8 weight storage on plain arrays: the conversion kernel of l3_finalize, and the fp8 forms of
-// the GEMV and of the rows kernel with EPI_STORE
-extern "C" int l3_op_to_fp8_rows_host(l3_ctx* c, const float* x, int64_t rows, int32_t K, uint8_t* codes_out,
-                                      float* scale_out, int64_t* n_inexact) {
-    CHECK_CTX(c);
-    if (rows < 0 || K <= 0 || K % 4 || (rows > 0 && (!x || !codes_out || !scale_out)))
-        return fail("l3_op_to_fp8_rows: bad argument (rows = %lld, K = %d: a positive multiple of 4)", (long long)rows, K);
-    if (set_dev(c)) return 1;
-    Scratch S{c};
-    SCRATCH(dx, rows * K);
-    SCRATCH(dq, rows * K / 4);
-    SCRATCH(ds, rows);
-    SCRATCH(dn, 8);
-    H2D(dx, x, rows * K);
-    HIP_TRY(hipMemsetAsync(dn, 0, 32, c->stream));
-    HIP_TRY(launch_to_fp8_rows(dx, reinterpret_cast<unsigned char*>(dq), ds, rows, K, 0, false,
-                               reinterpret_cast<unsigned long long*>(dn), c->stream));
-    unsigned long long cnt[4] = {0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(cnt, dn, 32, hipMemcpyDeviceToHost, c->stream));
-    if (rows > 0) {
-        HIP_TRY(hipMemcpyAsync(codes_out, dq, (size_t)rows * K, hipMemcpyDeviceToHost, c->stream));
-        D2H(scale_out, ds, rows);
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (cnt[2]) return fail("l3_op_to_fp8_rows: %llu elements are not finite", cnt[2]);
-    if (n_inexact) *n_inexact = (int64_t)cnt[0];
-    return 0;
-}
-
-// the operands of the two fp8 linear entries, checked on the host: no NaN code, scales that are
-// powers of two (normal fp32 values with a zero mantissa)
-static int check_fp8_operands(const char* who, const uint8_t* codes, const float* scale, int64_t N, int64_t K) {
-    for (int64_t i = 0; i < N * K; ++i)
-        if ((codes[i] & 0x7f) == 0x7f)
-            return fail("%s: code 0x%02x at row %lld, column %lld is a NaN of e4m3fn", who, codes[i], (long long)(i / K),
-                        (long long)(i % K));
-    for (int64_t n = 0; n < N; ++n) {
-        uint32_t u;
-        memcpy(&u, scale + n, 4);
-        const uint32_t ex = (u >> 23) & 0xff;
-        if ((u >> 31) || (u & 0x7fffff) || ex == 0 || ex == 255)
-            return fail("%s: scale[%lld] = %g is not a power of two", who, (long long)n, (double)scale[n]);
-    }
-    return 0;
-}
-
-static void route_out(int32_t* route) {
-    if (!route) return;
-    const GemmRoute r = gemm_last_route();
-    route[0] = r.family;
-    for (int i = 0; i < 5; ++i) route[1 + i] = r.v[i];
-}
-
-// The compact-weight linear with EPI_STORE on plain arrays, behind the four entries below:
-// y [rows, N] = x [rows, K] . W^T, W the bf16 array w, or (fp8) the codes w with one scale per row;
-// norm_w: the RMSNorm of x first.  rows_kernel false: the weight-streaming GEMV (gemv_kernel's WB
-// form), which stages its rows in 64 KB of LDS (gemm_is_gemv), so a long K takes the rows in
-// smaller blocks — always on the GEMV.  rows_kernel true: gemm_rows_bf16_kernel, one launch; the
-// context's own rows setting plays no part: the launch carries max_rows 64 and min_bytes 0.  A
-// shape the kernel does not take is an error, never another kernel.  fp8: the route is returned
-static int op_linear_compact(l3_ctx* c, const char* who, bool fp8, bool rows_kernel, const float* x, int64_t rows,
-                             int32_t K, int32_t N, const void* w, const float* scale, const float* norm_w, float eps,
-                             float* y, int32_t* route) {
-    CHECK_CTX(c);
-    if (!x || !w || (fp8 && !scale) || !y) return fail("%s: null argument", who);
-    if (rows_kernel && (rows < 2 || rows > WB_ROWS_MAX))
-        return fail("%s: rows = %lld outside [2, %d] (the kernel's range)", who, (long long)rows, WB_ROWS_MAX);
-    if (!rows_kernel && (rows < 1 || rows > 8))
-        return fail("%s: rows = %lld outside [1, 8] (the GEMV's range)", who, (long long)rows);
-    if (K <= 0 || K % 32) return fail("%s: K=%d must be a positive multiple of 32", who, K);
-    if (N <= 0 || N % 4) return fail("%s: N=%d must be a positive multiple of 4", who, N);
-    if (fp8 && check_fp8_operands(who, static_cast<const uint8_t*>(w), scale, N, K)) return 1;
-    int64_t per = rows_kernel ? rows : 8;  // rows per launch
-    while (!rows_kernel && per > 1 && per * K > 16384) per /= 2;
-    if (set_dev(c)) return 1;
-    Scratch S{c};
-    SCRATCH(dx, rows * K);
-    SCRATCH(dw, fp8 ? (int64_t)N * K / 4 : ((int64_t)N * K + 1) / 2);
-    float* ds = fp8 ? S.get(N) : nullptr;
-    if (fp8 && !ds) return fail("op scratch allocation failed");
-    SCRATCH(dg, K);
-    SCRATCH(dy, rows * N);
-    H2D(dx, x, rows * K);
-    HIP_TRY(hipMemcpyAsync(dw, w, (size_t)N * K * (fp8 ? 1 : 2), hipMemcpyHostToDevice, c->stream));
-    if (fp8) H2D(ds, scale, N);
-    if (norm_w) H2D(dg, norm_w, K);
-    if (fp8) gemm_route_reset();
-    // the kernel the entry stands for: the test that a launch reaches it, and its counter
-    bool (*const takes)(int, const GemmArgs&) = fp8 ? (rows_kernel ? gemm_takes_fp8_rows : gemm_takes_fp8)
-                                                    : (rows_kernel ? gemm_takes_bf16_rows : gemm_takes_bf16);
-    int64_t& launches = fp8 ? (rows_kernel ? c->wq_rows_launches : c->wq_launches)
-                            : (rows_kernel ? c->wb_rows_launches : c->wb_launches);
-    Weight W{};  // the uploaded operand as a projection's record: a compact copy and no fp32 tensor
-    W.rows = N; W.K = K; W.norm = norm_w ? dg : nullptr;
-    if (fp8) { W.q = reinterpret_cast<unsigned char*>(dw); W.s = ds; }
-    else W.b = reinterpret_cast<unsigned short*>(dw);
-    for (int64_t r0 = 0; r0 < rows; r0 += per) {
-        GemmArgs g{};
-        g.A = dx + r0 * K; g.lda = K; g.norm = norm_w != nullptr; g.eps = eps;
-        bind_weight(g, W, NO_X6);
-        g.C = dy + r0 * N; g.ldc = N;
-        g.M = (int)(rows - r0 < per ? rows - r0 : per); g.N = N; g.K = K;
-        if (rows_kernel) { g.wb_rows = WB_ROWS_MAX; g.wb_min_bytes = 0; }
-        if (!takes(EPI_STORE, g) && rows_kernel)
-            return fail("%s: %d x %d x %d is not a shape of the %s rows kernel", who, g.M, K, N, fp8 ? "fp8" : "bf16");
-        if (!takes(EPI_STORE, g))
-            return fail("%s: %d x %d x %d is not a shape of the weight-streaming GEMV", who, g.M, K, N);
-        launches += 1;  // (the GEMV forms: always the GEMV, whatever l3_set_weight_bf16_rows says)
-        HIP_TRY(launch_gemm(EPI_STORE, g, c->stream));
-    }
-    if (fp8) route_out(route);
-    D2H(y, dy, rows * N);
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-extern "C" int l3_op_linear_bf16_host(l3_ctx* c, const float* x, int64_t rows, int32_t K, int32_t N,
-                                      const uint16_t* w_u16, const float* norm_w, float eps, float* y) {
-    return op_linear_compact(c, "l3_op_linear_bf16", false, false, x, rows, K, N, w_u16, nullptr, norm_w, eps, y, nullptr);
-}
-
-extern "C" int l3_op_linear_bf16_rows_host(l3_ctx* c, const float* x, int64_t rows, int32_t K, int32_t N,
-                                           const uint16_t* w_u16, const float* norm_w, float eps, float* y) {
-    return op_linear_compact(c, "l3_op_linear_bf16_rows", false, true, x, rows, K, N, w_u16, nullptr, norm_w, eps, y,
-                             nullptr);
-}
-
-extern "C" int l3_op_linear_fp8_host(l3_ctx* c, const float* x, int64_t rows, int32_t K, int32_t N, const uint8_t* codes,
-                                     const float* scale, const float* norm_w, float eps, float* y, int32_t* route) {
-    return op_linear_compact(c, "l3_op_linear_fp8", true, false, x, rows, K, N, codes, scale, norm_w, eps, y, route);
-}
-
-extern "C" int l3_op_linear_fp8_rows_host(l3_ctx* c, const float* x, int64_t rows, int32_t K, int32_t N,
-                                          const uint8_t* codes, const float* scale, const float* norm_w, float eps,
-                                          float* y, int32_t* route) {
-    return op_linear_compact(c, "l3_op_linear_fp8_rows", true, true, x, rows, K, N, codes, scale, norm_w, eps, y, route);
-}
-
-extern "C" int l3_op_ffn_host(l3_ctx* c, const float* x, int64_t rows, int32_t dim, int32_t hidden,
-                              const float* w_gate, const float* w_up, const float* w_down, float* y) {
-    CHECK_CTX(c);
-    if (dim % 32 || hidden % 32) return fail("l3_op_ffn: dim and hidden must be multiples of 32");
-    if (set_dev(c)) return 1;
-    Scratch S{c};
-    SCRATCH(dx, rows * dim);
-    SCRATCH(dgu, 2LL * hidden * dim);
-    SCRATCH(dd, (int64_t)dim * hidden);
-    SCRATCH(dh, rows * hidden);
-    SCRATCH(dy, rows * dim);
-    H2D(dx, x, rows * dim);
-    HIP_TRY(hipMemcpy2DAsync(dgu, 32LL * dim * 4, w_gate, 16LL * dim * 4, 16LL * dim * 4, hidden / 16,
-                             hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpy2DAsync(dgu + 16LL * dim, 32LL * dim * 4, w_up, 16LL * dim * 4, 16LL * dim * 4,
-                             hidden / 16, hipMemcpyHostToDevice, c->stream));
-    H2D(dd, w_down, (int64_t)dim * hidden);
-    if (op_linear(c, EPI_SWIGLU, dx, rows, dim, 2 * hidden, dgu, dh, false)) return 1;
-    HIP_TRY(hipMemsetAsync(dy, 0, rows * dim * 4, c->stream));
-    if (op_linear(c, EPI_RESID, dh, rows, hidden, dim, dd, dy, false)) return 1;
-    D2H(y, dy, rows * dim);
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-// One FFN block on host arrays: y = x + down(SwiGLU(rowfactor(x) * x * Wgu^T)), rowfactor the
-// RMSNorm factor (norm) or 1.  fused: the fused kernel (ffn_fused.h), an error where it does not
-// take the shape — the pair never stands in; else the two tiled fp32 launches (more than 256 rows,
-// so launch_gemm reaches gemm_lds_kernel for both).  The pair needs whole 32-deep k-tiles of
-// hidden: a hidden of 16 mod 32 runs it with 16 zero hidden units appended (zero gate / up rows
-// and zero down columns), which add exact zeros at the end of every down sum.
-extern "C" int l3_op_ffn_block_host(l3_ctx* c, const float* x, int64_t rows, int32_t dim, int32_t hidden,
-                                    const float* w_gate, const float* w_up, const float* w_down, int32_t norm,
-                                    int32_t fused, float* y) {
-    CHECK_CTX(c);
-    const char* who = "l3_op_ffn_block";
-    if (!x || !w_gate || !w_up || !w_down || !y) return fail("%s: null argument", who);
-    if (rows <= 256 || rows > INT32_MAX / 4096) return fail("%s: %lld rows: the tiled kernels take more than 256", who, (long long)rows);
-    if (dim <= 0 || dim % 32 || hidden <= 0 || hidden % 16) return fail("%s: dim %d must be a multiple of 32 and hidden %d of 16", who, dim, hidden);
-    if (fused && !ffn_fused_takes(rows, dim, hidden))
-        return fail("%s: the fused kernel does not take %lld x %d x %d", who, (long long)rows, dim, hidden);
-    if (set_dev(c)) return 1;
-    const int32_t hp = fused ? hidden : (hidden + 31) / 32 * 32;  // the pair's hidden
-    Scratch S{c};
-    SCRATCH(dx, rows * dim);
-    SCRATCH(dgu, 2LL * hp * dim);
-    SCRATCH(dd, (int64_t)dim * hp);
-    SCRATCH(dh, rows * hp);
-    H2D(dx, x, rows * dim);
-    if (hp != hidden) {
-        HIP_TRY(hipMemsetAsync(dgu, 0, 2LL * hp * dim * 4, c->stream));
-        HIP_TRY(hipMemsetAsync(dd, 0, (int64_t)dim * hp * 4, c->stream));
-    }
-    HIP_TRY(hipMemcpy2DAsync(dgu, 32LL * dim * 4, w_gate, 16LL * dim * 4, 16LL * dim * 4, hidden / 16,
-                             hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpy2DAsync(dgu + 16LL * dim, 32LL * dim * 4, w_up, 16LL * dim * 4, 16LL * dim * 4,
-                             hidden / 16, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpy2DAsync(dd, (size_t)hp * 4, w_down, (size_t)hidden * 4, (size_t)hidden * 4, dim,
-                             hipMemcpyHostToDevice, c->stream));
-    if (fused) {
-        FfnArgs f{};
-        f.h = dx; f.wgu = dgu; f.wd = dd; f.M = (int)rows; f.D = dim; f.FD = hidden; f.norm = norm != 0;
-        f.eps = c->d.norm_eps;
-        HIP_TRY(launch_ffn_fused(f, c->stream));
-    } else {
-        GemmArgs gu{};
-        gu.A = dx; gu.lda = dim; gu.W = dgu; gu.C = dh; gu.ldc = hp;
-        gu.M = (int)rows; gu.N = 2 * hp; gu.K = dim; gu.norm = norm != 0; gu.eps = c->d.norm_eps;
-        GemmArgs dn{};
-        dn.A = dh; dn.lda = hp; dn.W = dd; dn.C = dx; dn.ldc = dim;
-        dn.M = (int)rows; dn.N = dim; dn.K = hp; dn.norm = false;
-        gemm_route_reset();
-        HIP_TRY(launch_gemm(EPI_SWIGLU, gu, c->stream));
-        if (gemm_last_route().family != ROUTE_TILED) return fail("%s: gate|up did not take the tiled kernel", who);
-        HIP_TRY(launch_gemm(EPI_RESID, dn, c->stream));
-        if (gemm_last_route().family != ROUTE_TILED) return fail("%s: down did not take the tiled kernel", who);
-    }
-    D2H(y, dx, rows * dim);
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-// One launch_gemm call on plain host arrays, any epilogue and any route the dispatcher reaches
-// without the captured-decode arguments (include/llama3hip.h l3_gemm_op).  The shapes are checked
-// against the buffers here, so no kernel is handed an index outside them; what the dispatcher
-// itself refuses comes back as an error, and no other kernel stands in.
-//
-// dec (l3_op_decode_gemm_host; null for l3_op_gemm_host): the captured-decode arguments on top —
-// the weight storage, the O-proj partial rows, the argmax partials in and out, the decode state,
-// the undo slots and the device position — staged the same way: every in / out array uploaded
-// whole, guard space included, and downloaded whole after the launch.
-static int state_io_check(const char* who, const l3_dec_state_io* st, int64_t rows) {
-    if (st->struct_size != (int32_t)sizeof(l3_dec_state_io))
-        return fail("%s: state struct_size %d, this library's l3_dec_state_io has %d bytes", who, st->struct_size,
-                    (int)sizeof(l3_dec_state_io));
-    if (st->hist_cap < 0 || (int64_t)st->hist_cap * rows > INT32_MAX) return fail("%s: hist_cap %d", who, st->hist_cap);
-    if ((st->hist || st->hist_val) && st->hist_len < (int64_t)st->hist_cap * rows + 1)
-        return fail("%s: hist_len %lld holds fewer than hist_cap * rows + 1 = %lld entries (one of guard space)", who,
-                    (long long)st->hist_len, (long long)st->hist_cap * rows + 1);
-    return 0;
-}
-
-// the DecState of a state description on the device (S owns the allocations)
-struct StateDev {
-    DecState* st = nullptr;
-    int32_t* hist = nullptr;
-    float* hist_val = nullptr;
-};
-static int state_io_upload(l3_ctx* c, Scratch& S, const l3_dec_state_io* io, StateDev* out) {
-    static_assert(sizeof(DecState) % 4 == 0, "DecState in whole floats");
-    SCRATCH(dst, sizeof(DecState) / 4);
-    DecState h{};
-    h.pos = io->pos; h.hist_base = io->hist_base; h.hist_cap = io->hist_cap; h.arrive = io->arrive;
-    if (io->hist) {
-        SCRATCH(dh, io->hist_len);
-        H2D(dh, io->hist, io->hist_len);
-        out->hist = h.hist = reinterpret_cast<int32_t*>(dh);
-    }
-    if (io->hist_val) {
-        SCRATCH(dhv, io->hist_len);
-        H2D(dhv, io->hist_val, io->hist_len);
-        out->hist_val = h.hist_val = dhv;
-    }
-    HIP_TRY(hipMemcpyAsync(dst, &h, sizeof h, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));  // h is a local
-    out->st = reinterpret_cast<DecState*>(dst);
-    return 0;
-}
-// ... and back: pos, arrive and both histories (the caller synchronises nothing else first)
-static int state_io_download(l3_ctx* c, const StateDev& d, l3_dec_state_io* io) {
-    DecState h{};
-    HIP_TRY(hipMemcpyAsync(&h, d.st, sizeof h, hipMemcpyDeviceToHost, c->stream));
-    if (d.hist) D2H(io->hist, d.hist, io->hist_len);
-    if (d.hist_val) D2H(io->hist_val, d.hist_val, io->hist_len);
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    io->pos = h.pos;
-    io->arrive = h.arrive;
-    return 0;
-}
-
-static int op_gemm_impl(l3_ctx* c, const char* who, l3_gemm_op* op, l3_decode_gemm_op* dec) {
-    for (int i = 0; i < 8; ++i) op->route[i] = 0;
-    const int epi = op->epi, M = op->M, N = op->N, K = op->K;
-    if (epi < EPI_STORE || epi > EPI_QKV) return fail("%s: epi %d outside [0, 3]", who, epi);
-    if (M < 1 || N < 1 || K < 1 || (int64_t)M * K > INT32_MAX || (int64_t)N * K > ((int64_t)1 << 32))
-        return fail("%s: bad shape %d x %d x %d", who, M, K, N);
-    if (!op->x || !op->w) return fail("%s: null operand", who);
-    const bool qkv = epi == EPI_QKV;
-    const bool fold = dec && dec->amax_in;
-    const bool bf16 = op->bf16 || (dec && dec->storage == 1), fp8 = dec && dec->storage == 2;
-    const int64_t x_rows = op->a_rows || fold ? op->x_rows : M;
-    if (x_rows < 1) return fail("%s: x_rows %lld", who, (long long)x_rows);
-    if (op->a_rows)
-        for (int r = 0; r < M; ++r)
-            if (op->a_rows[r] < 0 || op->a_rows[r] >= x_rows)
-                return fail("%s: a_rows[%d] = %d outside [0, %lld)", who, r, op->a_rows[r], (long long)x_rows);
-    const int64_t ldc = epi == EPI_SWIGLU ? N / 2 : N;
-    int64_t res_rows_n = 0;
-    if (!qkv) {
-        if (!op->c || op->c_rows < M + 1) return fail("%s: c must hold M + 1 = %d rows (one of guard space)", who, M + 1);
-        if ((op->res_src || op->res_rows) && epi != EPI_RESID) return fail("%s: res_src / res_rows go with EPI_RESID", who);
-        if (op->res_rows && !op->res_src) return fail("%s: res_rows without res_src", who);
-        if (op->res_src) {
-            res_rows_n = op->res_rows ? op->res_src_rows : M;
-            if (res_rows_n < 1 || (!op->res_rows && op->res_src_rows < M)) return fail("%s: res_src_rows %lld", who, (long long)op->res_src_rows);
-            if (op->res_rows)
-                for (int r = 0; r < M; ++r)
-                    if (op->res_rows[r] < 0 || op->res_rows[r] >= res_rows_n)
-                        return fail("%s: res_rows[%d] = %d outside [0, %lld)", who, r, op->res_rows[r], (long long)res_rows_n);
-        }
-    }
-    int Bq = 0;
-    int64_t qdim = 0, cache_n = 0;
-    if (qkv) {
-        const int L = op->L, H = op->H, KVH = op->KVH, HD = op->HD, Smax = op->Smax;
-        if (L < 1 || H < 1 || KVH < 1 || HD < 4 || HD % 4 || Smax < 1 || M % L)
-            return fail("%s: bad QKV geometry (L %d, H %d, KVH %d, HD %d, Smax %d, M %d)", who, L, H, KVH, HD, Smax, M);
-        if (op->start_pos < 0 || (int64_t)op->start_pos + L > Smax)
-            return fail("%s: slots [%d, %d) outside the cache's %d", who, op->start_pos, op->start_pos + L, Smax);
-        if (op->col_base != 0 && op->col_base != H * HD) return fail("%s: col_base %d is neither 0 nor H * HD", who, op->col_base);
-        // all of [q | k | v] from col_base on, or the q columns alone (a pruned last block's q launch)
-        if ((int64_t)N + op->col_base != (int64_t)(H + 2 * KVH) * HD && !(op->col_base == 0 && N == H * HD))
-            return fail("%s: N %d + col_base %d is neither (H + 2 KVH) * HD nor the q columns H * HD", who, N, op->col_base);
-        Bq = M / L;
-        qdim = (int64_t)H * HD;
-        if (!op->q_out || op->q_rows < M + 1 || !op->cache_k || !op->cache_v || op->cache_B < Bq + 1)
-            return fail("%s: q_out must hold M + 1 rows and the caches M / L + 1 sequences (guard space)", who);
-        if (!op->rope_cos || !op->rope_sin) return fail("%s: null RoPE table", who);
-        cache_n = (int64_t)op->cache_B * KVH * Smax * HD;
-    }
-    if (op->ws_floats < 0 || op->wb_rows < 0 || op->wb_min_bytes < 0) return fail("%s: negative route control", who);
-    if (bf16 && op->norm && !op->norm_w) return fail("%s: bf16 storage with the norm takes norm_w", who);
-    int64_t parts_d = 0, bak_n = 0;
-    if (dec) {
-        if (dec->storage < 0 || dec->storage > 2) return fail("%s: storage %d outside [0, 2]", who, dec->storage);
-        if (dec->storage && (op->x6 || (dec->storage == 2 && op->bf16)))
-            return fail("%s: one weight storage per launch (storage %d, bf16 %d, x6 %d)", who, dec->storage, op->bf16, op->x6);
-        if (fp8) {
-            if (!dec->wq_codes || !dec->wq_scale) return fail("%s: fp8 storage takes wq_codes and wq_scale", who);
-            if (op->norm && !op->norm_w) return fail("%s: fp8 storage with the norm takes norm_w", who);
-            if (check_fp8_operands(who, dec->wq_codes, dec->wq_scale, N, K)) return 1;
-        }
-        if (dec->parts) {
-            parts_d = epi == EPI_RESID ? N : K;
-            const bool counted = dec->nparts >= 1 && dec->nparts <= GEMV_MAXP;
-            if (dec->parts_rows < 1 || (counted && dec->parts_rows < (int64_t)M * dec->nparts + 1))
-                return fail("%s: parts must hold M * nparts + 1 rows (one of guard space), has %lld", who,
-                            (long long)dec->parts_rows);
-        }
-        if (dec->x_out && (!dec->parts || epi != EPI_SWIGLU || dec->x_out_rows < M + 1))
-            return fail("%s: x_out [M + 1, K] goes with parts on epi 2", who);
-        if (dec->amax_part && dec->amax_part_n < 1) return fail("%s: amax_part_n %d", who, dec->amax_part_n);
-        if (dec->amax_rows && (dec->amax_nct < 1 || dec->amax_rows_rows < M + 1))
-            return fail("%s: amax_rows must hold M + 1 rows of amax_nct >= 1 records (one of guard space)", who);
-        if (dec->state && state_io_check(who, dec->state, 1)) return 1;
-        if ((dec->pos_adv || dec->pos_dev) && !dec->state) return fail("%s: pos_adv / pos_dev take a state", who);
-        if (fold) {
-            for (int i = 0; i < dec->amax_in_n; ++i)
-                if (dec->amax_in[i].i < 0 || dec->amax_in[i].i >= x_rows)
-                    return fail("%s: amax_in[%d].i = %d outside [0, %lld)", who, i, dec->amax_in[i].i, (long long)x_rows);
-        }
-        if ((dec->kv_bak || dec->pos_dev) && !qkv) return fail("%s: kv_bak / pos_dev go with epi 3", who);
-        if (dec->pos_dev && (dec->state->pos < 0 || (int64_t)dec->state->pos + op->L > op->Smax))
-            return fail("%s: slots [%d, %d) of the device position outside the cache's %d", who, dec->state->pos,
-                        dec->state->pos + op->L, op->Smax);
-        if (dec->kv_bak) bak_n = (int64_t)(KV_BAK_SLOTS + 1) * 2 * Bq * op->KVH * op->HD;
-    }
-    if (set_dev(c)) return 1;
-    Scratch S{c};
-    SCRATCH(dx, x_rows * K);
-    SCRATCH(dw, (int64_t)N * K);
-    H2D(dx, op->x, x_rows * K);
-    H2D(dw, op->w, (int64_t)N * K);
-    GemmArgs g{};
-    g.A = dx; g.lda = K; g.W = dw; g.M = M; g.N = N; g.K = K;
-    g.norm = op->norm != 0; g.eps = op->eps;
-    if (op->a_rows) {
-        SCRATCH(da, M);
-        H2D(da, op->a_rows, M);
-        g.a_rows = reinterpret_cast<const int32_t*>(da);
-    }
-    float* dc = nullptr;
-    float *dq = nullptr, *dk = nullptr, *dv = nullptr;
-    if (!qkv) {
-        SCRATCH(dc_, op->c_rows * ldc);
-        dc = dc_;
-        H2D(dc, op->c, op->c_rows * ldc);
-        g.C = dc; g.ldc = ldc;
-        if (op->res_src) {
-            SCRATCH(drs, res_rows_n * ldc);
-            H2D(drs, op->res_src, res_rows_n * ldc);
-            g.res_src = drs;
-            if (op->res_rows) {
-                SCRATCH(drr, M);
-                H2D(drr, op->res_rows, M);
-                g.res_rows = reinterpret_cast<const int32_t*>(drr);
-            }
-        }
-    } else {
-        const int64_t tab = (int64_t)op->Smax * (op->HD / 2);
-        SCRATCH(dq_, op->q_rows * qdim);
-        SCRATCH(dk_, cache_n);
-        SCRATCH(dv_, cache_n);
-        SCRATCH(dcos, tab);
-        SCRATCH(dsin, tab);
-        dq = dq_; dk = dk_; dv = dv_;
-        H2D(dq, op->q_out, op->q_rows * qdim);
-        H2D(dk, op->cache_k, cache_n);
-        H2D(dv, op->cache_v, cache_n);
-        H2D(dcos, op->rope_cos, tab);
-        H2D(dsin, op->rope_sin, tab);
-        g.q_out = dq; g.cache_k = dk; g.cache_v = dv; g.rope_cos = dcos; g.rope_sin = dsin;
-        g.L = op->L; g.start_pos = op->start_pos; g.H = op->H; g.KVH = op->KVH; g.HD = op->HD; g.Smax = op->Smax;
-        g.q_scale = op->q_scale; g.col_base = op->col_base;
-    }
-    if (op->ws_floats > 0) {
-        SCRATCH(dws, op->ws_floats);
-        g.ws = dws; g.ws_cap = op->ws_floats;
-    }
-    g.force_skinny = op->force_skinny != 0;
-    g.force_tiled = op->force_tiled;
-    if (bf16) {
-        // finalize_compact's bf16 round mode: Wb = bf16(w), W = float(Wb); the norm weight stays beside Wb
-        // and is folded into the fp32 copy, which then holds the same model for the fp32 routes
-        SCRATCH(dwb, ((int64_t)N * K + 1) / 2);
-        SCRATCH(dcnt, 4);
-        HIP_TRY(hipMemsetAsync(dcnt, 0, 16, c->stream));
-        HIP_TRY(launch_to_bf16(dw, reinterpret_cast<unsigned short*>(dwb), (int64_t)N * K, 0, true,
-                               reinterpret_cast<unsigned long long*>(dcnt), c->stream));
-        g.Wb = reinterpret_cast<const unsigned short*>(dwb);
-        if (op->norm_w) {
-            SCRATCH(dnw, K);
-            H2D(dnw, op->norm_w, K);
-            g.norm_w = dnw;
-            if (g.norm) HIP_TRY(launch_fold_cols(dw, N, K, dnw, c->stream));
-        }
-        g.wb_rows = op->wb_rows; g.wb_min_bytes = op->wb_min_bytes;
-    }
-    if (op->x6) {
-        SCRATCH(dw3, ((int64_t)N * 3 * K + 1) / 2);
-        HIP_TRY(launch_split_planes(dw, reinterpret_cast<unsigned short*>(dw3), N, K, c->stream));
-        g.W3 = reinterpret_cast<const unsigned short*>(dw3);
-    }
-    StateDev sd;
-    float *dxo = nullptr, *dbak = nullptr;
-    ArgmaxPart *dap = nullptr, *dar = nullptr;
-    int32_t* dids = nullptr;
-    if (dec) {
-        dec->amax_blocks = 0;
-        if (fp8) {
-            // the codes and scales as l3_op_linear_fp8_host takes them; the norm weight stays beside
-            // them and is folded into the fp32 copy, as with bf16 storage
-            SCRATCH(dwq, ((int64_t)N * K + 3) / 4);
-            SCRATCH(dwsc, N);
-            HIP_TRY(hipMemcpyAsync(dwq, dec->wq_codes, (size_t)N * K, hipMemcpyHostToDevice, c->stream));
-            H2D(dwsc, dec->wq_scale, N);
-            g.Wq = reinterpret_cast<const unsigned char*>(dwq); g.wq_scale = dwsc;
-            if (op->norm_w) {
-                SCRATCH(dnw, K);
-                H2D(dnw, op->norm_w, K);
-                g.norm_w = dnw;
-                if (g.norm) HIP_TRY(launch_fold_cols(dw, N, K, dnw, c->stream));
-            }
-            g.wb_rows = op->wb_rows; g.wb_min_bytes = op->wb_min_bytes;
-        }
-        if (dec->state && state_io_upload(c, S, dec->state, &sd)) return 1;
-        if (dec->parts) {
-            SCRATCH(dp, dec->parts_rows * parts_d);
-            H2D(dp, dec->parts, dec->parts_rows * parts_d);
-            g.parts = dp; g.nparts = dec->nparts;
-        }
-        if (dec->x_out) {
-            SCRATCH(sxo, dec->x_out_rows * K);
-            H2D(sxo, dec->x_out, dec->x_out_rows * K);
-            g.x_out = dxo = sxo;
-        }
-        if (dec->amax_part) {
-            const int blocks = epi == EPI_STORE ? gemv_store_blocks(g) : 0;  // (0: the dispatcher refuses)
-            if (blocks && dec->amax_part_n < blocks + 1)
-                return fail("%s: amax_part_n %d holds fewer than the launch's %d blocks + 1 (guard space)", who,
-                            dec->amax_part_n, blocks);
-            SCRATCH(sap, 2LL * dec->amax_part_n);
-            H2D(sap, dec->amax_part, 2LL * dec->amax_part_n);
-            g.amax_part = dap = reinterpret_cast<ArgmaxPart*>(sap);
-            dec->amax_blocks = blocks;
-        }
-        if (dec->pos_adv) g.pos_adv = sd.st;
-        if (dec->amax_rows) {
-            SCRATCH(sar, 2 * dec->amax_rows_rows * dec->amax_nct);
-            H2D(sar, dec->amax_rows, 2 * dec->amax_rows_rows * dec->amax_nct);
-            g.amax_rows = dar = reinterpret_cast<ArgmaxPart*>(sar);
-            g.amax_nct = dec->amax_nct;
-        }
-        if (fold) {
-            const int n = dec->amax_in_n > 0 ? dec->amax_in_n : 0;
-            SCRATCH(sai, 2LL * (n > 0 ? n : 1));
-            if (n) H2D(sai, dec->amax_in, 2LL * n);
-            g.amax_in = reinterpret_cast<const ArgmaxPart*>(sai); g.amax_in_n = dec->amax_in_n;
-            if (dec->amax_ids) {
-                SCRATCH(di, 2);
-                H2D(di, dec->amax_ids, 2);
-                g.amax_ids = dids = reinterpret_cast<int32_t*>(di);
-            }
-            g.amax_st = sd.st;
-        }
-        if (dec->kv_bak) {
-            SCRATCH(sbak, bak_n);
-            H2D(sbak, dec->kv_bak, bak_n);
-            g.kv_bak = dbak = sbak;
-        }
-        if (dec->pos_dev) {
-            // the position travels in the state's first word; the argument holds another (in-range)
-            // one, so a kernel that read the argument would write the wrong slot
-            g.pos_dev = &sd.st->pos;
-            g.start_pos = dec->state->pos > 0 ? 0 : (op->L < op->Smax ? 1 : 0);
-        }
-    }
-    if (g.Wb) {
-        if (gemm_takes_bf16_rows(epi, g)) c->wb_rows_launches += 1;
-        else if (gemm_takes_bf16(epi, g)) c->wb_launches += 1;
-    } else if (g.Wq) {
-        if (gemm_takes_fp8_rows(epi, g)) c->wq_rows_launches += 1;
-        else if (gemm_takes_fp8(epi, g)) c->wq_launches += 1;
-    }
-    gemm_route_reset();
-    if (const hipError_t e = launch_gemm(epi, g, c->stream); e != hipSuccess) {
-        (void)hipStreamSynchronize(c->stream);
-        if (e != hipErrorInvalidValue) return fail("%s: launch_gemm failed: %s", who, hipGetErrorString(e));
-        // the dispatcher's refusals of the captured-decode arguments, in its own order: a restatement
-        // of launch_gemm's conditions (gemm.hip, from `if (a.parts)` down to the amax_in block) that
-        // only chooses the message — the refusal itself is the dispatcher's, so a condition added
-        // there and not here still fails, under the general message below.  Keep the two in step;
-        // tests/test_gpu_decode_gemv.py raises each of these by name.
-        if (dec && K % 32 == 0 && N % 4 == 0 && !(epi == EPI_SWIGLU && N % 32)) {
-            if (g.parts) {
-                if (epi != EPI_RESID && epi != EPI_SWIGLU) return fail("%s: parts go with epi 1 / 2, not epi %d", who, epi);
-                if (g.nparts < 1 || g.nparts > GEMV_MAXP) return fail("%s: nparts %d outside [1, %d]", who, g.nparts, GEMV_MAXP);
-                if (!gemv_direct(g))
-                    return fail("%s: parts take the one-row GEMV's range, not %d x %d x %d", who, M, K, N);
-            }
-            if (g.amax_part && (epi != EPI_STORE || !gemv_store_blocks(g)))
-                return fail("%s: amax_part takes epi 0 with M == 1 on the GEMV (epi %d, %d x %d x %d)", who, epi, M, K, N);
-            if (g.amax_rows && (epi != EPI_STORE || gemm_store_config(g) == 0 || g.ws || g.amax_nct != (N + 63) / 64))
-                return fail("%s: amax_rows takes epi 0 on the tiled kernels, no split-K workspace and amax_nct == "
-                            "ceil(N / 64) = %d (epi %d, amax_nct %d)", who, (N + 63) / 64, epi, g.amax_nct);
-            if (g.pos_adv && !g.amax_part) return fail("%s: pos_adv goes with amax_part", who);
-            if (g.amax_in) {
-                if (epi != EPI_QKV) return fail("%s: amax_in goes with epi 3, not epi %d", who, epi);
-                if (M != 1) return fail("%s: amax_in takes M == 1 (M %d)", who, M);
-                if (!gemv_direct(g)) return fail("%s: amax_in takes the one-row GEMV's range, not %d x %d x %d", who, M, K, N);
-                if (g.col_base) return fail("%s: amax_in takes no col_base (%d)", who, g.col_base);
-                if (g.a_rows) return fail("%s: amax_in takes no a_rows (the id selects the row)", who);
-                if (g.amax_in_n < 1) return fail("%s: amax_in_n %d", who, g.amax_in_n);
-                if (!g.amax_ids) return fail("%s: amax_in takes amax_ids", who);
-                if (!g.amax_st) return fail("%s: amax_in takes a state", who);
-            }
-        }
-        return fail("%s: launch_gemm refused epi %d, %d x %d x %d (no other kernel stands in)", who, epi, M, K, N);
-    }
-    const GemmRoute rt = gemm_last_route();
-    if (!qkv) {
-        D2H(op->c, dc, op->c_rows * ldc);
-    } else {
-        D2H(op->q_out, dq, op->q_rows * qdim);
-        D2H(op->cache_k, dk, cache_n);
-        D2H(op->cache_v, dv, cache_n);
-    }
-    if (dxo) D2H(dec->x_out, dxo, dec->x_out_rows * K);
-    if (dap) D2H(dec->amax_part, dap, 2LL * dec->amax_part_n);
-    if (dar) D2H(dec->amax_rows, dar, 2 * dec->amax_rows_rows * dec->amax_nct);
-    if (dids) D2H(dec->amax_ids, dids, 2);
-    if (dbak) D2H(dec->kv_bak, dbak, bak_n);
-    if (sd.st && state_io_download(c, sd, dec->state)) return 1;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    op->route[0] = rt.family;
-    for (int i = 0; i < 5; ++i) op->route[1 + i] = rt.v[i];
-    op->route[6] = (int32_t)rt.launches;
-    return 0;
-}
-
-extern "C" int l3_op_gemm_host(l3_ctx* c, l3_gemm_op* op) {
-    CHECK_CTX(c);
-    const char* who = "l3_op_gemm";
-    if (!op) return fail("%s: null argument", who);
-    if (op->struct_size != (int32_t)sizeof(l3_gemm_op))
-        return fail("%s: struct_size %d, this library's l3_gemm_op has %d bytes", who, op->struct_size, (int)sizeof(l3_gemm_op));
-    return op_gemm_impl(c, who, op, nullptr);
-}
-
-extern "C" int l3_op_decode_gemm_host(l3_ctx* c, l3_decode_gemm_op* op) {
-    CHECK_CTX(c);
-    const char* who = "l3_op_decode_gemm";
-    if (!op) return fail("%s: null argument", who);
-    if (op->struct_size != (int32_t)sizeof(l3_decode_gemm_op))
-        return fail("%s: struct_size %d, this library's l3_decode_gemm_op has %d bytes", who, op->struct_size,
-                    (int)sizeof(l3_decode_gemm_op));
-    if (op->g.struct_size != (int32_t)sizeof(l3_gemm_op))
-        return fail("%s: g.struct_size %d, this library's l3_gemm_op has %d bytes", who, op->g.struct_size, (int)sizeof(l3_gemm_op));
-    return op_gemm_impl(c, who, &op->g, op);
-}
-
-// argmax_parts_kernel on plain arrays (include/llama3hip.h): rows x n candidates, optionally with
-// a decode state built as l3_op_decode_gemm_host builds it
-extern "C" int l3_op_argmax_parts_host(l3_ctx* c, const l3_argmax_part* parts, int32_t rows, int32_t n, int32_t hist_off,
-                                       l3_dec_state_io* state, int32_t* ids) {
-    CHECK_CTX(c);
-    const char* who = "l3_op_argmax_parts";
-    if (!parts || !ids) return fail("%s: null argument", who);
-    if (rows < 1 || rows > 65535 || n < 1 || (int64_t)rows * n > INT32_MAX / 2) return fail("%s: bad shape %d x %d", who, rows, n);
-    if (hist_off != 0 && hist_off != 1) return fail("%s: hist_off %d is neither 0 nor 1", who, hist_off);
-    if (state && state_io_check(who, state, rows)) return 1;
-    if (set_dev(c)) return 1;
-    Scratch S{c};
-    SCRATCH(dp, 2LL * rows * n);
-    SCRATCH(di, rows + 1);
-    H2D(dp, parts, 2LL * rows * n);
-    H2D(di, ids, rows + 1);
-    StateDev sd;
-    if (state && state_io_upload(c, S, state, &sd)) return 1;
-    HIP_TRY(launch_argmax_parts(reinterpret_cast<const ArgmaxPart*>(dp), n, reinterpret_cast<int32_t*>(di), c->stream, sd.st,
-                                hist_off, rows));
-    D2H(ids, di, rows + 1);
-    if (sd.st && state_io_download(c, sd, state)) return 1;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-// kv_restore_kernel without a guard on plain arrays (include/llama3hip.h)
-extern "C" int l3_op_kv_restore_host(l3_ctx* c, float* cache, int64_t cache_B, const float* bak, int32_t B, int32_t KVH,
-                                     int32_t Smax, int32_t HD, int32_t pos) {
-    CHECK_CTX(c);
-    const char* who = "l3_op_kv_restore";
-    if (!cache || !bak) return fail("%s: null argument", who);
-    if (B < 1 || KVH < 1 || Smax < 1 || HD < 1 || cache_B < (int64_t)B + 1)
-        return fail("%s: bad shape (B %d, KVH %d, Smax %d, HD %d, cache_B %lld: B + 1 with the guard)", who, B, KVH, Smax, HD,
-                    (long long)cache_B);
-    const int64_t nc = cache_B * KVH * Smax * HD, nb = (int64_t)B * KVH * HD;
-    if (nc > INT32_MAX) return fail("%s: a cache of more than 2^31 elements", who);
-    if (pos < 0 || pos >= Smax) return fail("%s: pos %d outside [0, %d)", who, pos, Smax);
-    if (set_dev(c)) return 1;
-    Scratch S{c};
-    SCRATCH(dc, nc);
-    SCRATCH(db, nb);
-    H2D(dc, cache, nc);
-    H2D(db, bak, nb);
-    HIP_TRY(launch_kv_restore(dc, db, B, KVH, Smax, HD, pos, c->stream));
-    D2H(cache, dc, nc);
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
 // The persistent step's instance for a shape, (NCD, NCF, KPF, LMPF): a restatement of
 // decode_persist.hip's L3_PERSIST_INSTANCES / persist_instance (that file keeps its table to
 // itself), for l3_op_decode_persist_host's route report and refusal messages only — the launch
@@ -4267,18 +2910,15 @@ extern "C" int l3_op_decode_persist_host(l3_ctx* c, l3_decode_persist_op* op) {
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (persist_failed(c)) return fail("%s: an earlier persistent step's failure is not recovered", who);
 
-    Scratch S{c};
+    Staging S(c);
     StateDev sd;
-    if (state_io_upload(c, S, op->state, &sd)) return 1;
-    SCRATCH(dids, 2);
+    if (state_io_upload(S, op->state, &sd)) return 1;
+    int32_t* dids = S.alloc<int32_t>(2);
+    if (S.failed()) return 1;
     const int32_t ids0[2] = {op->token, -7};
     HIP_TRY(hipMemcpy(dids, ids0, sizeof ids0, hipMemcpyHostToDevice));
-    float* dbak = nullptr;
-    if (op->use_kv_bak) {
-        SCRATCH(sbak, op->kv_bak_n);
-        H2D(sbak, op->kv_bak, op->kv_bak_n);
-        dbak = sbak;
-    }
+    float* dbak = op->use_kv_bak ? S.inout(op->kv_bak, op->kv_bak_n) : nullptr;
+    if (S.failed()) return 1;
     unsigned tag = 0;
     {
         // another context's queued decode graphs first: the step needs every CU (launch_decode_graph)
@@ -4287,7 +2927,7 @@ extern "C" int l3_op_decode_persist_host(l3_ctx* c, l3_decode_persist_op* op) {
         if (d.ev && d.owner != c) HIP_TRY(hipStreamWaitEvent(c->stream, d.ev, 0));
         for (int i = 0; i < op->steps; ++i) {
             DecodePersistArgs a = c->persist;
-            a.ids = reinterpret_cast<int32_t*>(dids);
+            a.ids = dids;
             a.st = sd.st;
             a.kv_bak = dbak;
             a.from_parts = i > 0;
@@ -4310,8 +2950,8 @@ extern "C" int l3_op_decode_persist_host(l3_ctx* c, l3_decode_persist_op* op) {
     HIP_TRY(hipMemcpy(op->lm_parts, c->persist.gran + slab * nl, (size_t)512 * 8, hipMemcpyDeviceToHost));
     int32_t ids1[2] = {0, 0};
     HIP_TRY(hipMemcpy(ids1, dids, sizeof ids1, hipMemcpyDeviceToHost));
-    if (dbak) D2H(op->kv_bak, dbak, op->kv_bak_n);
-    if (state_io_download(c, sd, op->state)) return 1;
+    if (S.finish()) return 1;
+    state_io_result(sd, op->state);
     for (int i = 0; i < 3; ++i) op->epoch[i] = ep[i];
     op->tag = tag;
     op->err = *reinterpret_cast<volatile unsigned*>(c->persist_err);
@@ -4324,86 +2964,6 @@ extern "C" int l3_op_decode_persist_host(l3_ctx* c, l3_decode_persist_op* op) {
         // and reported — the outputs above are what the failed launch left
         if (persist_recover(c, nullptr)) return 1;
         return fail("%s: a workgroup gave up on a hand-off at position %d", who, (int)op->err - 1);
-    }
-    return 0;
-}
-
-// One launch_attention / launch_attention_last call on plain host arrays (include/llama3hip.h).
-// Only what would take an index outside a buffer is checked ahead of the dispatcher (null arrays,
-// sizes, the key range); every shape rule is the dispatcher's own, and what it refuses is named
-// here afterwards — no other kernel stands in, and out is not written.
-extern "C" int l3_op_attention_host(l3_ctx* c, const float* q, const float* cache_k, const float* cache_v, int32_t B,
-                                    int32_t L, int32_t start_pos, int32_t H, int32_t KVH, int32_t HD, int32_t Smax,
-                                    int32_t mode, const float* wo, int32_t D, float* out, int64_t out_rows,
-                                    int32_t* route) {
-    CHECK_CTX(c);
-    const char* who = "l3_op_attention";
-    if (route)
-        for (int i = 0; i < 8; ++i) route[i] = 0;
-    if (!q || !cache_k || !cache_v || !out) return fail("%s: null argument", who);
-    if (mode < 0 || mode > 3) return fail("%s: mode %d outside [0, 3]", who, mode);
-    const bool last = mode & 1, pos_dev = mode & 2;
-    if (B < 1 || B > 65535 || L < 1 || H < 1 || H > 65535 || KVH < 1 || HD < 4 || HD % 4 || Smax < 1)
-        return fail("%s: bad shape (B %d, L %d, H %d, KVH %d, head size %d, Smax %d)", who, B, L, H, KVH, HD, Smax);
-    if (start_pos < 0 || (int64_t)start_pos + L > Smax)
-        return fail("%s: keys [0, %lld) exceed Smax %d (start_pos %d + L %d)", who, (long long)start_pos + L, Smax,
-                    start_pos, L);
-    if (wo && D < 1) return fail("%s: D = %d with wo", who, D);
-    const int64_t width = wo ? (int64_t)H * D : (int64_t)H * HD;
-    const int64_t nq = (int64_t)B * L * H * HD, nc = (int64_t)B * KVH * Smax * HD, no = out_rows * width;
-    if (out_rows < (int64_t)B * L + 1)
-        return fail("%s: out must hold B * L + 1 = %lld rows (one of guard space)", who, (long long)B * L + 1);
-    if (nq > INT32_MAX || nc > INT32_MAX || no > INT32_MAX) return fail("%s: arrays of more than 2^31 elements", who);
-    if (set_dev(c)) return 1;
-    Scratch S{c};
-    SCRATCH(dq, nq);
-    SCRATCH(dk, nc);
-    SCRATCH(dv, nc);
-    SCRATCH(dout, no);
-    SCRATCH(dpos, 1);
-    H2D(dq, q, nq);
-    H2D(dk, cache_k, nc);
-    H2D(dv, cache_v, nc);
-    H2D(dout, out, no);
-    AttnArgs a{};
-    a.q = dq; a.cache_k = dk; a.cache_v = dv;
-    a.B = B; a.L = L; a.start_pos = start_pos; a.H = H; a.KVH = KVH; a.HD = HD; a.Smax = Smax;
-    if (wo) {
-        SCRATCH(dwo, (int64_t)D * H * HD);
-        H2D(dwo, wo, (int64_t)D * H * HD);
-        a.wo = dwo; a.parts = dout; a.D = D;
-    } else {
-        a.out = dout;
-    }
-    if (pos_dev) {
-        // the position travels in the device word; the argument holds another (in-range) one, so a
-        // kernel that read the argument would attend over the wrong keys
-        H2D(dpos, &start_pos, 1);
-        a.pos_dev = reinterpret_cast<const int*>(dpos);
-        a.start_pos = start_pos > 0 ? 0 : (L < Smax ? 1 : 0);
-    }
-    AttnRoute rt;
-    const hipError_t e = last ? launch_attention_last(a, c->stream, &rt) : launch_attention(a, c->stream, &rt);
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(c->stream);
-        if (e != hipErrorInvalidValue) return fail("%s: the launch failed: %s", who, hipGetErrorString(e));
-        // the dispatcher's refusals, in its own order
-        if (H % KVH) return fail("%s: n_heads %% n_kv_heads != 0 (H %d, KVH %d)", who, H, KVH);
-        if (last && (wo || pos_dev))
-            return fail("%s: the last-rows launch takes neither wo nor a device position (mode %d)", who, mode);
-        if (wo && (L != 1 || Smax > 8192))
-            return fail("%s: the fused O-proj is a decode launch: L == 1 and Smax <= 8192 (L %d, Smax %d)", who, L, Smax);
-        if (HD != 16 && HD != 32 && HD != 48 && HD != 64 && HD != 96 && HD != 128)
-            return fail("%s: head size %d has no attention instantiation (16, 32, 48, 64, 96, 128)", who, HD);
-        if (wo && D % 4) return fail("%s: D %d must be a multiple of 4 with wo", who, D);
-        return fail("%s: the dispatcher refused the launch (no other kernel stands in)", who);
-    }
-    if (rt.kernel == ATTN_NONE) return fail("%s: the dispatcher launched nothing", who);
-    D2H(out, dout, no);
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (route) {
-        route[0] = rt.kernel; route[1] = rt.HD; route[2] = rt.QBW; route[3] = rt.G; route[4] = rt.KT;
-        for (int i = 0; i < 3; ++i) route[5 + i] = rt.grid[i];
     }
     return 0;
 }
@@ -4429,9 +2989,9 @@ static int score_row_bufs(l3_ctx* c, int64_t rows) {
 // A [rows, K] (row stride lda) against W [N, K]: logprob / lse / argmax of rows (device, the last
 // two optional).  The kernel configuration comes from the call's row count and holds for every
 // chunk, so a row's bits do not depend on the workspace size.
-static int score_lm(l3_ctx* c, const float* A, int64_t lda, int64_t rows, int K, int N, const float* W, bool norm,
-                    const int32_t* targets_dev, float* tgt_logit_dev, float* logprob_dev, float* lse_dev,
-                    int32_t* argmax_dev) {
+int l3rt::score_lm(l3_ctx* c, const float* A, int64_t lda, int64_t rows, int K, int N, const float* W, bool norm,
+                   const int32_t* targets_dev, float* tgt_logit_dev, float* logprob_dev, float* lse_dev,
+                   int32_t* argmax_dev) {
     const int64_t row_bytes = score_row_bytes(N);
     const int64_t chunk = c->score_ws_bytes / row_bytes / 256 * 256;
     if (chunk < 256)
@@ -4477,16 +3037,6 @@ extern "C" int l3_set_score_workspace(l3_ctx* c, int64_t bytes) {
     return 0;
 }
 
-// targets [T]: -1 (no target) or a column of [0, N); checked before any launch
-template <typename Tgt>
-static int check_targets(const char* who, const Tgt* t, int64_t T, int64_t N) {
-    for (int64_t i = 0; i < T; ++i)
-        if (t[i] < -1 || t[i] >= N)
-            return fail("%s: target %lld at %lld outside [0, %lld) (-1: no target)", who, (long long)t[i],
-                        (long long)i, (long long)N);
-    return 0;
-}
-
 extern "C" int l3_score_host(l3_ctx* c, const int64_t* ids_host, const int64_t* targets_host, int32_t B, int32_t L,
                              int32_t start_pos, float* logprobs_host, int32_t* argmax_host) {
     CHECK_CTX(c);
@@ -4515,34 +3065,6 @@ extern "C" int l3_score_host(l3_ctx* c, const int64_t* ids_host, const int64_t* 
         return 1;
     HIP_TRY(hipMemcpyAsync(logprobs_host, lp, (size_t)T * 4, hipMemcpyDeviceToHost, c->stream));
     if (am) HIP_TRY(hipMemcpyAsync(argmax_host, am, (size_t)T * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-extern "C" int l3_op_linear_logprob_host(l3_ctx* c, const float* x, int64_t rows, int32_t K, int32_t N,
-                                         const float* w, const int32_t* targets, float* logprob, float* lse,
-                                         int32_t* argmax) {
-    CHECK_CTX(c);
-    if (rows <= 0 || rows > INT32_MAX || N <= 0 || K <= 0)
-        return fail("l3_op_linear_logprob: bad shape %lld x %d x %d", (long long)rows, K, N);
-    if (K % 32) return fail("l3_op_linear_logprob: K=%d must be a multiple of 32", K);
-    if (N % 4) return fail("l3_op_linear_logprob: N=%d must be a multiple of 4", N);
-    if (!x || !w || !targets || !logprob) return fail("l3_op_linear_logprob: null argument");
-    if (check_targets("l3_op_linear_logprob", targets, rows, N)) return 1;
-    if (set_dev(c)) return 1;
-    Scratch S{c};
-    SCRATCH(dx, rows * K);
-    SCRATCH(dw, (int64_t)N * K);
-    SCRATCH(dr, rows * 5);
-    H2D(dx, x, rows * K);
-    H2D(dw, w, (int64_t)N * K);
-    H2D(dr, targets, rows);
-    if (score_lm(c, dx, K, rows, K, N, dw, false, reinterpret_cast<int32_t*>(dr), dr + rows, dr + 2 * rows,
-                 lse ? dr + 3 * rows : nullptr, argmax ? reinterpret_cast<int32_t*>(dr + 4 * rows) : nullptr))
-        return 1;
-    D2H(logprob, dr + 2 * rows, rows);
-    if (lse) D2H(lse, dr + 3 * rows, rows);
-    if (argmax) D2H(argmax, dr + 4 * rows, rows);
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -4901,13 +3423,11 @@ extern "C" int l3_comm_barrier(l3_ctx* c) {
     if (!c->comm) return fail("l3_comm_barrier: communicator not initialised");
     if (c->group) return fail("l3_comm_barrier: this context is a member of an l3_group (use l3_group_*)");
     if (set_dev(c)) return 1;
-    float* one = nullptr;
-    if (!c->scratch.empty()) one = (float*)c->scratch[0];
-    else {
-        HIP_TRY(hipMalloc(&one, 4));
-        c->scratch.push_back(one);
-        HIP_TRY(hipMemsetAsync(one, 0, 4, c->stream));  // the sum stays 0: no inf/NaN over time
+    if (!c->barrier_buf) {
+        HIP_TRY(hipMalloc(&c->barrier_buf, 4));
+        HIP_TRY(hipMemsetAsync(c->barrier_buf, 0, 4, c->stream));  // the sum stays 0: no inf/NaN over time
     }
+    float* one = c->barrier_buf;
     NCCL_TRY(ncclAllReduce(one, one, 1, ncclFloat32, ncclSum, c->comm, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
